@@ -2,6 +2,8 @@
 """bench.py -- BASELINE.json's metric on MI355X: "BLS12-381 G1 scalar-muls/sec at MSM size 2^20; shuffle proofs verified/sec".
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full   # + every side measurement and check (see --full below)
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR    # + the last timed step's MSM result as DIR/*.npy
     python bench.py --gpus N --steps K --warmup W          # spawns its own N ranks (fresh child processes, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W               # or under a launcher that exports RANK / LOCAL_RANK / WORLD_SIZE
@@ -24,6 +26,12 @@ proofs (the 1024 DISTINCT ell = 124 proofs of tests/golden/shuffle_batch_ell124{
 fresh random weights per slot) from wire bytes in host memory to verdicts, with per-phase times, its own cpu_baseline and the
 integer-MAD roofline of its dominant kernel k_batch_decompress.  `--mode verify` runs that part alone (and proof-per-GPU at N>1:
 BASELINE configs[4]'s structure).
+
+A plain run (`--mode msm`, the default) sets up, warms up, times the `--steps` steps and prints the headline line (with the
+`roofline` of k_accumulate as timed in those steps).  `--full` adds what takes runs or checks of its own: the timed MSM against
+its closed form, the per-phase table, the other seeds, two calls in flight, the N>1 side records, roofline_int_mad with its
+same-run peak and madd probe, the CPU baselines, the secondary metric and the python_face / unchanged_control_flow objects
+(the --no-* options still drop pieces of it).
 """
 import argparse
 import json
@@ -54,6 +62,19 @@ def raw96_gen():
     gx = 0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB
     gy = 0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1
     return gx.to_bytes(48, "little") + gy.to_bytes(48, "little")
+
+
+def dump_outputs(out_dir, N, blob):
+    """--dump-outputs: what a caller of the timed path receives -- the G1 point of the last timed step -- in canonical affine form
+    (independent of the internal coordinates), as float64 so that two builds can be compared output for output."""
+    import ctypes
+
+    import numpy as np
+
+    aff = ctypes.create_string_buffer(96)
+    N.cg1_to_affine96(aff, blob)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result_affine.npy"), np.frombuffer(aff.raw, dtype=np.uint8).reshape(2, 48).astype(np.float64))
 
 
 def mad_peak_same_run(ctx):
@@ -503,8 +524,14 @@ def main():
     ap.add_argument("--verify-mode", choices=["merged", "independent"], default="merged")
     ap.add_argument("--front-end", choices=["auto", "host", "device"], default="auto",
                     help="verifier front-end (transcript, D / A', challenge algebra): host threads, k_shuffle_front_end, or by the threads available")
+    ap.add_argument("--full", action="store_true", help="--mode msm: besides the headline, every side measurement and check (closed form, "
+                                                         "per-phase table, seeds, two calls in flight, N>1 records, roofline_int_mad, CPU "
+                                                         "baselines, secondary metric, python face); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--mode msm: write the last timed step's MSM result to DIR/msm_result_affine.npy (float64 [2, 48]: the affine x "
+                         "and y coordinates, 48 little-endian bytes each; all zero for the identity)")
     ap.add_argument("--mode", choices=["msm", "batched", "pcie", "verify"], default="msm",
-                    help="msm: the driver's line (headline MSM + secondary proofs/s). batched: BASELINE config 3's MSM content (1024 independent "
+                    help="msm: the driver's line (headline MSM; + secondary proofs/s with --full). batched: BASELINE config 3's MSM content (1024 independent "
                          "627-term accumulator MSMs per step, regime B). verify: BASELINE config 3 end to end alone (and config 5's structure at "
                          "N>1). pcie: the headline MSM with inputs in HOST memory")
     ap.add_argument("--backend", choices=["rccl", "socket", "nccl", "gloo"], default="rccl",
@@ -514,6 +541,8 @@ def main():
     ap.add_argument("--allow-socket", action="store_true", help="N > 1 with one GPU per rank: keep going on the TCP transport when RCCL cannot be attached "
                                                                  "(default: exit non-zero -- a scaling run must not silently stop being an RCCL run)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "msm":
+        ap.error("--dump-outputs is only supported with --mode msm")
 
     if args.batch is None:
         args.batch = 2048 if (args.mode == "verify" and args.gpus > 1) else 1024
@@ -664,12 +693,15 @@ def main():
         return rec
 
     n_per_gpu = 1 << args.logn
-    main_rec = run(args.shard, n_per_gpu, args.seed, args.steps, args.warmup, check=True)
-    # the per-phase table: a few more steps with an event around every phase (not the timed region)
-    main_rec["phases_ms_detailed"] = run(args.shard, n_per_gpu, args.seed, max(3, args.steps // 4), 1, detail=True)["phases_ms"]
+    main_rec = run(args.shard, n_per_gpu, args.seed, args.steps, args.warmup, check=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, N, main_rec["result"])
+    if args.full:
+        # the per-phase table: a few more steps with an event around every phase (not the timed region)
+        main_rec["phases_ms_detailed"] = run(args.shard, n_per_gpu, args.seed, max(3, args.steps // 4), 1, detail=True)["phases_ms"]
 
     extra = {}
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # the reference's input distribution at three seeds: short side-by-side runs outside the timed region
         seeds = {}
         for s in (1, 2, 3):
@@ -716,7 +748,7 @@ def main():
             except Exception:
                 pmc = None
         ctx.set_param("profile", 0)
-        peak = mad_peak_same_run(ctx)
+        peak = mad_peak_same_run(ctx) if args.full else None
         out = {
             "metric": "BLS12-381 G1 scalar-muls/sec at MSM size 2^20",
             "value": r["value"],
@@ -748,23 +780,26 @@ def main():
                                          "bytes; achieved = 128 B x terms / the two launches' summed duration = 64 B x terms / one launch's average"
                                          if launches == 2 else "one k_accumulate launch per call"),
                          "note": "path is integer-multiply (v_mad_u64_u32) bound, not HBM-bound: see roofline_int_mad and DESIGN.md"},
-            # The bound that actually applies: 32x32+64 integer multiply-adds.  Algorithmic MADs of one
-            # k_accumulate launch = the additions it really performs (bucket entries minus one copy per chunk, both counted on
-            # the device in this run): 3542 each, 1974 for the first one of a chunk; peak = the chip-wide v_mad_u64_u32 rate
-            # measured by tools/ubench_valu.hip.
-            "roofline_int_mad": {"bound": "valu v_mad_u64_u32", "achieved": mads / (acc_ms * 1e-3) / 1e12, "peak": peak["peak_T"],
-                                 "unit": "T mad/s", "frac": mads / (acc_ms * 1e-3) / (peak["peak_T"] * 1e12), "kernel": "k_accumulate",
-                                 "kernel_ms": acc_ms / launches, "launches_per_step": launches, "kernel_ms_per_step": acc_ms, "peak_same_run": peak,
-                                 "peak_round1_other_box": MAD_PEAK_T,
-                                 "mixed_adds_per_launch": madds, "bucket_entries": r["counts"]["entries"], "chunks": r["counts"]["chunks"],
-                                 "mads_per_mixed_add": MADS_PER_MADD, "first_additions_of_chunks": pair_adds, "mads_per_first_addition": MADS_PER_MMADD,
-                                 "valu_per_wave_mixed_add": (pmc or {}).get("k_accumulate_valu_per_wave_mixed_add"),
-                                 "valu_source": (pmc or {}).get("sq_source")},
-            "phases_ms": dict(r["phases_ms_detailed"], note="from extra steps with a hipEvent around every phase; the timed region brackets only "
-                                                                 "k_accumulate (roofline.kernel_ms)"),
             "per_rank_ms_per_step": r["per_rank_ms_per_step"],
         }
         out.update(extra)
+        if args.full:
+            out.update({
+                # The bound that actually applies: 32x32+64 integer multiply-adds.  Algorithmic MADs of one
+                # k_accumulate launch = the additions it really performs (bucket entries minus one copy per chunk, both counted on
+                # the device in this run): 3542 each, 1974 for the first one of a chunk; peak = the chip-wide v_mad_u64_u32 rate
+                # measured by tools/ubench_valu.hip.
+                "roofline_int_mad": {"bound": "valu v_mad_u64_u32", "achieved": mads / (acc_ms * 1e-3) / 1e12, "peak": peak["peak_T"],
+                                     "unit": "T mad/s", "frac": mads / (acc_ms * 1e-3) / (peak["peak_T"] * 1e12), "kernel": "k_accumulate",
+                                     "kernel_ms": acc_ms / launches, "launches_per_step": launches, "kernel_ms_per_step": acc_ms, "peak_same_run": peak,
+                                     "peak_round1_other_box": MAD_PEAK_T,
+                                     "mixed_adds_per_launch": madds, "bucket_entries": r["counts"]["entries"], "chunks": r["counts"]["chunks"],
+                                     "mads_per_mixed_add": MADS_PER_MADD, "first_additions_of_chunks": pair_adds, "mads_per_first_addition": MADS_PER_MMADD,
+                                     "valu_per_wave_mixed_add": (pmc or {}).get("k_accumulate_valu_per_wave_mixed_add"),
+                                     "valu_source": (pmc or {}).get("sq_source")},
+                "phases_ms": dict(r["phases_ms_detailed"], note="from extra steps with a hipEvent around every phase; the timed region brackets only "
+                                                                     "k_accumulate (roofline.kernel_ms)")
+            })
         if world > 1:
             out["collective"] = {"backend": comm.transport, "backend_note": getattr(comm, "note", None), "world_seen": comm.world_seen,
                                  "world_seen_source": "ncclCommCount" if comm.transport == "rccl" else "ranks connected to the TCP hub",
@@ -775,7 +810,7 @@ def main():
             out["measured_on"] = ("%d ranks, one GPU each: a measured multi-GPU line" % world) if not args.same_device else \
                                  ("%d ranks REHEARSING on one GPU (--same-device): not a scaling measurement" % world)
             out["predicted_ms_per_step_emulated"] = EMULATED_MS.get(args.shard, {}).get(world)
-        if world == 1:
+        if world == 1 and args.full:
             # the practical ceiling of the same arithmetic: chains of dependent mixed additions on register-resident operands
             # (k_probe_madd: no sort, no gathers, every lane busy), as many lane-level additions as one k_accumulate launch
             wl = Workload(ctx, d_g, 4096, args.seed)
@@ -789,11 +824,11 @@ def main():
                 "what": "k_probe_madd: %d lanes x %d dependent mixed additions, operands in registers" % (lanes, iters),
                 "ms": pms, "lane_mixed_adds_per_s": probe_rate, "k_accumulate_mixed_add_equivalents_per_s": acc_rate,
                 "k_accumulate_vs_probe": acc_rate / probe_rate}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             wl = Workload(ctx, d_g, max(1 << 18, 1 << args.cpu_sample_logn), args.seed)
             out["cpu_baseline"] = cpu_baseline(wl.d_pts, wl.d_sc, 1 << args.cpu_sample_logn)
             wl.free()
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             ctx2.close()                                      # (its streams would keep hardware queues the verifier's lanes need: a process has 24)
             cores = int(N.cg1_shuffle_default_threads())
             out["secondary"] = verify_measure(ctx, cores, args.verify_steps, 2, args.batch, args.verify_mode, cpu_leg=not args.no_cpu_baseline, peak_T=peak["peak_T"], front_end=args.front_end)
@@ -810,7 +845,7 @@ def main():
             out["secondary"]["device_front_end_on_2_host_threads_batches_of_%d" % (2 * args.batch)] = {k: dv2[k] for k in keys if k != "phases_ms_per_step"}
             out["secondary"]["opening_proofs"] = opening_measure(ctx)
             out["secondary"]["single_proof"] = single_proof_measure(ctx)
-        if world == 1 and not args.no_python_face:
+        if world == 1 and args.full and not args.no_python_face:
             # the drop-in itself: compute_MSM / MSMAccumulator through the reference's signature (lists of G1Point / Scalar objects), and
             # the reference's own backend-call sequence for one proof replayed through this backend.  (After the secondary metric: these
             # run on the package's default context, and every further live context costs the verifier hardware queues -- DESIGN.md 9.)

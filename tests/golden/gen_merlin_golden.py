@@ -17,6 +17,22 @@ from merlin_transcripts import MerlinTranscript  # noqa: E402
 R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
 
+def live_seed5():
+    """The challenges the reference gives for the op sequence tests/test_merlin.py::test_live_against_reference_package draws
+    from random.Random(5), in the order the test asks for them."""
+    rng = random.Random(5)
+    outs = []
+    for _ in range(6):
+        t = MerlinTranscript(rng.randbytes(rng.randrange(0, 30)))
+        for _ in range(10):
+            lab = rng.randbytes(rng.randrange(1, 12))
+            if rng.random() < 0.6:
+                t.append_message(lab, rng.randbytes(rng.choice([0, 7, 48, 166, 333, 1000])))
+            else:
+                outs.append(bytes(t.challenge_bytes(lab, rng.choice([1, 32, 200]))).hex())
+    return outs
+
+
 def main():
     rng = random.Random(20241008)
     cases = []
@@ -51,7 +67,8 @@ def main():
                 ops.append({"op": "scalar", "label": lab.hex(), "out": cb.hex()})
         cases.append({"label": label.hex(), "ops": ops})
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "merlin_vectors.json")
-    json.dump({"generator": "tests/golden/gen_merlin_golden.py (reference merlin_transcripts imported)", "cases": cases}, open(out, "w"))
+    json.dump({"generator": "tests/golden/gen_merlin_golden.py (reference merlin_transcripts imported)", "cases": cases,
+               "live_seed5": live_seed5()}, open(out, "w"))
     print("wrote", out, os.path.getsize(out), "bytes")
 
 

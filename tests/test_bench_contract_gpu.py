@@ -28,7 +28,7 @@ def im_peak_ok(im):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--logn", "16", "--cpu-sample-logn", "10",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--logn", "16", "--cpu-sample-logn", "10",
                         "--verify-steps", "3", "--batch", "256"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -54,6 +54,27 @@ def test_single_gpu_line():
     assert sec["cpu_baseline"]["kind"] == "port" and sec["cpu_baseline"]["cores"] == 1
 
 
+def test_plain_line_and_dump_outputs(tmp_path):
+    """Without --full: the headline alone, exactly --steps timed steps; --dump-outputs writes the last step's MSM result (affine,
+    on the curve)."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--logn", "16",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    for k in KEYS:
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "u32"
+    for k in ("secondary", "cpu_baseline", "roofline_int_mad", "seeds_ms_per_step", "python_face"):
+        assert k not in d, k
+    a = np.load(tmp_path / "msm_result_affine.npy")
+    assert a.dtype == np.float64 and a.shape == (2, 48) and ((a >= 0) & (a < 256) & (a == np.floor(a))).all()
+    x, y = (int.from_bytes(bytes(row.astype(np.uint8)), "little") for row in a)
+    p = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+    assert (x, y) != (0, 0) and (y * y - x ** 3 - 4) % p == 0
+
+
 def _check_two_rank_line(d):
     for k in KEYS:
         assert k in d, k
@@ -72,7 +93,7 @@ def test_two_rank_direct_launch_prints_one_line():
     """`python bench.py --gpus 2` with no launcher around it: bench.py starts its own two ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--logn", "16", "--same-device", "--no-cpu-baseline"],
+                        "--logn", "16", "--same-device", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     _check_two_rank_line(_last_json(r.stdout))
@@ -85,7 +106,7 @@ def test_two_rank_torchrun_launch_prints_one_line():
     env = {**os.environ, "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--logn", "16", "--same-device", "--no-cpu-baseline", "--no-secondary"],
+                        "--logn", "16", "--same-device", "--no-cpu-baseline", "--no-secondary", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -118,7 +139,7 @@ def test_rccl_refusal_falls_back_to_the_socket_transport():
     env["CG1_BENCH_TRY_RCCL_ON_ONE_DEVICE"] = "1"
     env["NCCL_DEBUG"] = "WARN"
     r = subprocess.run(["timeout", "-k", "10", "400", sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--logn", "14",
-                        "--same-device", "--backend", "rccl", "--no-cpu-baseline", "--no-secondary"],
+                        "--same-device", "--backend", "rccl", "--no-cpu-baseline", "--no-secondary", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -133,7 +154,7 @@ def test_four_rank_rehearsal_of_both_modes():
     scaling measurement: the line says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     r = subprocess.run(["timeout", "-k", "10", "500", sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--logn", "14", "--same-device", "--no-cpu-baseline", "--no-secondary"],
+                        "--logn", "14", "--same-device", "--no-cpu-baseline", "--no-secondary", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)

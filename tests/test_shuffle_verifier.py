@@ -22,7 +22,6 @@ from curdleproofs_pie_amd.shuffle_verifier import REJECT_LENGTH, ShuffleBatchVer
 from oracle.shuffle_check import decompress_affine, oracle_verdicts  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden", "shuffle_vectors.json")
-REF = "/root/reference/curdleproofs"
 
 
 @pytest.fixture(scope="module")
@@ -141,49 +140,19 @@ def test_threads_agree(gold):
     assert outs[0] == outs[1]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_differential_against_reference_verifier():
-    """Fresh seeded proofs (ell = 12) from the reference prover; EVERY field of the proof is tampered in turn and the
-    reference verifier's verdict (IsValidWhiskShuffleProof over our host backend) is compared with the statement's."""
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import gen_shuffle_golden as G                      # injects the backend, imports the reference
-
-    rng = random.Random(2024)
-    random.seed(77)
-    ell = 12
-    crs = G.CurdleproofsCrs.new(ell, 4)
-    pre = G.make_trackers(ell)
-    post, proof = G.GenerateWhiskShuffleProof(crs, pre)
-    proof = bytes(proof)
-    offs, total = G.proof_offsets(4)
-    assert total == len(proof)
-    other = bytes(G.point_projective_to_bytes(G.G1 * G.Scalar(12345)))
-    pre_r, pre_k = G.cat(pre)
-    post_r, post_k = G.cat(post)
-    items, names = [], []
-
-    def push(name, pr=pre_r, pk=pre_k, qr=post_r, qk=post_k, pf=proof):
-        items.append((G.split(pr, pk), G.split(qr, qk), pf))
-        names.append(name)
-
-    push("valid")
-    push("trailing bytes", pf=proof + b"\x00" * 7)
-    for nm, (off, size) in offs.items():
-        if size == 48:
-            push(nm + " := other", pf=proof[:off] + other + proof[off + 48:])
-        else:
-            val = (int.from_bytes(proof[off: off + 32], "little") + rng.randint(1, 1000)) % G.FR_MODULUS
-            push(nm + " shifted", pf=proof[:off] + val.to_bytes(32, "little") + proof[off + 32:])
-    for which in range(4):
-        for idx in (0, ell - 1):
-            bufs = [bytearray(pre_r), bytearray(pre_k), bytearray(post_r), bytearray(post_k)]
-            bufs[which][48 * idx: 48 * idx + 48] = other
-            push(f"tracker buf {which}[{idx}] := other", *(bytes(b) for b in bufs))
-    want = [bool(G.IsValidWhiskShuffleProof(crs, a, b, c)) for a, b, c in items]
-    assert want[0] and want[1] and not any(want[2:])
-    v = ShuffleBatchVerifier(crs)
+    """A seeded proof (ell = 12) from the reference prover with EVERY field of the proof tampered in turn, and the reference
+    verifier's verdict (IsValidWhiskShuffleProof) on each (tests/golden/differential_vectors.json, gen_differential_golden.py),
+    compared with the statement's."""
+    with open(os.path.join(ROOT, "tests", "golden", "differential_vectors.json")) as f:
+        case = json.load(f)
+    items = [apply_edits(case, var["edits"]) for var in case["variants"]]
+    names = [var["name"] for var in case["variants"]]
+    want = [var["accepts"] for var in case["variants"]]
+    assert want[0] and want[1] and not any(want[2:]) and len(want) == 76
+    v = ShuffleBatchVerifier(bytes.fromhex(case["crs"]))
     inst, proofs, st = v.pack(items)
-    prep = v.prepare(inst, proofs, len(items), rng=rng)
+    prep = v.prepare(inst, proofs, len(items), rng=random.Random(2024))
     got = oracle_verdicts(v, prep)
     assert got == want, [(n, g, w) for n, g, w in zip(names, got, want) if g != w]
 

@@ -7,7 +7,7 @@ TAG=${1:-run}
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 mkdir -p $O
-timeout -k 10 400 python $R/bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+timeout -k 10 400 python $R/bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 tail -c 300 $O/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --no-python-face > $O/${TAG}_kt.txt 2>&1
