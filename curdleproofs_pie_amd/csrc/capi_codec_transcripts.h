@@ -184,6 +184,23 @@ int cg1_merlin_batch_device(cg1_ctx* ctx, const uint8_t* init_state208, const cg
   HIPCHK(hipGetLastError());
   return CG1_OK;
 }
+}  // extern "C"
+namespace {
+// The transcript of an opening proof (opening.py:45-51 = :60-71) as cg1_merlin_batch_device's program over kernels_opening.h's rows
+// [k_G | k_r_G | r_G | A | B | G]: the state after CurdleproofsTranscript(b"whisk_opening_proof"), six 48-byte appends of
+// "tracker_opening_proof" in the reference's order k_G G k_r_G r_G A B, then the challenge.  The verifier's front-end and the prover share it.
+void opening_transcript_program(uint8_t init[CG1_MERLIN_STATE_BYTES], cg1_merlin_op ops[7]) {
+  cg1_merlin_init(init, (const uint8_t*)"whisk_opening_proof", 19);
+  memset(ops, 0, 7 * sizeof(cg1_merlin_op));
+  static const uint32_t off[6] = {0, 240, 48, 96, 144, 192};
+  for (int k = 0; k < 6; ++k) {
+    ops[k].kind = 0; ops[k].label_len = 21; memcpy(ops[k].label, "tracker_opening_proof", 21);
+    ops[k].len = 48; ops[k].data_off = off[k];
+  }
+  ops[6].kind = 2; ops[6].label_len = 31; memcpy(ops[6].label, "tracker_opening_proof_challenge", 31);
+}
+}  // namespace
+extern "C" {
 // Opening proofs, the batch verifier's front-end on the device (kernels_opening.h): the wire bytes of n proofs go up as they are, the
 // five own points of each are gathered in MSM order and decompressed WITH the subgroup test (both equalities are asserted exactly by the
 // reference, opening.py:73-74, on points it decodes unchecked: a random combination is sound only inside G1), the six-append transcript
@@ -229,15 +246,8 @@ int cg1_opening_prepare_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96
   launch_decompress(ctx, d_wire, d_points96, d_ps, 5 * n, 1);
   HIPCHK(hipMemcpyAsync((uint8_t*)d_points96 + 96 * 5 * n, g96, 96, hipMemcpyHostToDevice, st));
   uint8_t init[CG1_MERLIN_STATE_BYTES];
-  cg1_merlin_init(init, (const uint8_t*)"whisk_opening_proof", 19);                      // opening.py:60
   cg1_merlin_op ops[7];
-  memset(ops, 0, sizeof ops);
-  static const uint32_t off[6] = {0, 240, 48, 96, 144, 192};                              // k_G G k_r_G r_G A B (opening.py:61-66) inside a row
-  for (int k = 0; k < 6; ++k) {
-    ops[k].kind = 0; ops[k].label_len = 21; memcpy(ops[k].label, "tracker_opening_proof", 21);
-    ops[k].len = 48; ops[k].data_off = off[k];
-  }
-  ops[6].kind = 2; ops[6].label_len = 31; memcpy(ops[6].label, "tracker_opening_proof_challenge", 31);
+  opening_transcript_program(init, ops);
   { int rc = cg1_merlin_batch_device(ctx, init, ops, 7, d_rows, cg1open::ROW_BYTES, d_ch, 32, nullptr, n); if (rc) return rc; }
   hipLaunchKernelGGL(cg1open::k_opening_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const uint8_t*)d_ch, (const uint8_t*)d_pf,
                      weights64 ? (const uint8_t*)d_w : (const uint8_t*)nullptr, seed, (const uint8_t*)d_ps, n32, (int32_t)CG1_SHUFFLE_BAD_SCALAR, (int32_t)CG1_SHUFFLE_BAD_WEIGHT, (int32_t)CG1_SHUFFLE_BAD_POINT,
@@ -248,6 +258,118 @@ int cg1_opening_prepare_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96
   HIPCHK(hipMemcpyAsync(status, d_st, 4 * n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(point_status, d_ps, 5 * n, hipMemcpyDeviceToHost, st));
   if (out_g_scalars32) HIPCHK(hipMemcpyAsync(out_g_scalars32, d_gs, 32 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  return CG1_OK;
+}
+}  // extern "C"
+namespace {
+// k_generator_mul's table of G (kernels_generator.h), built once per context: entry w * GEN_HALF + (d - 1) = d * 2^(c w) * G from ONE
+// k_batch_mul launch over the scalars d * 2^(c w) (nbase = 1), then prepared records.  Synchronous; a no-op once built.
+int ensure_generator_table(cg1_ctx* ctx) {
+  if (ctx->d_gen_tab) return CG1_OK;
+  constexpr size_t E = cg1::GEN_ENTRIES;
+  std::vector<uint8_t> sc(E * 32, 0);
+  for (int w = 0; w < cg1::GEN_WINDOWS; ++w)
+    for (int d = 1; d <= cg1::GEN_HALF; ++d) {
+      const int bit = w * cg1::GEN_C;
+      const uint32_t v = (uint32_t)d << (bit & 7);
+      uint8_t* s = sc.data() + ((size_t)w * cg1::GEN_HALF + (d - 1)) * 32;
+      s[bit >> 3] = (uint8_t)v;
+      if ((bit >> 3) + 1 < 32) s[(bit >> 3) + 1] = (uint8_t)(v >> 8);
+    }
+  uint8_t gblob[CG1_POINT_BYTES], g96[96];
+  cg1_generator(gblob);
+  cg1_to_affine96(g96, gblob);
+  DevBuf dsc, dbase, dout, dflags;
+  HIPCHK(dsc.alloc(E * 32)); HIPCHK(dbase.alloc(96)); HIPCHK(dout.alloc(E * 96)); HIPCHK(dflags.alloc(E + 16));
+  HIPCHK(hipMemcpy(dsc.p, sc.data(), E * 32, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dbase.p, g96, 96, hipMemcpyHostToDevice));
+  { const int rc = cg1_batch_mul_device(ctx, dbase.p, 1, dsc.p, dout.p, E); if (rc) return rc; }
+  DevBuf tab;
+  HIPCHK(tab.alloc(E * sizeof(cg1::PreparedPoint)));
+  hipLaunchKernelGGL(cg1::k_prepare_points, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)dout.p,
+                     (cg1::PreparedPoint*)tab.p, (uint8_t*)dflags.p, (uint32_t)E);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  ctx->d_gen_tab = (cg1::PreparedPoint*)tab.p;
+  tab.p = nullptr;                                        // the context owns it now (cg1_ctx_destroy frees it)
+  return CG1_OK;
+}
+void launch_generator_mul(cg1_ctx* ctx, const void* d_scalars32, size_t n, void* d_out96, void* d_out48) {
+  hipLaunchKernelGGL(cg1::k_generator_mul, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const cg1::PreparedPoint*)ctx->d_gen_tab,
+                     (const uint32_t*)d_scalars32, (uint32_t)n, (uint32_t*)d_out96, (uint32_t*)d_out48);
+}
+}  // namespace
+extern "C" {
+int cg1_generator_mul_device(cg1_ctx* ctx, const void* d_scalars32, size_t n, void* d_out_affine96, void* d_out48) {
+  if (!ctx) return CG1_ERR_HIP;
+  if (n == 0) return CG1_OK;
+  if (!d_scalars32 || (!d_out_affine96 && !d_out48) || n >= (1ull << 31)) return CG1_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rc = ensure_generator_table(ctx); if (rc) return rc; }
+  launch_generator_mul(ctx, d_scalars32, n, d_out_affine96, d_out48);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  return CG1_OK;
+}
+// Opening proofs, the PROVER on the device (kernels_opening_prover.h): n items (tracker, k) -> n proofs A | B | s and n k_commitments k G,
+// with the status codes of the host's cg1_opening_prove.  blinders32 == NULL: blinder i is derived on the device from seed32
+// (blinder_from_seed).  Host buffers in and out; synchronous.
+int cg1_opening_prove_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96, const uint8_t* ks32, const uint8_t* blinders32, const uint8_t* seed32,
+                             uint8_t* out_proofs128, uint8_t* out_k_commitments48, int32_t* status) {
+  if (!ctx) return CG1_ERR_HIP;
+  if (n == 0) return CG1_OK;
+  if (!trackers96 || !ks32 || (!blinders32 && !seed32) || !out_proofs128 || !out_k_commitments48 || !status || n >= (1ull << 26)) return CG1_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  { const int rc = ensure_generator_table(ctx); if (rc) return rc; }
+  // scratch: trackers 96 | k 32 | blinders 32 | wire 96 | affine 192 | gen scalars 64 | gen48 96 | B affine 96 | B48 48 | rows 288 |
+  //          challenges 32 | status 4 | proofs 128 | k_G 48 | point status 2
+  const size_t per = 96 + 32 + 32 + 96 + 192 + 64 + 96 + 96 + 48 + cg1open::ROW_BYTES + 32 + 4 + 128 + 48 + 2, need = per * n;
+  if (need > ctx->cap_prover) {
+    if (ctx->d_prover) (void)hipFree(ctx->d_prover);
+    ctx->d_prover = nullptr; ctx->cap_prover = 0;
+    HIPCHK(hipMalloc(&ctx->d_prover, need));
+    ctx->cap_prover = need;
+  }
+  uint8_t* base = (uint8_t*)ctx->d_prover;
+  uint8_t *d_trk = base, *d_k = d_trk + 96 * n, *d_bl = d_k + 32 * n, *d_wire = d_bl + 32 * n, *d_aff = d_wire + 96 * n, *d_gsc = d_aff + 192 * n,
+          *d_gen48 = d_gsc + 64 * n, *d_b96 = d_gen48 + 96 * n, *d_b48 = d_b96 + 96 * n, *d_rows = d_b48 + 48 * n, *d_ch = d_rows + (size_t)cg1open::ROW_BYTES * n,
+          *d_st = d_ch + 32 * n, *d_pf = d_st + 4 * n, *d_kc = d_pf + 128 * n, *d_ps = d_kc + 48 * n;
+  hipStream_t st = ctx->stream;
+  const uint32_t n32 = (uint32_t)n;
+  HIPCHK(hipMemcpyAsync(d_trk, trackers96, 96 * n, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_k, ks32, 32 * n, hipMemcpyHostToDevice, st));
+  if (blinders32) HIPCHK(hipMemcpyAsync(d_bl, blinders32, 32 * n, hipMemcpyHostToDevice, st));
+  cg1open::Seed32 seed{};
+  if (!blinders32) memcpy(seed.w, seed32, 32);
+  hipLaunchKernelGGL(cg1open::k_prove_split, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_trk, n32, (uint32_t*)d_wire);
+  launch_decompress(ctx, d_wire, d_aff, d_ps, 2 * n, 0);                                   // unchecked (util.py:35-36)
+  hipLaunchKernelGGL(cg1open::k_prove_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const uint8_t*)d_ps, (const uint8_t*)d_k,
+                     blinders32 ? (const uint8_t*)d_bl : (const uint8_t*)nullptr, seed, n32, (int32_t)CG1_SHUFFLE_BAD_POINT, (int32_t)CG1_SHUFFLE_BAD_SCALAR,
+                     (int32_t)CG1_OPENING_BAD_BLINDER, d_gsc, (int32_t*)d_st);
+  launch_generator_mul(ctx, d_gsc, 2 * n, nullptr, d_gen48);                               // [k_G ...][A ...]
+  // B = b r_G: k_batch_mul (one lane per proof, xyzz_dbl / xyzz_madd, exact for any curve point).  Not k_batch_mul_quad, which
+  // cg1_batch_mul_add_device picks for small n: its table {P, 2P, 3P} takes 3P as finite, and r_G may have order 3 (T3 = (0, 2)).
+  hipLaunchKernelGGL(cg1::k_batch_mul, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, (const uint32_t*)d_aff, n32, (const uint32_t*)(d_gsc + 32 * n), n32,
+                     (const uint32_t*)nullptr, (uint32_t*)d_b96, n32);
+  hipLaunchKernelGGL(cg1::k_batch_compress, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_b96, d_b48, n32);
+  uint8_t gblob[CG1_POINT_BYTES], g48[48];
+  cg1_generator(gblob);
+  cg1_compress(g48, gblob);
+  cg1open::Enc48 genc;
+  memcpy(genc.w, g48, 48);
+  hipLaunchKernelGGL(cg1open::k_prove_gather, dim3((unsigned)((6 * n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_gen48, (const uint32_t*)d_b48,
+                     (const uint32_t*)d_wire, genc, n32, (uint32_t*)d_rows);
+  uint8_t init[CG1_MERLIN_STATE_BYTES];
+  cg1_merlin_op ops[7];
+  opening_transcript_program(init, ops);
+  { const int rc = cg1_merlin_batch_device(ctx, init, ops, 7, d_rows, cg1open::ROW_BYTES, d_ch, 32, nullptr, n); if (rc) return rc; }
+  hipLaunchKernelGGL(cg1open::k_prove_response, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t*)d_ch, (const uint8_t*)d_gsc,
+                     (const uint32_t*)d_gen48, (const uint32_t*)d_b48, (const int32_t*)d_st, n32, (uint32_t*)d_pf, (uint32_t*)d_kc);
+  HIPCHK(hipMemcpyAsync(out_proofs128, d_pf, 128 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(out_k_commitments48, d_kc, 48 * n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(status, d_st, 4 * n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   return CG1_OK;

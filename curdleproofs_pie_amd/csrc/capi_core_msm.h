@@ -183,6 +183,8 @@ void cg1_ctx_destroy(cg1_ctx* ctx) {
   cg1::free_bufs(ctx);
   if (ctx->d_merlin_rows) (void)hipFree(ctx->d_merlin_rows);
   if (ctx->d_opening) (void)hipFree(ctx->d_opening);
+  if (ctx->d_prover) (void)hipFree(ctx->d_prover);
+  if (ctx->d_gen_tab) (void)hipFree(ctx->d_gen_tab);
   if (ctx->d_small_partial) (void)hipFree(ctx->d_small_partial);
   if (ctx->d_small_ctr) (void)hipFree(ctx->d_small_ctr);
   if (ctx->d_small_pts) (void)hipFree(ctx->d_small_pts);

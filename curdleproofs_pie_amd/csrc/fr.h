@@ -148,6 +148,16 @@ CG1FR_HD bool fr_from_le32(const uint8_t* b, fr& out) {
   out = fr_mul(a, r2);
   return true;
 }
+// 64 little-endian bytes as one 512-bit integer, reduced mod r (int.from_bytes(b, "little") % r), in Montgomery form:
+// lo + hi * 2^256 with 2^256 = R, whose Montgomery forms are fr_mul(lo, R2) and fr_mul(fr_mul(hi, R2), R2).  fr_mul takes any
+// 256-bit first operand against a second one below r (the product stays below r * 2^256), so neither half needs reducing first.
+CG1FR_HD fr fr_from_le64_wide(const uint8_t* b) {
+  fr lo, hi;
+  memcpy(lo.l, b, 32);
+  memcpy(hi.l, b + 32, 32);
+  const fr r2{{cg1::H_FR_R2[0], cg1::H_FR_R2[1], cg1::H_FR_R2[2], cg1::H_FR_R2[3]}};
+  return fr_add(fr_mul(lo, r2), fr_mul(fr_mul(hi, r2), r2));
+}
 // out of Montgomery form: four reduction rounds only (half the work of a multiplication by 1)
 CG1FR_HD void fr_to_le32(const fr& a, uint8_t* b) {
   uint64_t t[4] = {a.l[0], a.l[1], a.l[2], a.l[3]};

@@ -62,6 +62,7 @@ int pick_window(size_t n);
 #include "kernels_reduce.h"
 #include "kernels_small.h"
 #include "kernels_batch.h"
+#include "kernels_generator.h"
 }  // namespace cg1
 #include "kernels_rows.h"
 #include "kernels_merlin.h"
@@ -73,6 +74,6 @@ int pick_window(size_t n);
 #include "capi_vec_batched.h"      // resident vectors, batched normalisation, regime B
 #include "capi_lincomb.h"          // deferred G1Point evaluation: cg1_lincomb_batch, cg1_batch_subgroup
 #include "capi_timing_batchmul.h"  // timings / counters, cg1_batch_mul_add*
-#include "capi_codec_transcripts.h"// decompression, subgroup flags, Merlin batches, opening proofs
+#include "capi_codec_transcripts.h"// decompression, subgroup flags, Merlin batches, opening proofs (verifier front-end, prover), k G
 #include "capi_frontend.h"         // the shuffle verifier front-end on the device
 #include "capi_rows_probes.h"      // scalar rows, compression, synthetic scalars, probes

@@ -969,6 +969,68 @@ int cg1_opening_prepare(size_t n, const uint8_t* trackers, const uint8_t* k_comm
   return CG1_OK;
 }
 
+// ---- Whisk tracker-opening proofs, the PROVER (GenerateWhiskTrackerProof, whisk_interface.py:177-190 -> TrackerOpeningProof.new,
+// opening.py:33-56), one item at a time on the worker pool: the host twin of cg1_opening_prove_device (csrc/kernels_opening.h), same bytes,
+// same status codes, for the small batches a GPU round trip does not pay for.  k_G and A come from 8-bit windows over G (FixedBase: 32
+// mixed additions each), B = b r_G from a plain double-and-add (r_G may lie outside G1: no endomorphism).
+int cg1_opening_prove(size_t n, const uint8_t* trackers96, const uint8_t* ks32, const uint8_t* blinders32, uint8_t* out_proofs128,
+                      uint8_t* out_k_commitments48, int32_t* status) {
+  if (n && (!trackers96 || !ks32 || !blinders32 || !out_proofs128 || !out_k_commitments48 || !status)) return CG1_ERR_ARG;
+  if (n == 0) return CG1_OK;
+  static const FixedBase* gtab = [] { FixedBase* t = new FixedBase; t->build(cg1h::jac_generator()); return t; }();
+  uint8_t G48[48];
+  cg1h::g1_compress(cg1h::jac_generator(), G48);
+  auto one = [&](size_t i) {
+    const uint8_t *rG = trackers96 + 96 * i, *krG = rG + 48;
+    uint8_t* pf = out_proofs128 + 128 * i;
+    uint8_t* kc = out_k_commitments48 + 48 * i;
+    memset(pf, 0, 128);
+    memset(kc, 0, 48);
+    jac jkrG, jrG;
+    fr k, b;
+    if (cg1h::g1_decompress(krG, false, jkrG) || cg1h::g1_decompress(rG, false, jrG)) { status[i] = CG1_SHUFFLE_BAD_POINT; return; }   // whisk_interface.py:182-183
+    if (!fr_from_le32(ks32 + 32 * i, k)) { status[i] = CG1_SHUFFLE_BAD_SCALAR; return; }
+    if (!fr_from_le32(blinders32 + 32 * i, b) || fr_is_zero(b)) { status[i] = CG1_OPENING_BAD_BLINDER; return; }
+    jac kG = cg1h::jac_identity(), A = cg1h::jac_identity();
+    gtab->mul_into(kG, k);
+    gtab->mul_into(A, b);
+    uint8_t b32[32];
+    fr_to_le32(b, b32);
+    const jac B = cg1h::jac_mul(jrG, b32);
+    uint8_t row[6 * 48];                                       // k_G G k_r_G r_G A B, re-serialised (opening.py:45-48)
+    cg1h::g1_compress(kG, row);
+    memcpy(row + 48, G48, 48);
+    memcpy(row + 96, krG, 48);
+    memcpy(row + 144, rG, 48);
+    canonicalize_infinities(row + 96, 2);
+    cg1h::g1_compress(A, row + 192);
+    cg1h::g1_compress(B, row + 240);
+    Transcript tr("whisk_opening_proof");
+    for (int j = 0; j < 6; ++j) tr.point("tracker_opening_proof", row + 48 * j);
+    const fr c = tr.challenge("tracker_opening_proof_challenge");
+    memcpy(pf, row + 192, 96);                                 // A | B | s  (opening.py:94-99)
+    fr_to_le32(fr_sub(b, fr_mul(c, k)), pf + 96);
+    memcpy(kc, row, 48);
+    status[i] = 0;
+  };
+  if (n < 8) {
+    for (size_t i = 0; i < n; ++i) one(i);
+    return CG1_OK;
+  }
+  std::atomic<size_t> next{0};
+  const size_t items = (n + 3) / 4;                            // slices of 4 proofs (~0.1 ms each)
+  std::function<void()> work = [&]() {
+    for (;;) {
+      const size_t it = next.fetch_add(1);
+      if (it >= items) return;
+      for (size_t i = it * 4; i < std::min(n, it * 4 + 4); ++i) one(i);
+    }
+  };
+  Pool& pool = Pool::get();
+  pool.run(work, std::min(items, pool.size() + 1));
+  return CG1_OK;
+}
+
 // out[i] = addend[i] + scalars[i % nscalars] * bases[i % nbase] on the HOST's worker pool: the same contract as the device kernel behind
 // cg1_batch_mul_add (affine96 standard-form records in and out, zeros = identity, inputs not checked against the curve), for the calls
 // where a launch costs more than the arithmetic: a fold / map of a few hundred points is 255 dependent doublings on the GPU whatever

@@ -491,6 +491,28 @@ int cg1_opening_prepare_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96
  * 32 bytes of SHAKE256(seed32 || le64(i)); seed32 = 32 fresh bytes from the OS per batch.  Writes proofs first .. first + n - 1. */
 int cg1_opening_weights_from_seed(const uint8_t seed32[32], size_t first, size_t n, uint8_t* out_weights64);
 
+/* Whisk tracker-opening proofs, the PROVER: GenerateWhiskTrackerProof (whisk_interface.py:177-190) -> TrackerOpeningProof.new
+ * (opening.py:33-56) for n items (tracker, k, blinder b): decode k_r_G and r_G unchecked (a point outside G1 is multiplied exactly),
+ * k_G = k G, A = b G, B = b r_G, the six appends [k_G, G, k_r_G, r_G, A, B] re-serialised and the challenge c, s = b - c k.
+ * out_proofs128[i] = A | B | s (opening.py:94-99), out_k_commitments48[i] = k_G (the caller's k_commitment).  status[i]: 0, or
+ * CG1_SHUFFLE_BAD_POINT (k_r_G or r_G does not decode: the reference raises ValueError before it draws a blinder), CG1_SHUFFLE_BAD_SCALAR
+ * (k >= r), CG1_OPENING_BAD_BLINDER (b == 0 or b >= r), checked in that order; a rejected item gets a zeroed proof and k_commitment.
+ * The k_r_G = k r_G relation is not checked (the reference does not check it either).
+ * Host: on the worker pool (what a few proofs should take: a GPU round trip costs more than their scalar multiplications). */
+#define CG1_OPENING_BAD_BLINDER  4   /* = CG1_SHUFFLE_BAD_WEIGHT: a blinder that is zero or >= r */
+int cg1_opening_prove(size_t n, const uint8_t* trackers96 /* r_G | k_r_G */, const uint8_t* ks32, const uint8_t* blinders32,
+                      uint8_t* out_proofs128, uint8_t* out_k_commitments48, int32_t* status);
+/* The same proofs on the device (csrc/kernels_opening_prover.h), byte for byte and with the same status codes; host buffers in and out.
+ * blinders32 == NULL: blinder i = int.from_bytes(SHAKE256("whisk_opening_blinder" || seed32 || le64(i)).digest(64), "little") mod r,
+ * derived on the device.  A seed that is reused or known to anyone else reveals every k it was used with (k = (b - s) / c). */
+int cg1_opening_prove_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96 /* r_G | k_r_G */, const uint8_t* ks32,
+                             const uint8_t* blinders32 /* or NULL */, const uint8_t* seed32 /* used when blinders32 == NULL */,
+                             uint8_t* out_proofs128, uint8_t* out_k_commitments48, int32_t* status);
+/* Fixed-base multiples of the generator: out[i] = scalars[i] * G (any 256-bit scalar; k G = (k mod r) G) from a table of G built once per
+ * context at the first call (csrc/kernels_generator.h: signed 8-bit windows, 32 mixed additions and one inversion per output against
+ * k_batch_mul's 255 doublings).  Device pointers; d_out_affine96 (zeros = identity) and d_out48 (compressed) may each be NULL, not both. */
+int cg1_generator_mul_device(cg1_ctx* ctx, const void* d_scalars32, size_t n, void* d_out_affine96 /* nullable */, void* d_out48 /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif
