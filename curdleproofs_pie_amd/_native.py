@@ -249,6 +249,15 @@ cg1_opening_exact_status = _proto("cg1_opening_exact_status", c_int, c_void_p, c
 cg1_opening_prove = _proto("cg1_opening_prove", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 cg1_opening_prove_device = _proto("cg1_opening_prove_device", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 cg1_generator_mul_device = _proto("cg1_generator_mul_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p)
+# resident tables of fixed bases (csrc/kernels_fixed.h)
+cg1_fixed_create = _proto("cg1_fixed_create", c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_int))
+cg1_fixed_destroy = _proto("cg1_fixed_destroy", None, c_void_p)
+cg1_fixed_len = _proto("cg1_fixed_len", c_size_t, c_void_p)
+cg1_fixed_bytes = _proto("cg1_fixed_bytes", c_size_t, c_void_p)
+cg1_fixed_msm = _proto("cg1_fixed_msm", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p)
+cg1_fixed_msm_device = _proto("cg1_fixed_msm_device", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p)
+cg1_fixed_digits = _proto("cg1_fixed_digits", None, _u8p, c_void_p)
+FIXED_MAX_BASES, FIXED_MAX_MSMS, FIXED_MAX_TERMS = 1024, 1024, 2048      # CG1_FIXED_MAX_* of include/curdle_g1.h
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -269,6 +278,7 @@ EXPORTED_SYMBOLS = [
     "cg1_comm_world_seen", "cg1_comm_error", "cg1_comm_allgather", "cg1_comm_allgather_host", "cg1_comm_barrier", "cg1_comm_allreduce_g1", "cg1_comm_destroy",
     "cg1_validate_compressed", "cg1_fp_jacobi", "cg1_batch_decompress_pool", "cg1_batch_subgroup_pool", "cg1_batch_subgroup", "cg1_lincomb_batch", "cg1_lincomb_batch_pool", "cg1_glv_split", "cg1_batch_decompress_rows",
     "cg1_probe_add_chain", "cg1_msm_blobs", "cg1_stage_reserve", "cg1_msm_blobs_device", "cg1_vec_create", "cg1_vec_destroy", "cg1_vec_len", "cg1_msm_vec", "cg1_batch_normalize", "cg1_batch_from_affine96", "cg1_get_last_launches", "cg1_plan_describe",
+    "cg1_fixed_create", "cg1_fixed_destroy", "cg1_fixed_len", "cg1_fixed_bytes", "cg1_fixed_msm", "cg1_fixed_msm_device", "cg1_fixed_digits",
 ]
 
 
@@ -443,6 +453,35 @@ class Context:
         raw = out.raw
         return [raw[POINT_BYTES * j: POINT_BYTES * (j + 1)] for j in range(m)]
 
+    def fixed_table(self, bases_affine96: bytes, n_bases: int) -> "FixedTable":
+        """A resident table of `n_bases` fixed bases (cg1_fixed): 512 KiB of prepared records per base."""
+        return FixedTable(self, bases_affine96, n_bases)
+
+    def fixed_msm_host(self, tab: "FixedTable", term_base, scalars32: bytes, offsets, compressed: bool = False) -> list:
+        """cg1_fixed_msm: MSM j over the table entries term_base[offsets[j] : offsets[j + 1]] (bit 31 = the negated base); one 144-byte
+        blob per MSM, or one compressed48 each."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        m = len(offsets) - 1
+        n = offsets[-1]
+        assert len(term_base) >= n and len(scalars32) >= 32 * n
+        tb = (ctypes.c_uint32 * max(n, 1))(*term_base[:n])
+        arr = (ctypes.c_uint32 * (m + 1))(*offsets)
+        w = 48 if compressed else POINT_BYTES
+        out = ctypes.create_string_buffer(w * max(m, 1))
+        self.check(cg1_fixed_msm(self.handle, tab.handle, tb, scalars32, arr, m, None if compressed else out, out if compressed else None))
+        raw = out.raw
+        return [raw[w * j: w * (j + 1)] for j in range(m)]
+
+    def fixed_msm_device(self, tab: "FixedTable", d_term_base, d_scalars32, d_offsets, n_msm: int, n_terms: int, max_terms: int,
+                         d_out_affine96=None, d_out_comp48=None) -> None:
+        """cg1_fixed_msm_device: device arrays in, affine96 and / or compressed48 left in device buffers."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        self.check(cg1_fixed_msm_device(self.handle, tab.handle, g(d_term_base), g(d_scalars32), g(d_offsets), n_msm, n_terms, max_terms,
+                                        g(d_out_affine96), g(d_out_comp48)))
+
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""
         e, c = ctypes.c_uint32(), ctypes.c_uint32()
@@ -540,6 +579,37 @@ class Vec:
     def free(self) -> None:
         if self.handle:
             cg1_vec_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class FixedTable:
+    """A table of fixed bases resident on the device (cg1_fixed): for each base the 32 x 128 multiples d * 2^(8 w) * B."""
+
+    def __init__(self, ctx: Context, bases_affine96: bytes, n_bases: int):
+        assert len(bases_affine96) >= 96 * n_bases
+        self.ctx, self.n = ctx, int(n_bases)
+        st = c_int(0)
+        self.handle = cg1_fixed_create(ctx.handle, bases_affine96, self.n, ctypes.byref(st))
+        if not self.handle:
+            msg = cg1_ctx_error(ctx.handle)
+            err = f"cg1_fixed_create({n_bases} bases) failed ({st.value}): {msg.decode() if msg else ''}"
+            if st.value in (ERR_ENCODING, ERR_NOT_ON_CURVE):
+                raise ValueError(err)
+            raise NativeError(err)
+
+    @property
+    def nbytes(self) -> int:
+        return int(cg1_fixed_bytes(self.handle)) if self.handle else 0
+
+    def free(self) -> None:
+        if self.handle:
+            cg1_fixed_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

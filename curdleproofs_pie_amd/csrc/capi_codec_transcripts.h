@@ -264,11 +264,13 @@ int cg1_opening_prepare_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96
 }
 }  // extern "C"
 namespace {
-// k_generator_mul's table of G (kernels_generator.h), built once per context: entry w * GEN_HALF + (d - 1) = d * 2^(c w) * G from ONE
-// k_batch_mul launch over the scalars d * 2^(c w) (nbase = 1), then prepared records.  Synchronous; a no-op once built.
-int ensure_generator_table(cg1_ctx* ctx) {
-  if (ctx->d_gen_tab) return CG1_OK;
-  constexpr size_t E = cg1::GEN_ENTRIES;
+// The fixed-base tables of kernels_generator.h / kernels_fixed.h: for bases B_0 .. B_{m-1} (host affine96 records) entry
+// (b * GEN_WINDOWS + w) * GEN_HALF + (d - 1) = d * 2^(c w) * B_b as prepared records -- the scalars d * 2^(c w) through k_batch_mul (one
+// lane per entry, double-and-add with the complete formulas: exact for ANY curve point, where k_batch_mul_quad's table {P, 2P, 3P} takes
+// 3P as finite), then k_prepare_points (all-zero products, the identity, become flagged records).  All bases of a table in one call,
+// up to 32 of them (131 072 entries) per launch pair.  Synchronous; *out_tab is the caller's to free.
+int build_fixed_table(cg1_ctx* ctx, const uint8_t* bases96, size_t m, cg1::PreparedPoint** out_tab) {
+  constexpr size_t E = cg1::GEN_ENTRIES, CHUNK = 32;
   std::vector<uint8_t> sc(E * 32, 0);
   for (int w = 0; w < cg1::GEN_WINDOWS; ++w)
     for (int d = 1; d <= cg1::GEN_HALF; ++d) {
@@ -278,23 +280,35 @@ int ensure_generator_table(cg1_ctx* ctx) {
       s[bit >> 3] = (uint8_t)v;
       if ((bit >> 3) + 1 < 32) s[(bit >> 3) + 1] = (uint8_t)(v >> 8);
     }
+  const size_t cm = std::min(m, CHUNK);
+  DevBuf dsc, dbase, dout, dflags, tab;
+  HIPCHK(dsc.alloc(E * 32)); HIPCHK(dbase.alloc(cm * E * 96)); HIPCHK(dout.alloc(cm * E * 96)); HIPCHK(dflags.alloc(cm * E + 16));
+  HIPCHK(tab.alloc(m * E * sizeof(cg1::PreparedPoint)));
+  HIPCHK(hipMemcpy(dsc.p, sc.data(), E * 32, hipMemcpyHostToDevice));
+  std::vector<uint8_t> hb(cm * E * 96);                    // entry i of a launch multiplies base record i by scalar i mod E
+  for (size_t b0 = 0; b0 < m; b0 += CHUNK) {
+    const size_t cnt = std::min(CHUNK, m - b0), n = cnt * E;
+    for (size_t b = 0; b < cnt; ++b)
+      for (size_t e = 0; e < E; ++e) memcpy(hb.data() + (b * E + e) * 96, bases96 + (b0 + b) * 96, 96);
+    HIPCHK(hipMemcpy(dbase.p, hb.data(), n * 96, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(cg1::k_batch_mul, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, ctx->stream, (const uint32_t*)dbase.p, (uint32_t)n, (const uint32_t*)dsc.p,
+                       (uint32_t)E, (const uint32_t*)nullptr, (uint32_t*)dout.p, (uint32_t)n);
+    hipLaunchKernelGGL(cg1::k_prepare_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)dout.p,
+                       (cg1::PreparedPoint*)tab.p + b0 * E, (uint8_t*)dflags.p, (uint32_t)n);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+  }
+  *out_tab = (cg1::PreparedPoint*)tab.p;
+  tab.p = nullptr;
+  return CG1_OK;
+}
+// k_generator_mul's table of G, built once per context (cg1_ctx_destroy frees it); a no-op once built
+int ensure_generator_table(cg1_ctx* ctx) {
+  if (ctx->d_gen_tab) return CG1_OK;
   uint8_t gblob[CG1_POINT_BYTES], g96[96];
   cg1_generator(gblob);
   cg1_to_affine96(g96, gblob);
-  DevBuf dsc, dbase, dout, dflags;
-  HIPCHK(dsc.alloc(E * 32)); HIPCHK(dbase.alloc(96)); HIPCHK(dout.alloc(E * 96)); HIPCHK(dflags.alloc(E + 16));
-  HIPCHK(hipMemcpy(dsc.p, sc.data(), E * 32, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dbase.p, g96, 96, hipMemcpyHostToDevice));
-  { const int rc = cg1_batch_mul_device(ctx, dbase.p, 1, dsc.p, dout.p, E); if (rc) return rc; }
-  DevBuf tab;
-  HIPCHK(tab.alloc(E * sizeof(cg1::PreparedPoint)));
-  hipLaunchKernelGGL(cg1::k_prepare_points, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)dout.p,
-                     (cg1::PreparedPoint*)tab.p, (uint8_t*)dflags.p, (uint32_t)E);
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipGetLastError());
-  ctx->d_gen_tab = (cg1::PreparedPoint*)tab.p;
-  tab.p = nullptr;                                        // the context owns it now (cg1_ctx_destroy frees it)
-  return CG1_OK;
+  return build_fixed_table(ctx, g96, 1, &ctx->d_gen_tab);
 }
 void launch_generator_mul(cg1_ctx* ctx, const void* d_scalars32, size_t n, void* d_out96, void* d_out48) {
   hipLaunchKernelGGL(cg1::k_generator_mul, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const cg1::PreparedPoint*)ctx->d_gen_tab,

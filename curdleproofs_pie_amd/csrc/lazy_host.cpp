@@ -14,6 +14,7 @@
 #endif
 namespace cg1 {
 #include "glv.h"
+#include "fixed_digits.h"
 }
 
 namespace cg1h {
@@ -437,6 +438,13 @@ void cg1_glv_split(const uint8_t* scalar32, uint8_t* k1_16, uint8_t* k2_16, int*
   memcpy(k1_16, o.k1, 16);
   memcpy(k2_16, o.k2, 16);
   *neg1 = (int)o.neg1; *neg2 = (int)o.neg2;
+}
+
+// The signed 8-bit recoding of the fixed-base tables (csrc/fixed_digits.h: the function k_fixed_msm runs), one scalar: for the CPU tests.
+void cg1_fixed_digits(const uint8_t* scalar32, int16_t* out32) {
+  uint32_t k[8];
+  memcpy(k, scalar32, 32);
+  (void)cg1::fixed_digits(k, out32, 1);
 }
 
 }  // extern "C"

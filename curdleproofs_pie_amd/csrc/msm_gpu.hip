@@ -63,6 +63,8 @@ int pick_window(size_t n);
 #include "kernels_small.h"
 #include "kernels_batch.h"
 #include "kernels_generator.h"
+#include "fixed_digits.h"
+#include "kernels_fixed.h"
 }  // namespace cg1
 #include "kernels_rows.h"
 #include "kernels_merlin.h"
@@ -77,3 +79,4 @@ int pick_window(size_t n);
 #include "capi_codec_transcripts.h"// decompression, subgroup flags, Merlin batches, opening proofs (verifier front-end, prover), k G
 #include "capi_frontend.h"         // the shuffle verifier front-end on the device
 #include "capi_rows_probes.h"      // scalar rows, compression, synthetic scalars, probes
+#include "capi_fixed.h"            // resident fixed-base tables: cg1_fixed_*

@@ -42,7 +42,7 @@ def _halves(n0: int, n: int):
 
 
 def ipa_rounds_many(provers: Sequence[Tuple[Sequence[G1Point], Sequence[G1Point], G1Point, Sequence[Scalar], Sequence[Scalar]]],
-                    next_gammas: Sequence[Callable[[G1Point, G1Point, G1Point, G1Point], Scalar]]):
+                    next_gammas: Sequence[Callable[[G1Point, G1Point, G1Point, G1Point], Scalar]], table=None):
     """ipa.py:117-151 for SEVERAL independent provers in step (same vector length): round k of all of them is ONE batched MSM call
     (4 MSMs per prover; up to 16 MSMs ride one k_msm_small launch).  provers[p] = (crs_G_vec, crs_G_prime_vec, H, vec_c, vec_d) with
     `H` = crs_H * beta (ipa.py:110) and the vectors already blinded (ipa.py:107-109).
@@ -53,9 +53,15 @@ def ipa_rounds_many(provers: Sequence[Tuple[Sequence[G1Point], Sequence[G1Point]
     ones, G^(k)_i = sum over j = i (mod n_k) of coef_j G_j with coef_j the product of the challenges of the rounds in which j sat in
     the right half.  So the bases stay what they were (normal forms cached, or resident on the device) and the challenges fold into
     the SCALARS: MSM(G^(k)_R, c_L) = sum over j in the right half of c_L[j mod 2n - n] coef_j G_j.  Same group elements, no fold
-    launches at all (they were 15.8 of the 21 ms these rounds took: profiles/r03_prover_flows_v2.txt)."""
+    launches at all (they were 15.8 of the 21 ms these rounds took: profiles/r03_prover_flows_v2.txt).
+
+    table (a fixed_base.FixedBaseTable): the four MSMs of a round, for all provers in step, go through ONE `table.msm_many` call -- no
+    doublings, the sums finished on the device.  Every G[j], Gp[j] and H must then be an object of the table (KeyError otherwise).
+    `H` = crs_H * beta is not a CRS point: a seventh tuple element gives it implicitly, H = provers[p][2] * provers[p][6] (pass crs_H
+    itself and beta), the way the sixth stands for the base change of G'; the inner-product scalars are multiplied by it instead."""
     st = [dict(G=list(pr[0]), Gp=list(pr[1]), H=pr[2], c=[x._v for x in pr[3]], d=[x._v for x in pr[4]], LC=[], RC=[], LD=[], RD=[],
-               kGp0=(list(pr[5]) if len(pr) > 5 and pr[5] is not None else None)) for pr in provers]
+               kGp0=(list(pr[5]) if len(pr) > 5 and pr[5] is not None else None),
+               kH=(pr[6]._v if len(pr) > 6 and pr[6] is not None else None)) for pr in provers]
     n0 = n = len(st[0]["c"])
     assert all(len(s["c"]) == len(s["d"]) == len(s["G"]) == len(s["Gp"]) == n for s in st) and n & (n - 1) == 0
     for s in st:
@@ -74,12 +80,14 @@ def ipa_rounds_many(provers: Sequence[Tuple[Sequence[G1Point], Sequence[G1Point]
             c, d, kG, kGp, G, Gp = s["c"], s["d"], s["kG"], s["kGp"], s["G"], s["Gp"]
             ip_l = sum(c[i] * d[n + i] for i in range(n)) % R            # <c_L, d_R>
             ip_r = sum(c[n + i] * d[i] for i in range(n)) % R            # <c_R, d_L>
+            if s["kH"] is not None:                                      # H stands for H * kH
+                ip_l, ip_r = ip_l * s["kH"] % R, ip_r * s["kH"] % R
             # L_C = MSM(G_R, c_L) + H <c_L, d_R>;  L_D = MSM(G'_L, d_R);  R_C = MSM(G_L, c_R) + H <c_R, d_L>;  R_D = MSM(G'_R, d_L)
             jobs += [([G[j] for j in right] + [s["H"]], [S(c[j % (2 * n) - n] * kG[j] % R) for j in right] + [S(ip_l)]),
                      ([Gp[j] for j in left], [S(d[n + j % (2 * n)] * kGp[j] % R) for j in left]),
                      ([G[j] for j in left] + [s["H"]], [S(c[n + j % (2 * n)] * kG[j] % R) for j in left] + [S(ip_r)]),
                      ([Gp[j] for j in right], [S(d[j % (2 * n) - n] * kGp[j] % R) for j in right])]
-        res = compute_MSM_batch(jobs)
+        res = compute_MSM_batch(jobs) if table is None else table.msm_many(jobs)
         for i, (s, ng) in enumerate(zip(st, next_gammas)):
             L_C, L_D, R_C, R_D = res[4 * i: 4 * i + 4]
             s["LC"].append(L_C); s["RC"].append(R_C); s["LD"].append(L_D); s["RD"].append(R_D)
@@ -96,11 +104,12 @@ def ipa_rounds_many(provers: Sequence[Tuple[Sequence[G1Point], Sequence[G1Point]
 
 def ipa_rounds(crs_G_vec: Sequence[G1Point], crs_G_prime_vec: Sequence[G1Point], H: G1Point, vec_c: Sequence[Scalar],
                vec_d: Sequence[Scalar], next_gamma: Callable[[G1Point, G1Point, G1Point, G1Point], Scalar],
-               G_prime_coeffs: Sequence[Scalar] = None):
+               G_prime_coeffs: Sequence[Scalar] = None, H_coeff: Scalar = None, table=None):
     """ipa.py:117-151.  `H` is crs_H * beta (ipa.py:110); vec_c / vec_d are the blinded vectors (after ipa.py:107-109).
     G_prime_coeffs (optional): crs_G_prime_vec[j] stands for crs_G_prime_vec[j] * G_prime_coeffs[j] (see ipa_rounds_many).
+    H_coeff (optional): `H` stands for H * H_coeff (pass crs_H and beta).  table (optional): a FixedBaseTable holding every base.
     -> (vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final)."""
-    return ipa_rounds_many([(crs_G_vec, crs_G_prime_vec, H, vec_c, vec_d, G_prime_coeffs)], [next_gamma])[0]
+    return ipa_rounds_many([(crs_G_vec, crs_G_prime_vec, H, vec_c, vec_d, G_prime_coeffs, H_coeff)], [next_gamma], table=table)[0]
 
 
 def same_msm_rounds_many(provers: Sequence[Tuple[Sequence[G1Point], Sequence[G1Point], Sequence[G1Point], Sequence[Scalar]]],
@@ -148,17 +157,21 @@ def same_msm_rounds(crs_G_vec: Sequence[G1Point], vec_T: Sequence[G1Point], vec_
     return same_msm_rounds_many([(crs_G_vec, vec_T, vec_U, vec_x)], [next_gamma])[0]
 
 
-def shuffle_permute_and_commit_input(crs, vec_R: Sequence[G1Point], vec_S: Sequence[G1Point], permutation: Sequence[int], k: Scalar
-                                     ) -> Tuple[List[G1Point], List[G1Point], G1Point, List[Scalar]]:
+def shuffle_permute_and_commit_input(crs, vec_R: Sequence[G1Point], vec_S: Sequence[G1Point], permutation: Sequence[int], k: Scalar,
+                                     table=None) -> Tuple[List[G1Point], List[G1Point], G1Point, List[Scalar]]:
     """Drop-in for curdleproofs.py:301-321: vec_T = perm([R * k]), vec_U = perm([S * k]) as one same-scalar launch, M as one GPU
-    MSM over vec_G | vec_H.  Draws the N_BLINDERS blinders exactly where the reference does (util.py:81-82)."""
+    MSM over vec_G | vec_H.  Draws the N_BLINDERS blinders exactly where the reference does (util.py:81-82).
+    table (optional): a FixedBaseTable holding crs.vec_G and crs.vec_H (FixedBaseTable.for_crs(crs)); M then comes from the table."""
     ell = len(crs.vec_G)
     both = batch_mul_same_scalar(list(vec_R) + list(vec_S), k)
     vec_T = [both[j] for j in permutation]                               # get_permutation, util.py:93-96
     vec_U = [both[len(vec_R) + j] for j in permutation]
     sigma_ell = [Scalar(j) for j in permutation]
     vec_m_blinders = [random_scalar() for _ in range(N_BLINDERS)]
-    M = compute_MSM(list(crs.vec_G) + list(crs.vec_H), sigma_ell + vec_m_blinders)
+    if table is None:
+        M = compute_MSM(list(crs.vec_G) + list(crs.vec_H), sigma_ell + vec_m_blinders)
+    else:
+        M = table.msm(sigma_ell + vec_m_blinders, list(crs.vec_G) + list(crs.vec_H))
     assert len(sigma_ell) == ell
     return vec_T, vec_U, M, vec_m_blinders
 

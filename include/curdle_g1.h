@@ -106,6 +106,8 @@ void* cg1_ctx_stream(cg1_ctx* ctx);                                  /* the cont
  *   transcripts         "merlin_rows" (1: block program when the operation list fits), "merlin_sync" (1: lanes of a wave permute together),
  *                       "merlin_lanes" (1..64 transcripts per wave)
  *   verifier front-end  "fe_rows" (1: block program, 0: byte-level machine), "fe_timed" (shader-clock split of a launch), "fe_prio" (0..3)
+ *   fixed-base tables   "fixed_slice" (terms per workgroup of k_fixed_msm, 1..128; 0: by the size of the call), "fixed_waves" (4, 8, 16 waves per
+ *                       workgroup; 0: by the size of the call)
  * Unknown names and out-of-range values return CG1_ERR_ARG. */
 int  cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value);
 
@@ -512,6 +514,41 @@ int cg1_opening_prove_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96 /
  * context at the first call (csrc/kernels_generator.h: signed 8-bit windows, 32 mixed additions and one inversion per output against
  * k_batch_mul's 255 doublings).  Device pointers; d_out_affine96 (zeros = identity) and d_out48 (compressed) may each be NULL, not both. */
 int cg1_generator_mul_device(cg1_ctx* ctx, const void* d_scalars32, size_t n, void* d_out_affine96 /* nullable */, void* d_out48 /* nullable */);
+
+/* ---- Resident tables of FIXED bases, and MSMs over them without a doubling (csrc/kernels_fixed.h).
+ * The bases the protocol's small MSMs run over never change (the CRS, crs.py:92-101).  A table holds, for every base B and every
+ * window w = 0 .. 31, the 128 multiples d * 2^(8 w) * B as prepared records -- 512 KiB per base, built in one call for all bases
+ * (the builder of the generator's table above) -- and a term k * B is then at most 32 additions of records picked by the signed
+ * 8-bit digits of k.  The sum is finished on the device: no bucket reduction, no host Horner.
+ *   cg1_fixed_create   n_bases = 1 .. CG1_FIXED_MAX_BASES (beyond, the table would pass 512 MiB: CG1_ERR_ARG).  A base is any point of
+ *                      the CURVE (it need not lie in G1) or the all-zero identity record, whose entries are identities; a coordinate
+ *                      >= p is CG1_ERR_ENCODING, a point off the curve CG1_ERR_NOT_ON_CURVE.  NULL on failure, the status in *status
+ *                      (nullable).  The table lives on ctx's device and is used with contexts of that device; destroy it before them.
+ *   cg1_fixed_msm      n_msm MSMs in one launch: MSM j sums term_scalars32[t] * base[term_base[t] & 0x7fffffff] over the terms
+ *                      t = offsets[j] .. offsets[j + 1] - 1 (offsets[0] = 0; bit 31 of term_base[t] = the NEGATED base, cg1_lincomb_batch's
+ *                      convention; an index may repeat).  An empty MSM is the identity.  Host buffers in and out; out_blobs144 and
+ *                      out_comp48 may each be NULL, not both.  At most CG1_FIXED_MAX_MSMS MSMs per call and CG1_FIXED_MAX_TERMS terms
+ *                      per MSM, an index outside the table: CG1_ERR_ARG.  A scalar >= r: CG1_ERR_ENCODING for the whole call, checked
+ *                      before anything is written -- never reduced: outside G1 k P depends on k itself, not only on k mod r.
+ *   cg1_fixed_msm_device   the same over DEVICE arrays (indices, scalars, n_msm + 1 offsets; n_terms = their length, max_terms >= the
+ *                      longest MSM: both size the launch, and an MSM that exceeds them fails the call with CG1_ERR_ARG without reading
+ *                      past the arrays).  Results stay on the device as affine96 (zeros = identity) and / or compressed48, enqueued on
+ *                      the context's stream; the call returns once the status word is back.  A failed call writes no output.
+ *   cg1_fixed_digits   host only, test support: the recoding k = sum_w out[w] 2^(8 w), |out[w]| <= 128, compiled from the function the
+ *                      kernel runs (csrc/fixed_digits.h).  Meaningful for scalars below r. */
+#define CG1_FIXED_MAX_BASES 1024
+#define CG1_FIXED_MAX_MSMS  1024
+#define CG1_FIXED_MAX_TERMS 2048
+typedef struct cg1_fixed cg1_fixed;
+cg1_fixed* cg1_fixed_create(cg1_ctx* ctx, const uint8_t* bases_affine96, size_t n_bases, int* status /* nullable */);
+void   cg1_fixed_destroy(cg1_fixed* tab);
+size_t cg1_fixed_len(const cg1_fixed* tab);
+size_t cg1_fixed_bytes(const cg1_fixed* tab);                        /* device bytes of the table's records */
+int cg1_fixed_msm(cg1_ctx* ctx, cg1_fixed* tab, const uint32_t* term_base, const uint8_t* term_scalars32, const uint32_t* offsets, size_t n_msm,
+                  uint8_t* out_blobs144 /* nullable */, uint8_t* out_comp48 /* nullable */);
+int cg1_fixed_msm_device(cg1_ctx* ctx, cg1_fixed* tab, const void* d_term_base, const void* d_term_scalars32, const void* d_offsets, size_t n_msm,
+                         size_t n_terms, size_t max_terms, void* d_out_affine96 /* nullable */, void* d_out_comp48 /* nullable */);
+void cg1_fixed_digits(const uint8_t scalar32[32], int16_t out[32]);
 
 #ifdef __cplusplus
 }
