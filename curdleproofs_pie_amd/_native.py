@@ -258,6 +258,13 @@ cg1_fixed_msm = _proto("cg1_fixed_msm", c_int, c_void_p, c_void_p, c_void_p, c_v
 cg1_fixed_msm_device = _proto("cg1_fixed_msm_device", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p)
 cg1_fixed_digits = _proto("cg1_fixed_digits", None, _u8p, c_void_p)
 FIXED_MAX_BASES, FIXED_MAX_MSMS, FIXED_MAX_TERMS = 1024, 1024, 2048      # CG1_FIXED_MAX_* of include/curdle_g1.h
+# the inner-product argument proved on the device (csrc/kernels_ipa.h, csrc/ipa_rounds.h)
+cg1_ipa_proof_bytes = _proto("cg1_ipa_proof_bytes", c_size_t, c_size_t)
+cg1_ipa_prove_device = _proto("cg1_ipa_prove_device", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+cg1_ipa_round_emulate = _proto("cg1_ipa_round_emulate", c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p)
+IPA_MAX_N, IPA_MAX_PROVERS = 2048, 256                                   # CG1_IPA_MAX_* of include/curdle_g1.h
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -279,6 +286,7 @@ EXPORTED_SYMBOLS = [
     "cg1_validate_compressed", "cg1_fp_jacobi", "cg1_batch_decompress_pool", "cg1_batch_subgroup_pool", "cg1_batch_subgroup", "cg1_lincomb_batch", "cg1_lincomb_batch_pool", "cg1_glv_split", "cg1_batch_decompress_rows",
     "cg1_probe_add_chain", "cg1_msm_blobs", "cg1_stage_reserve", "cg1_msm_blobs_device", "cg1_vec_create", "cg1_vec_destroy", "cg1_vec_len", "cg1_msm_vec", "cg1_batch_normalize", "cg1_batch_from_affine96", "cg1_get_last_launches", "cg1_plan_describe",
     "cg1_fixed_create", "cg1_fixed_destroy", "cg1_fixed_len", "cg1_fixed_bytes", "cg1_fixed_msm", "cg1_fixed_msm_device", "cg1_fixed_digits",
+    "cg1_ipa_proof_bytes", "cg1_ipa_prove_device", "cg1_ipa_round_emulate",
 ]
 
 
@@ -481,6 +489,23 @@ class Context:
         g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
         self.check(cg1_fixed_msm_device(self.handle, tab.handle, g(d_term_base), g(d_scalars32), g(d_offsets), n_msm, n_terms, max_terms,
                                         g(d_out_affine96), g(d_out_comp48)))
+
+    def ipa_prove_device(self, tab: "FixedTable", n: int, n_provers: int, g_index, g_prime_index, h_index, g_prime_coeffs32, cd48: bytes, z32: bytes,
+                         vec_c32: bytes, vec_d32: bytes, vec_r_c32: bytes, vec_r_d32: bytes, states208: bytes, want_clocks: bool = False):
+        """cg1_ipa_prove_device: n_provers inner-product arguments of length n over the table, one launch chain, one wait.
+        -> (proofs, states) as bytes [, clocks]; raises (check) on a refusal, and then nothing the caller holds has changed."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        assert len(g_index) == len(g_prime_index) == n * n_provers and len(h_index) == n_provers
+        gi = (ctypes.c_uint32 * max(1, len(g_index)))(*g_index)
+        gpi = (ctypes.c_uint32 * max(1, len(g_prime_index)))(*g_prime_index)
+        hi = (ctypes.c_uint32 * max(1, n_provers))(*h_index)
+        st = ctypes.create_string_buffer(bytes(states208), 208 * n_provers)
+        out = ctypes.create_string_buffer(max(1, int(cg1_ipa_proof_bytes(n)) * n_provers))
+        ck = (ctypes.c_uint32 * (4 * max(1, n_provers)))() if want_clocks else None
+        self.check(cg1_ipa_prove_device(self.handle, tab.handle, n, n_provers, gi, gpi, hi, g_prime_coeffs32, cd48, z32, vec_c32, vec_d32, vec_r_c32, vec_r_d32,
+                                        st, out, ck))
+        return (out.raw, st.raw, list(ck)) if want_clocks else (out.raw, st.raw)
 
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""

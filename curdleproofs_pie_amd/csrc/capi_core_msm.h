@@ -304,6 +304,7 @@ int cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value) {
   if (!strcmp(name, "small_msm")) { ctx->small_msm = value ? 1 : 0; return CG1_OK; }
   if (!strcmp(name, "fixed_slice")) { if (value < 0 || value > 128) return CG1_ERR_ARG; ctx->fixed_slice = value; return CG1_OK; }
   if (!strcmp(name, "fixed_waves")) { if (value != 0 && value != 4 && value != 8 && value != 16) return CG1_ERR_ARG; ctx->fixed_waves = value; return CG1_OK; }
+  if (!strcmp(name, "ipa_inv")) { if (value != 0 && value != 1) return CG1_ERR_ARG; ctx->ipa_inv = value; return CG1_OK; }
   if (!strcmp(name, "small_row_tail")) { ctx->small_row_tail = value ? 1 : 0; return CG1_OK; }
   if (!strcmp(name, "split")) { ctx->split = value ? 1 : 0; return CG1_OK; }
   if (!strcmp(name, "split_min_log2n")) { if (value < 10 || value > 31) return CG1_ERR_ARG; ctx->split_min_n = (size_t)1 << value; return CG1_OK; }

@@ -12,6 +12,7 @@ struct cg1_fixed {
   cg1::PointSum* d_sum = nullptr;                           // FX_MAX_MSMS records for k_fixed_finish
   cg1::PointWords* h_out = nullptr; cg1::PointWords* h_out_dev = nullptr;      // pinned + mapped: FX_MAX_MSMS records + the status record
   uint8_t* h_in = nullptr; uint8_t* h_in_dev = nullptr; void* d_in = nullptr; size_t cap_in = 0;      // offsets | indices | scalars of a host call
+  uint8_t* h_ipa = nullptr; uint8_t* d_ipa = nullptr; size_t cap_ipa = 0;      // cg1_ipa_prove_device's staging block and its device twin (capi_ipa.h)
 };
 
 namespace {
@@ -79,7 +80,7 @@ int fixed_enqueue(cg1_ctx* ctx, cg1_fixed* t, const uint32_t* d_tb, const uint32
   a.out_sum = (d_out96 || d_out48) ? t->d_sum : nullptr;
   hipLaunchKernelGGL(cg1::k_fixed_msm, dim3(Smax, M), dim3(shape.waves * 64), 0, ctx->stream, a);
   if (a.out_sum)
-    hipLaunchKernelGGL(cg1::k_fixed_finish, dim3((M + 63) / 64), dim3(64), 0, ctx->stream, (const cg1::PointSum*)t->d_sum, (const uint32_t*)a.status_out, M,
+    hipLaunchKernelGGL(cg1::k_fixed_finish, dim3((M + 3) / 4), dim3(64), 0, ctx->stream, (const cg1::PointSum*)t->d_sum, (const uint32_t*)a.status_out, M,
                        (uint32_t*)d_out96, (uint32_t*)d_out48);
   return CG1_OK;
 }
@@ -118,6 +119,8 @@ void cg1_fixed_destroy(cg1_fixed* t) {
   if (t->d_in) (void)hipFree(t->d_in);
   if (t->h_out) (void)hipHostFree(t->h_out);
   if (t->h_in) (void)hipHostFree(t->h_in);
+  if (t->d_ipa) (void)hipFree(t->d_ipa);
+  if (t->h_ipa) (void)hipHostFree(t->h_ipa);
   delete t;
 }
 size_t cg1_fixed_len(const cg1_fixed* t) { return t ? t->n_bases : 0; }

@@ -168,17 +168,55 @@ __global__ void __launch_bounds__(FX_THREADS) k_fixed_msm(FixedArgs a) {
   }
 }
 
-// The sums k_fixed_msm left on the device -> affine96 (standard words, zeros = identity) and / or compressed48, one lane per output and
-// one inversion each (k_generator_mul's tail).  A call whose status word is set writes nothing.
+// a^(p-2) with one limb per lane: fp_pow6's sliding window (width 3, ~380 squarings + ~96 multiplications) over row_mul, every row of
+// the wave inverting its own element.  The same products in the same order as fp_inv, so the same value, limb for limb after fp_norm.
+// An inversion is ONE dependent chain, and what it costs a lone wave is the instructions on that chain: ~150 per product here against
+// ~470 for the one-lane fp_mul (fp_row.h) -- and between two rounds of a device-resident argument (kernels_ipa.h) the chain IS the
+// kernel: measured in profiles/r07_ipa_device_timing.txt.
+__device__ __noinline__ uint32_t row_inv(uint32_t a, const RowK k) {
+  constexpr uint64_t e[6] = {H_INV_EXP[0], H_INV_EXP[1], H_INV_EXP[2], H_INV_EXP[3], H_INV_EXP[4], H_INV_EXP[5]};
+  const uint32_t a2 = row_mul(a, a, k);
+  const uint32_t t3 = row_mul(a, a2, k), t5 = row_mul(t3, a2, k), t7 = row_mul(t5, a2, k);
+  auto bit = [&](int i) -> unsigned { return (unsigned)((e[i >> 6] >> (i & 63)) & 1u); };
+  uint32_t r = k.one;
+  bool started = false;
+  int i = 383;
+  while (i >= 0 && !bit(i)) --i;
+#pragma unroll 1
+  while (i >= 0) {
+    if (!bit(i)) { r = row_mul(r, r, k); --i; continue; }
+    int j = i >= 2 ? i - 2 : 0;
+    while (!bit(j)) ++j;                                     // window [i .. j], odd value
+    unsigned val = 0;
+    for (int t = i; t >= j; --t) val = (val << 1) | bit(t);
+    const uint32_t lo = (val & 2u) ? t3 : a, hi = (val & 2u) ? t7 : t5, m = (val & 4u) ? hi : lo;
+    if (started) {
+      for (int t = i; t >= j; --t) r = row_mul(r, r, k);
+      r = row_mul(r, m, k);
+    } else {
+      r = m;
+      started = true;
+    }
+    i = j - 1;
+  }
+  return r;
+}
+
+// The sums k_fixed_msm left on the device -> affine96 (standard words, zeros = identity) and / or compressed48: one ROW of a wave per
+// output (four outputs per workgroup), one inversion each -- row_inv above -- and lane 0 of the row finishes on the one-lane form
+// (k_generator_mul's tail).  A call whose status word is set writes nothing.
 __global__ void __launch_bounds__(64) k_fixed_finish(const PointSum* __restrict__ sums, const uint32_t* __restrict__ status, uint32_t M,
                                                      uint32_t* __restrict__ out96, uint32_t* __restrict__ out48) {
-  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= M || status[0] != 0u) return;
-  const xyzz acc = load_sum(sums + i);
+  if (status[0] != 0u) return;                             // (uniform)
+  const RowK rk = row_constants();
+  const uint32_t i = blockIdx.x * 4u + rk.row;
+  const xyzz acc = load_sum(sums + (i < M ? i : M - 1u));  // every lane of the wave takes part in the row products: no early exit
+  const fp tinv = fp_norm(row_to_fp(row_inv(row_from_fp(fp_mul(acc.ZZ, acc.ZZZ), rk.lane16), rk)));
+  if (i >= M || rk.lane16 != 0u) return;
   uint32_t o[24];
   for (int k = 0; k < 24; ++k) o[k] = 0;
   if (!acc.inf) {
-    const fp t = fp_inv(fp_mul(acc.ZZ, acc.ZZZ));
+    const fp t = tinv;
     fp_to_words(fp_mul(acc.X, fp_mul(t, acc.ZZZ)), o);
     fp_to_words(fp_mul(acc.Y, fp_mul(t, acc.ZZ)), o + 12);
   }

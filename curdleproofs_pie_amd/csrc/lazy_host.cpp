@@ -2,6 +2,7 @@
 #include "lazy_host.h"
 #include "bls_consts.h"
 #include "pool.h"
+#include "ipa_rounds.h"
 #include "../../include/curdle_g1.h"
 
 #include <algorithm>
@@ -445,6 +446,63 @@ void cg1_fixed_digits(const uint8_t* scalar32, int16_t* out32) {
   uint32_t k[8];
   memcpy(k, scalar32, 32);
   (void)cg1::fixed_digits(k, out32, 1);
+}
+
+// The scalar schedule and the folds of the device prover of the inner-product argument (csrc/ipa_rounds.h: the functions k_ipa_step
+// runs, one lane per term there, a loop here): for the CPU tests.
+int cg1_ipa_round_emulate(int op, size_t n0, size_t len, uint8_t* c32, uint8_t* d32, uint8_t* kg32, uint8_t* kgp32, const uint8_t* kh32,
+                          const uint8_t* challenge32, const uint8_t* r_c32, const uint8_t* r_d32, const uint32_t* g_index, const uint32_t* g_prime_index,
+                          uint32_t h_index, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets) {
+  using cg1fr::fr;
+  auto pow2 = [](size_t v) { return v >= 2 && (v & (v - 1)) == 0; };
+  if (op < 0 || op > 2 || !pow2(n0) || n0 > CG1_IPA_MAX_N || !pow2(len) || len > n0 || (op != 2 && len != n0) || !c32 || !d32 || !kg32 || !kgp32 || !kh32) return CG1_ERR_ARG;
+  if (op != 2 && (!r_c32 || !r_d32)) return CG1_ERR_ARG;
+  if (op == 1 && !challenge32) return CG1_ERR_ARG;
+  if (op != 1 && (!g_index || !g_prime_index || !out_term_base || !out_term_scalars32 || !out_offsets)) return CG1_ERR_ARG;
+  bool ok = true;
+  auto load = [&](const uint8_t* src, size_t count) {
+    std::vector<fr> v(count);
+    for (size_t i = 0; i < count; ++i) ok = cg1fr::fr_from_le32(src + 32 * i, v[i]) && ok;
+    return v;
+  };
+  std::vector<fr> c = load(c32, len), d = load(d32, len), kg = load(kg32, n0), kgp = load(kgp32, n0), kh = load(kh32, 1);
+  std::vector<fr> ch = challenge32 ? load(challenge32, 1) : std::vector<fr>(), rc = op != 2 ? load(r_c32, n0) : std::vector<fr>(),
+                  rd = op != 2 ? load(r_d32, n0) : std::vector<fr>();
+  if (!ok) return CG1_ERR_ENCODING;
+  cg1ipa::View v{c.data(), d.data(), kg.data(), kgp.data(), g_index, g_prime_index, h_index, (uint32_t)n0};
+  const uint32_t h = (uint32_t)n0 / 2;
+  if (op == 0) {
+    std::vector<uint64_t> sc(4 * (size_t)cg1ipa::step1_terms((uint32_t)n0));
+    for (uint32_t j = 0; j < n0; ++j) cg1ipa::step1_term(v, j, rc[j], rd[j], out_term_base, sc.data());
+    memcpy(out_term_scalars32, sc.data(), sc.size() * 8);
+    cg1ipa::step1_offsets((uint32_t)n0, 0, out_offsets);
+    return CG1_OK;
+  }
+  if (op == 1) {
+    for (uint32_t j = 0; j < n0; ++j) cg1ipa::blind_elem(v, j, ch[0], rc[j], rd[j]);
+  } else {
+    const uint32_t half = (uint32_t)len / 2;
+    std::vector<uint64_t> sc(4 * (size_t)cg1ipa::round_terms((uint32_t)n0));
+    fr sl = cg1fr::fr_zero(), sr = cg1fr::fr_zero();
+    for (uint32_t t = 0; t < h; ++t) {
+      fr pl, pr;
+      cg1ipa::round_term(v, half, t, out_term_base, sc.data(), pl, pr);
+      sl = cg1fr::fr_add(sl, pl); sr = cg1fr::fr_add(sr, pr);
+    }
+    cg1ipa::round_h_terms(v, kh[0], sl, sr, out_term_base, sc.data());
+    memcpy(out_term_scalars32, sc.data(), sc.size() * 8);
+    cg1ipa::round_offsets((uint32_t)n0, 0, out_offsets);
+    if (challenge32) {
+      if (cg1fr::fr_is_zero(ch[0])) return CG1_ERR_ARG;
+      const fr ginv = cg1ipa::fr_inv_binary(ch[0]);
+      if (!cg1fr::fr_eq(ginv, cg1fr::fr_inv(ch[0]))) return CG1_ERR_ARG;          // the two inversions agree, or the test hears of it
+      for (uint32_t t = 0; t < h; ++t) cg1ipa::fold_elem(v, half, t, ch[0], ginv);
+      len = half;
+    }
+  }
+  for (size_t i = 0; i < len; ++i) { cg1fr::fr_to_le32(c[i], c32 + 32 * i); cg1fr::fr_to_le32(d[i], d32 + 32 * i); }
+  for (size_t i = 0; i < n0; ++i) { cg1fr::fr_to_le32(kg[i], kg32 + 32 * i); cg1fr::fr_to_le32(kgp[i], kgp32 + 32 * i); }
+  return CG1_OK;
 }
 
 }  // extern "C"

@@ -70,6 +70,7 @@ int pick_window(size_t n);
 #include "kernels_merlin.h"
 #include "kernels_frontend.h"
 #include "kernels_opening.h"
+#include "kernels_ipa.h"           // k_ipa_step: the Fr and transcript half of the inner-product argument's prover
 #include "host_context.h"          // Ctx: streams, helper threads, scratch buffers
 #include "host_chains.h"           // planner + launch chains: regime A, k_msm_small, regime B
 #include "capi_core_msm.h"         // cg1_* : host operators, context, memory, parameters, MSM entry points
@@ -80,3 +81,4 @@ int pick_window(size_t n);
 #include "capi_frontend.h"         // the shuffle verifier front-end on the device
 #include "capi_rows_probes.h"      // scalar rows, compression, synthetic scalars, probes
 #include "capi_fixed.h"            // resident fixed-base tables: cg1_fixed_*
+#include "capi_ipa.h"              // the inner-product argument proved on the device: cg1_ipa_prove_device

@@ -86,6 +86,12 @@ class FixedBaseTable:
         except Exception:
             pass
 
+    def _ctx_lock(self):
+        """The lock every call on this table's context runs under; raises when the table is closed."""
+        if self._tab is None or not self._tab.handle or not self._ctx.handle:
+            raise N.NativeError("the fixed-base table is closed")
+        return _LOCK
+
     def _indices(self, bases: Sequence[Base], n: int):
         pos = self._pos
         m = len(self._points)

@@ -112,6 +112,78 @@ def ipa_rounds(crs_G_vec: Sequence[G1Point], crs_G_prime_vec: Sequence[G1Point],
     return ipa_rounds_many([(crs_G_vec, crs_G_prime_vec, H, vec_c, vec_d, G_prime_coeffs, H_coeff)], [next_gamma], table=table)[0]
 
 
+def ipa_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence) -> List[tuple]:
+    """IPA.new (ipa.py:75-153) after its blinder draw, for SEVERAL independent provers of one vector length in step, proved ON THE DEVICE:
+    one launch chain (csrc/kernels_ipa.h), one wait -- the MSMs over the resident `table` (a fixed_base.FixedBaseTable), the
+    transcript, gamma^-1 and the folds between them never come back to the host.
+    provers[p] = (crs_G_vec, crs_G_prime_vec, crs_H, C, D, z, vec_c, vec_d, vec_r_c, vec_r_d[, G_prime_coeffs]): bases are objects of the
+    table or indices into it (KeyError / IndexError, FixedBaseTable._indices); C, D are G1Points or their 48-byte encodings (only
+    hashed); z and the vectors are Scalars, vec_c / vec_d UNBLINDED (the call blinds them with the alpha it draws) and the blinders
+    the caller's own (the reference's generate_ipa_blinders, ipa.py:27-48); G_prime_coeffs as in ipa_rounds_many.
+    transcripts[p]: that prover's CurdleproofsTranscript, advanced to the state after the last ipa_gamma -- the caller goes on exactly
+    where the reference would.  -> per prover (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final), the fields of IPA.
+    A refused call (ValueError: n not a power of two >= 2; NativeError: a scalar >= r, an undecodable C or D) changes nothing."""
+    import ctypes
+
+    from . import _native as N
+    from .py_arkworks_bls12381 import pack_scalars, points_to_compressed
+
+    provers = [tuple(pr) for pr in provers]
+    if len(provers) != len(transcripts):
+        raise ValueError("one transcript per prover")
+    if not provers:
+        return []
+    n = len(provers[0][6])
+    if n < 2 or n & (n - 1) or n > N.IPA_MAX_N:
+        raise ValueError(f"the vectors of an inner-product argument have a power-of-two length in 2 .. {N.IPA_MAX_N}, not {n}")
+    if any(not (len(pr[0]) == len(pr[1]) == len(pr[6]) == len(pr[7]) == len(pr[8]) == len(pr[9]) == n) for pr in provers):
+        raise ValueError("provers in step share one vector length")
+    coeffs = [pr[10] if len(pr) > 10 else None for pr in provers]
+    if any(k is not None and len(k) != n for k in coeffs):
+        raise ValueError("G_prime_coeffs has one entry per base")
+    pts = [x for pr in provers for x in pr[3:5] if type(x) is G1Point]
+    enc = iter(points_to_compressed(pts))
+    out: List[tuple] = []
+    with table._ctx_lock():
+        for lo in range(0, len(provers), N.IPA_MAX_PROVERS):             # (more provers than one chain carries: several calls)
+            part, P = provers[lo: lo + N.IPA_MAX_PROVERS], len(provers[lo: lo + N.IPA_MAX_PROVERS])
+            gi, gpi, hi, cd, flat = [], [], [], [], [[] for _ in range(6)]
+            for pr, k in zip(part, coeffs[lo: lo + P]):
+                gi.extend(table._indices(pr[0], n)); gpi.extend(table._indices(pr[1], n)); hi.extend(table._indices([pr[2]], 1))
+                cd.extend(bytes(x) if type(x) is not G1Point else next(enc) for x in pr[3:5])
+                if any(len(e) != 48 for e in cd[-2:]):
+                    raise ValueError("C and D are G1Points or 48-byte encodings")
+                flat[0].append(pr[5])
+                for dst, src in zip(flat[1:5], pr[6:10]):
+                    dst.extend(src)
+                if any(c is not None for c in coeffs[lo: lo + P]):
+                    flat[5].extend(k if k is not None else [1] * n)
+            bufs = []
+            for vals in flat:
+                b = ctypes.create_string_buffer(32 * max(1, len(vals)))
+                pack_scalars(vals, ctypes.addressof(b), len(vals))
+                bufs.append(b)
+            states = b"".join(bytes(t.strobe._st.raw[:N.MERLIN_STATE_BYTES]) for t in transcripts[lo: lo + P])
+            proofs, new_states = table._ctx.ipa_prove_device(table._tab, n, P, gi, gpi, hi, bufs[5] if flat[5] else None, b"".join(cd), bufs[0], bufs[1],
+                                                             bufs[2], bufs[3], bufs[4], states)
+            lg, pb, S = n.bit_length() - 1, len(proofs) // P, N.MERLIN_STATE_BYTES
+            for i, t in enumerate(transcripts[lo: lo + P]):
+                ctypes.memmove(t.strobe._st, new_states[S * i: S * i + S], S)
+                raw = proofs[pb * i: pb * i + pb]
+                P48 = [G1Point.from_compressed_bytes_unchecked(raw[48 * j: 48 * j + 48]) for j in range(2 + 4 * lg)]
+                vecs = [P48[2 + q * lg: 2 + (q + 1) * lg] for q in range(4)]
+                out.append((P48[0], P48[1], *vecs, Scalar.from_le_bytes(raw[pb - 64: pb - 32]), Scalar.from_le_bytes(raw[pb - 32:])))
+    return out
+
+
+def ipa_prove_device(table, crs_G_vec, crs_G_prime_vec, crs_H, C, D, z: Scalar, vec_c: Sequence[Scalar], vec_d: Sequence[Scalar],
+                     vec_r_c: Sequence[Scalar], vec_r_d: Sequence[Scalar], transcript, G_prime_coeffs: Sequence[Scalar] = None):
+    """IPA.new (ipa.py:75-153) after `generate_ipa_blinders`, on the device: see ipa_prove_device_many.  `transcript` is advanced as the
+    reference advances it.  -> (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final)."""
+    pr = (crs_G_vec, crs_G_prime_vec, crs_H, C, D, z, vec_c, vec_d, vec_r_c, vec_r_d) + ((G_prime_coeffs,) if G_prime_coeffs is not None else ())
+    return ipa_prove_device_many(table, [pr], [transcript])[0]
+
+
 def same_msm_rounds_many(provers: Sequence[Tuple[Sequence[G1Point], Sequence[G1Point], Sequence[G1Point], Sequence[Scalar]]],
                          next_gammas: Sequence[Callable[..., Scalar]]):
     """same_msm.py:93-130 for several independent provers in step: per round ONE batched MSM call (6 MSMs per prover), the

@@ -550,6 +550,47 @@ int cg1_fixed_msm_device(cg1_ctx* ctx, cg1_fixed* tab, const void* d_term_base, 
                          size_t n_terms, size_t max_terms, void* d_out_affine96 /* nullable */, void* d_out_comp48 /* nullable */);
 void cg1_fixed_digits(const uint8_t scalar32[32], int16_t out[32]);
 
+/* ---- The inner-product argument PROVED on the device: IPA.new (ipa.py:75-153) after its blinders are drawn, for n_provers independent
+ * provers of one vector length n in step, as ONE launch chain with one host wait (csrc/kernels_ipa.h, csrc/ipa_rounds.h).
+ * The bases stay what they are -- entries of a cg1_fixed table -- and the round challenges fold into the scalars: per round one
+ * k_fixed_msm launch of 4 MSMs of n / 2 (+ 1) terms per prover, one k_fixed_finish (the encodings, on the device) and one k_ipa_step
+ * (the transcript over the prover's own state, gamma^-1, the folds, the next round's scalars): 1 + 3 (lg n + 1) launches in all.
+ *   per prover p, host buffers:
+ *     g_index[p n ..], g_prime_index[p n ..]   table indices of crs_G_vec / crs_G_prime_vec;  h_index[p]  that of crs_H (crs_H * beta is
+ *                         never formed: beta multiplies the inner-product scalars)
+ *     g_prime_coeffs32    NULL, or n scalars per prover: entry j of G' stands for base * coeff (grand_prod.py:64-71 without a multiplication)
+ *     cd48                C | D as 48-byte encodings.  They are only HASHED: validated (compression flag, x < p, on the curve; no
+ *                         subgroup test) and absorbed re-serialised as the reference does (an identity as C0 00 .. 00)
+ *     z32, vec_c32, vec_d32, vec_r_c32, vec_r_d32   canonical scalars; the blinders are the caller's (generate_ipa_blinders, ipa.py:27-48)
+ *     states208           in: the transcript where IPA.new would find it; out: after the last ipa_gamma
+ *     out_proofs          cg1_ipa_proof_bytes(n) = (2 + 4 lg n) 48 + 64 bytes each, IPA.to_bytes order:
+ *                         B_c | B_d | vec_L_C | vec_R_C | vec_L_D | vec_R_D | c_final | d_final
+ *     out_clocks          NULL, or 4 words per prover: clock ticks (s_memtime) of its lane 0 in the transcript | in the inversions of gamma | in the
+ *                         whole of the steps that emit terms (all but the last) | steps counted
+ *   The returned status covers the whole call, and a refused call leaves out_proofs and states208 untouched.  Refused before anything
+ *   is written: n not a power of two in 2 .. CG1_IPA_MAX_N (the reference itself fails at n = 1; beyond, an MSM would pass
+ *   CG1_FIXED_MAX_TERMS) or more than CG1_IPA_MAX_PROVERS provers (4 MSMs each per launch against CG1_FIXED_MAX_MSMS: larger batches
+ *   are REFUSED, not chunked -- the caller splits them), an index outside the table, a table of another device: CG1_ERR_ARG; a scalar
+ *   >= r: CG1_ERR_ENCODING (never reduced); an undecodable C or D: cg1_validate_compressed's status.
+ *   cg1_ctx_set_param "ipa_inv" (0: binary Euclid, 1: a^(r-2)) picks the inversion of a round challenge -- an A/B switch, same bytes.
+ *   cg1_ipa_round_emulate   host only, test support: the scalar schedule and the folds compiled from the header the kernel runs
+ *                         (csrc/ipa_rounds.h).  State: c32 / d32 (len scalars, in and out), kg32 / kgp32 (n0 coefficients of the original
+ *                         indices, in and out), kh32.  op 0: the step-1 terms (B_c over r_c32, B_d over r_d32 and kgp32; 2 MSMs, 3
+ *                         offsets; len = n0).  op 1: c <- r_c + x c, d <- r_d + x d with x = challenge32 (alpha).  op 2: the round's terms
+ *                         at the current length len (4 MSMs -- L_C, L_D, R_C, R_D --, 5 offsets, 2 n0 + 2 terms; out_term_base bit 31 =
+ *                         the negated base, never set), then, when challenge32 (gamma) is not NULL, the fold: c32 / d32 hold len / 2
+ *                         scalars afterwards.  The same refusals: CG1_ERR_ARG / CG1_ERR_ENCODING. */
+#define CG1_IPA_MAX_N       2048
+#define CG1_IPA_MAX_PROVERS 256
+size_t cg1_ipa_proof_bytes(size_t n);                               /* 0 when n is not a power of two >= 2 */
+int cg1_ipa_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t n, size_t n_provers, const uint32_t* g_index, const uint32_t* g_prime_index,
+                         const uint32_t* h_index, const uint8_t* g_prime_coeffs32 /* nullable */, const uint8_t* cd48, const uint8_t* z32,
+                         const uint8_t* vec_c32, const uint8_t* vec_d32, const uint8_t* vec_r_c32, const uint8_t* vec_r_d32, uint8_t* states208,
+                         uint8_t* out_proofs, uint32_t* out_clocks /* nullable */);
+int cg1_ipa_round_emulate(int op, size_t n0, size_t len, uint8_t* c32, uint8_t* d32, uint8_t* kg32, uint8_t* kgp32, const uint8_t* kh32,
+                          const uint8_t* challenge32 /* nullable for op 2 */, const uint8_t* r_c32, const uint8_t* r_d32, const uint32_t* g_index,
+                          const uint32_t* g_prime_index, uint32_t h_index, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets);
+
 #ifdef __cplusplus
 }
 #endif
