@@ -265,6 +265,22 @@ cg1_ipa_prove_device = _proto("cg1_ipa_prove_device", c_int, c_void_p, c_void_p,
 cg1_ipa_round_emulate = _proto("cg1_ipa_round_emulate", c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p)
 IPA_MAX_N, IPA_MAX_PROVERS = 2048, 256                                   # CG1_IPA_MAX_* of include/curdle_g1.h
+# light tables of variable bases (csrc/kernels_light.h)
+cg1_light_create = _proto("cg1_light_create", c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_int))
+cg1_light_destroy = _proto("cg1_light_destroy", None, c_void_p)
+cg1_light_len = _proto("cg1_light_len", c_size_t, c_void_p)
+cg1_light_bytes = _proto("cg1_light_bytes", c_size_t, c_void_p)
+cg1_light_msm = _proto("cg1_light_msm", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p)
+cg1_light_msm_device = _proto("cg1_light_msm_device", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p)
+cg1_light_digits = _proto("cg1_light_digits", c_int, _u8p, c_void_p)
+LIGHT_WINDOW_BITS, LIGHT_MAX_BASES, LIGHT_MAX_MSMS, LIGHT_MAX_TERMS = 4, 16384, 1024, 2048      # CG1_LIGHT_* of include/curdle_g1.h
+# the same-MSM argument proved on the device (csrc/kernels_same_msm.h, csrc/same_msm_rounds.h)
+cg1_same_msm_proof_bytes = _proto("cg1_same_msm_proof_bytes", c_size_t, c_size_t)
+cg1_same_msm_prove_device = _proto("cg1_same_msm_prove_device", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p)
+cg1_same_msm_round_emulate = _proto("cg1_same_msm_round_emulate", c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p)
+SAME_MSM_MAX_N, SAME_MSM_MAX_PROVERS = 1024, 64                          # CG1_SAME_MSM_MAX_* of include/curdle_g1.h
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -287,6 +303,8 @@ EXPORTED_SYMBOLS = [
     "cg1_probe_add_chain", "cg1_msm_blobs", "cg1_stage_reserve", "cg1_msm_blobs_device", "cg1_vec_create", "cg1_vec_destroy", "cg1_vec_len", "cg1_msm_vec", "cg1_batch_normalize", "cg1_batch_from_affine96", "cg1_get_last_launches", "cg1_plan_describe",
     "cg1_fixed_create", "cg1_fixed_destroy", "cg1_fixed_len", "cg1_fixed_bytes", "cg1_fixed_msm", "cg1_fixed_msm_device", "cg1_fixed_digits",
     "cg1_ipa_proof_bytes", "cg1_ipa_prove_device", "cg1_ipa_round_emulate",
+    "cg1_light_create", "cg1_light_destroy", "cg1_light_len", "cg1_light_bytes", "cg1_light_msm", "cg1_light_msm_device", "cg1_light_digits",
+    "cg1_same_msm_proof_bytes", "cg1_same_msm_prove_device", "cg1_same_msm_round_emulate",
 ]
 
 
@@ -490,6 +508,34 @@ class Context:
         self.check(cg1_fixed_msm_device(self.handle, tab.handle, g(d_term_base), g(d_scalars32), g(d_offsets), n_msm, n_terms, max_terms,
                                         g(d_out_affine96), g(d_out_comp48)))
 
+    def light_table(self, bases_affine96: bytes, n_bases: int) -> "LightTable":
+        """A light table of `n_bases` variable bases (cg1_light): built on the device in the call, 128 KiB of XYZZ records per base."""
+        return LightTable(self, bases_affine96, n_bases)
+
+    def light_msm_host(self, tab: "LightTable", term_base, scalars32: bytes, offsets, compressed: bool = False) -> list:
+        """cg1_light_msm: fixed_msm_host over a light table."""
+        if not tab.handle:
+            raise NativeError("the light table is closed")
+        m = len(offsets) - 1
+        n = offsets[-1]
+        assert len(term_base) >= n and len(scalars32) >= 32 * n
+        tb = (ctypes.c_uint32 * max(n, 1))(*term_base[:n])
+        arr = (ctypes.c_uint32 * (m + 1))(*offsets)
+        w = 48 if compressed else POINT_BYTES
+        out = ctypes.create_string_buffer(w * max(m, 1))
+        self.check(cg1_light_msm(self.handle, tab.handle, tb, scalars32, arr, m, None if compressed else out, out if compressed else None))
+        raw = out.raw
+        return [raw[w * j: w * (j + 1)] for j in range(m)]
+
+    def light_msm_device(self, tab: "LightTable", d_term_base, d_scalars32, d_offsets, n_msm: int, n_terms: int, max_terms: int,
+                         d_out_affine96=None, d_out_comp48=None) -> None:
+        """cg1_light_msm_device: device arrays in, affine96 and / or compressed48 left in device buffers."""
+        if not tab.handle:
+            raise NativeError("the light table is closed")
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        self.check(cg1_light_msm_device(self.handle, tab.handle, g(d_term_base), g(d_scalars32), g(d_offsets), n_msm, n_terms, max_terms,
+                                        g(d_out_affine96), g(d_out_comp48)))
+
     def ipa_prove_device(self, tab: "FixedTable", n: int, n_provers: int, g_index, g_prime_index, h_index, g_prime_coeffs32, cd48: bytes, z32: bytes,
                          vec_c32: bytes, vec_d32: bytes, vec_r_c32: bytes, vec_r_d32: bytes, states208: bytes, want_clocks: bool = False):
         """cg1_ipa_prove_device: n_provers inner-product arguments of length n over the table, one launch chain, one wait.
@@ -505,6 +551,21 @@ class Context:
         ck = (ctypes.c_uint32 * (4 * max(1, n_provers)))() if want_clocks else None
         self.check(cg1_ipa_prove_device(self.handle, tab.handle, n, n_provers, gi, gpi, hi, g_prime_coeffs32, cd48, z32, vec_c32, vec_d32, vec_r_c32, vec_r_d32,
                                         st, out, ck))
+        return (out.raw, st.raw, list(ck)) if want_clocks else (out.raw, st.raw)
+
+    def same_msm_prove_device(self, tab: "FixedTable", n: int, n_provers: int, g_index, azz48: bytes, tu_affine96: bytes, vec_x32: bytes, vec_r32: bytes,
+                              states208: bytes, want_clocks: bool = False):
+        """cg1_same_msm_prove_device: n_provers same-MSM arguments of length n, crs_G_vec from the table and vec_T | vec_U as affine96
+        records (a light table is built over them inside the call), one launch chain, one wait.
+        -> (proofs, states) as bytes [, clocks]; raises (check) on a refusal, and then nothing the caller holds has changed."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        assert len(g_index) == n * n_provers and len(azz48) == 144 * n_provers and len(tu_affine96) == 192 * n * n_provers
+        gi = (ctypes.c_uint32 * max(1, len(g_index)))(*g_index)
+        st = ctypes.create_string_buffer(bytes(states208), 208 * n_provers)
+        out = ctypes.create_string_buffer(max(1, int(cg1_same_msm_proof_bytes(n)) * n_provers))
+        ck = (ctypes.c_uint32 * (4 * max(1, n_provers)))() if want_clocks else None
+        self.check(cg1_same_msm_prove_device(self.handle, tab.handle, n, n_provers, gi, azz48, tu_affine96, vec_x32, vec_r32, st, out, ck))
         return (out.raw, st.raw, list(ck)) if want_clocks else (out.raw, st.raw)
 
     def last_counts(self) -> dict:
@@ -635,6 +696,37 @@ class FixedTable:
     def free(self) -> None:
         if self.handle:
             cg1_fixed_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class LightTable:
+    """A light table of variable bases on the device (cg1_light): for each base the 64 x 8 multiples d * 2^(4 w) * B as XYZZ records."""
+
+    def __init__(self, ctx: Context, bases_affine96: bytes, n_bases: int):
+        assert len(bases_affine96) >= 96 * n_bases
+        self.ctx, self.n = ctx, int(n_bases)
+        st = c_int(0)
+        self.handle = cg1_light_create(ctx.handle, bases_affine96, self.n, ctypes.byref(st))
+        if not self.handle:
+            msg = cg1_ctx_error(ctx.handle)
+            err = f"cg1_light_create({n_bases} bases) failed ({st.value}): {msg.decode() if msg else ''}"
+            if st.value in (ERR_ENCODING, ERR_NOT_ON_CURVE):
+                raise ValueError(err)
+            raise NativeError(err)
+
+    @property
+    def nbytes(self) -> int:
+        return int(cg1_light_bytes(self.handle)) if self.handle else 0
+
+    def free(self) -> None:
+        if self.handle:
+            cg1_light_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -1,0 +1,186 @@
+// C ABI, part 11: the same-MSM argument proved on the device (kernels_same_msm.h over a cg1_fixed table for crs_G_vec and a light table,
+// built inside the call, for the provers' vec_T | vec_U).
+// Part of the single translation unit csrc/msm_gpu.hip (included there; not a stand-alone header).
+#pragma once
+
+namespace {
+struct SmsmLayout {                          // byte offsets into the staging block (pinned host memory and its device twin: the same layout)
+  size_t gi, vx, vr, tu96, offs_a1, offs_a2, offs_l2, offs_l4;        // uploaded
+  size_t status, clocks, states, proof;                               // uploaded (zeros | zeros | the states after the host's two lists | --) and read back
+  size_t x, k, row, chal, pts_a, pts_tu, tba, sca, tbl, scl;          // device only
+  size_t up_end, down_begin, down_end, total;
+};
+SmsmLayout smsm_layout(size_t n, size_t P, size_t proof_bytes) {
+  SmsmLayout L{};
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
+  L.gi = take(P * n * 4); L.vx = take(P * n * 32); L.vr = take(P * n * 32); L.tu96 = take(P * 2 * n * 96);
+  L.offs_a1 = take((P + 1) * 4); L.offs_a2 = take((2 * P + 1) * 4); L.offs_l2 = take((2 * P + 1) * 4); L.offs_l4 = take((4 * P + 1) * 4);
+  L.down_begin = o;
+  L.status = take(16); L.clocks = take(P * 16); L.states = take(P * 208);
+  L.up_end = o;
+  L.proof = take(P * proof_bytes);
+  L.down_end = o;
+  L.x = take(P * n * 32); L.k = take(P * n * 32); L.row = take(P * cg1smsm::SMSM_ROW); L.chal = take(P * 32);
+  L.pts_a = take(P * 2 * 48); L.pts_tu = take(P * 4 * 48);
+  L.tba = take(P * n * 4); L.sca = take(P * n * 32); L.tbl = take(P * 2 * n * 4); L.scl = take(P * 2 * n * 32);
+  L.total = o;
+  return L;
+}
+}  // namespace
+
+extern "C" {
+size_t cg1_same_msm_proof_bytes(size_t n) {
+  if (n < 2 || (n & (n - 1)) != 0) return 0;
+  size_t lg = 0;
+  while (((size_t)1 << lg) < n) ++lg;
+  return (3 + 6 * lg) * 48 + 32;
+}
+
+int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_provers, const uint32_t* g_index, const uint8_t* azz48,
+                              const uint8_t* tu_affine96, const uint8_t* vec_x32, const uint8_t* vec_r32, uint8_t* states208, uint8_t* out_proofs,
+                              uint32_t* out_clocks) {
+  static const char* const who = "cg1_same_msm_prove_device";
+  if (!ctx) return CG1_ERR_HIP;
+  if (n_provers == 0) return CG1_OK;
+  // ---- refusals: the whole call, before anything is written
+  if (!t || t->device != ctx->device || !g_index || !azz48 || !tu_affine96 || !vec_x32 || !vec_r32 || !states208 || !out_proofs) {
+    snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
+  if (n < 2 || (n & (n - 1)) != 0 || n > CG1_SAME_MSM_MAX_N) {
+    snprintf(ctx->err, sizeof ctx->err, "%s: n must be a power of two in 2 .. %d", who, CG1_SAME_MSM_MAX_N); return CG1_ERR_ARG; }
+  if (n_provers > CG1_SAME_MSM_MAX_PROVERS || n_provers * 2 * n > CG1_LIGHT_MAX_BASES) {
+    snprintf(ctx->err, sizeof ctx->err, "%s: more than %d provers, or more than %d bases T | U, in one call", who, CG1_SAME_MSM_MAX_PROVERS, CG1_LIGHT_MAX_BASES);
+    return CG1_ERR_ARG; }
+  const size_t P = n_provers;
+  for (size_t i = 0; i < P * n; ++i)
+    if (g_index[i] >= t->n_bases) { snprintf(ctx->err, sizeof ctx->err, "%s: a base index is outside the table", who); return CG1_ERR_ARG; }
+  if (!ipa_scalars_canonical(vec_x32, P * n) || !ipa_scalars_canonical(vec_r32, P * n)) {
+    snprintf(ctx->err, sizeof ctx->err, "%s: a scalar is >= r: scalar32 must be a canonical Fr element", who); return CG1_ERR_ENCODING; }
+  std::vector<uint8_t> head(P * 144), blobs(P * 2 * n * CG1_POINT_BYTES), tu48(P * 2 * n * 48);
+  for (size_t i = 0; i < 3 * P; ++i) {                      // A, Z_t, Z_u: only hashed, as re-serialised (util.py:27-32)
+    int inf = 0;
+    const int rc = cg1_validate_compressed(azz48 + 48 * i, &inf);
+    if (rc != CG1_OK) { snprintf(ctx->err, sizeof ctx->err, "%s: prover %zu: %s does not decode (status %d)", who, i / 3, i % 3 == 0 ? "A" : i % 3 == 1 ? "Z_t" : "Z_u", rc); return rc; }
+    memcpy(&head[48 * i], azz48 + 48 * i, 48);
+    if (inf) { memset(&head[48 * i], 0, 48); head[48 * i] = 0xC0; }
+  }
+  for (size_t b = 0; b < P * 2 * n; ++b) {                  // canonical coordinates, on the curve (or the all-zero identity record)
+    const int rc = cg1_from_affine96(&blobs[b * CG1_POINT_BYTES], tu_affine96 + 96 * b, 1);
+    if (rc != CG1_OK) { snprintf(ctx->err, sizeof ctx->err, "%s: prover %zu: entry %zu of vec_T | vec_U is not a curve point (status %d)", who, b / (2 * n), b % (2 * n), rc); return rc; }
+  }
+  cg1_batch_compress(tu48.data(), blobs.data(), P * 2 * n);
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->pend.active = false;
+  size_t lg = 0;
+  while (((size_t)1 << lg) < n) ++lg;
+  const size_t pb = cg1_same_msm_proof_bytes(n);
+  const SmsmLayout L = smsm_layout(n, P, pb);
+  if (L.total > t->cap_smsm) {
+    if (t->h_smsm) (void)hipHostFree(t->h_smsm);
+    if (t->d_smsm) (void)hipFree(t->d_smsm);
+    t->h_smsm = nullptr; t->d_smsm = nullptr; t->cap_smsm = 0;
+    HIPCHK(hipHostMalloc((void**)&t->h_smsm, L.total, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&t->d_smsm, L.total));
+    t->cap_smsm = L.total;
+  }
+  if (P * 2 * n > t->cap_smsm_bases) {                      // the light table's records: kept with the handle, regrown only when too small
+    if (t->smsm_light) cg1_light_destroy(t->smsm_light);
+    t->smsm_light = new cg1_light();
+    t->smsm_light->device = ctx->device;
+    t->cap_smsm_bases = 0;
+    { const int rc = light_alloc(ctx, t->smsm_light, P * 2 * n); if (rc) { cg1_light_destroy(t->smsm_light); t->smsm_light = nullptr; return rc; } }
+    t->cap_smsm_bases = P * 2 * n;
+  }
+  cg1_light* lt = t->smsm_light;
+  lt->n_bases = P * 2 * n;
+  // ---- stage the inputs: one block, one copy.  The first two same_msm_step1 lists ([A, Z_t, Z_u] and vec_T + vec_U, 2 n encodings:
+  // ~74 Keccak permutations at n = 128) depend on nothing the device computes: absorbed here, into the states that go up.
+  uint8_t* H = t->h_smsm;
+  uint8_t* D = t->d_smsm;
+  memcpy(H + L.gi, g_index, P * n * 4);
+  memcpy(H + L.vx, vec_x32, P * n * 32); memcpy(H + L.vr, vec_r32, P * n * 32);
+  memcpy(H + L.tu96, tu_affine96, P * 2 * n * 96);
+  const uint32_t nn = (uint32_t)n, Pn = (uint32_t)P, hh = nn / 2;
+  uint32_t* oa1 = reinterpret_cast<uint32_t*>(H + L.offs_a1);
+  uint32_t* oa2 = reinterpret_cast<uint32_t*>(H + L.offs_a2);
+  uint32_t* ol2 = reinterpret_cast<uint32_t*>(H + L.offs_l2);
+  uint32_t* ol4 = reinterpret_cast<uint32_t*>(H + L.offs_l4);
+  for (uint32_t i = 0; i <= Pn; ++i) oa1[i] = i * nn;
+  for (uint32_t i = 0; i <= 2 * Pn; ++i) { oa2[i] = i * hh; ol2[i] = i * nn; }
+  for (uint32_t i = 0; i <= 4 * Pn; ++i) ol4[i] = i * hh;
+  memset(H + L.status, 0, 16); memset(H + L.clocks, 0, P * 16);
+  memcpy(H + L.states, states208, P * 208);
+  static const uint8_t step1[] = "same_msm_step1";
+  for (size_t p = 0; p < P; ++p) {
+    cg1_merlin_append_list(H + L.states + 208 * p, step1, 14, &head[144 * p], 48, 3);
+    cg1_merlin_append_list(H + L.states + 208 * p, step1, 14, &tu48[p * 2 * n * 48], 48, 2 * n);
+  }
+  HIPCHK(hipMemcpyAsync(D, H, L.up_end, hipMemcpyHostToDevice, ctx->stream));
+
+  cg1smsm::SmsmArgs a;
+  a.n0 = nn; a.lg = (uint32_t)lg;
+  a.gi = (const uint32_t*)(D + L.gi); a.vx = (const uint64_t*)(D + L.vx); a.vr = (const uint64_t*)(D + L.vr);
+  a.x = (cg1fr::fr*)(D + L.x); a.k = (cg1fr::fr*)(D + L.k);
+  a.states = D + L.states; a.row = D + L.row; a.chal = D + L.chal;
+  a.pts_a = (const uint32_t*)(D + L.pts_a); a.pts_tu = (const uint32_t*)(D + L.pts_tu);
+  a.proof = (uint32_t*)(D + L.proof); a.proof_words = (uint32_t)(pb / 4);
+  a.tba = (uint32_t*)(D + L.tba); a.sca = (uint64_t*)(D + L.sca); a.tbl = (uint32_t*)(D + L.tbl); a.scl = (uint64_t*)(D + L.scl);
+  a.status_a = t->d_status; a.status_tu = lt->d_status; a.chain_status = (uint32_t*)(D + L.status); a.clocks = (uint32_t*)(D + L.clocks);
+
+  // ---- the slice sums of the chain's largest launches (step B: n terms per MSM), reserved BEFORE the first launch: fixed_enqueue /
+  // light_enqueue would otherwise free and allocate in mid-chain, which waits for the device
+  auto shapes = [&](uint32_t per_a, uint32_t mt, FixedShape& sa, FixedShape& sl) {
+    const uint32_t Ma = per_a * Pn, Ml = 2 * per_a * Pn;
+    sa = fixed_pick_shape(ctx, [&](uint32_t s) { return (size_t)Ma * std::max<uint32_t>(1u, (mt + s - 1) / s); }, Ma, mt);
+    sl = light_pick_shape(ctx, [&](uint32_t s) { return (size_t)Ml * std::max<uint32_t>(1u, (mt + s - 1) / s); }, Ml, mt);
+  };
+  {
+    size_t need_a = 0, need_l = 0;
+    for (uint32_t per_a = 1; per_a <= 2; ++per_a) {
+      const uint32_t mt = per_a == 1 ? nn : hh;
+      FixedShape sa, sl;
+      shapes(per_a, mt, sa, sl);
+      const size_t Sa = (mt + sa.slice - 1) / sa.slice, Sl = (mt + sl.slice - 1) / sl.slice;
+      if (Sa > 1) need_a = std::max(need_a, (size_t)per_a * Pn * Sa);
+      if (Sl > 1) need_l = std::max(need_l, (size_t)2 * per_a * Pn * Sl);
+    }
+    if (need_a > t->cap_partial) {
+      if (t->d_partial) (void)hipFree(t->d_partial);
+      t->d_partial = nullptr; t->cap_partial = 0;
+      HIPCHK(hipMalloc(&t->d_partial, need_a * sizeof(cg1::PointSum)));
+      t->cap_partial = need_a;
+    }
+    if (need_l > lt->cap_partial) {
+      if (lt->d_partial) (void)hipFree(lt->d_partial);
+      lt->d_partial = nullptr; lt->cap_partial = 0;
+      HIPCHK(hipMalloc(&lt->d_partial, need_l * sizeof(cg1::PointSum)));
+      lt->cap_partial = need_l;
+    }
+  }
+
+  // ---- the chain: begin, build | MSMs finish stepB | (MSMs finish round) x lg n -- plain launches on the context's stream, no host wait between
+  hipLaunchKernelGGL(cg1smsm::k_smsm_step, dim3(Pn), dim3(cg1smsm::SMSM_THREADS), 0, ctx->stream, a, cg1smsm::SMSM_BEGIN, nn, 0u);
+  light_build(ctx, D + L.tu96, P * 2 * n, lt->d_tab);
+  auto msms = [&](uint32_t per_a, uint32_t mt, const uint32_t* d_oa, const uint32_t* d_ol) -> int {
+    const uint32_t Ma = per_a * Pn, Ml = 2 * per_a * Pn;
+    FixedShape sa, sl;
+    shapes(per_a, mt, sa, sl);
+    { const int rc = fixed_enqueue(ctx, t, a.tba, (const uint32_t*)a.sca, d_oa, Ma, Pn * nn, mt, sa, false, nullptr, D + L.pts_a); if (rc) return rc; }
+    return light_enqueue(ctx, lt, a.tbl, (const uint32_t*)a.scl, d_ol, Ml, Pn * 2 * nn, mt, sl, false, nullptr, D + L.pts_tu);
+  };
+  { const int rc = msms(1, nn, (const uint32_t*)(D + L.offs_a1), (const uint32_t*)(D + L.offs_l2)); if (rc) return rc; }
+  hipLaunchKernelGGL(cg1smsm::k_smsm_step, dim3(Pn), dim3(cg1smsm::SMSM_THREADS), 0, ctx->stream, a, cg1smsm::SMSM_STEPB, nn, 0u);
+  for (uint32_t r = 0; r < (uint32_t)lg; ++r) {
+    { const int rc = msms(2, hh, (const uint32_t*)(D + L.offs_a2), (const uint32_t*)(D + L.offs_l4)); if (rc) return rc; }
+    hipLaunchKernelGGL(cg1smsm::k_smsm_step, dim3(Pn), dim3(cg1smsm::SMSM_THREADS), 0, ctx->stream, a, cg1smsm::SMSM_ROUND, nn >> r, r);
+  }
+  HIPCHK(hipMemcpyAsync(H + L.down_begin, D + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));                 // the one wait
+  HIPCHK(hipGetLastError());
+  { const int rc = fixed_status_error(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
+  memcpy(out_proofs, H + L.proof, P * pb);
+  memcpy(states208, H + L.states, P * 208);
+  if (out_clocks) memcpy(out_clocks, H + L.clocks, P * 16);
+  return CG1_OK;
+}
+}  // extern "C"

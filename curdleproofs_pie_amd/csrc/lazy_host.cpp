@@ -3,6 +3,7 @@
 #include "bls_consts.h"
 #include "pool.h"
 #include "ipa_rounds.h"
+#include "same_msm_rounds.h"
 #include "../../include/curdle_g1.h"
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 namespace cg1 {
 #include "glv.h"
 #include "fixed_digits.h"
+#include "light_digits.h"
 }
 
 namespace cg1h {
@@ -448,6 +450,16 @@ void cg1_fixed_digits(const uint8_t* scalar32, int16_t* out32) {
   (void)cg1::fixed_digits(k, out32, 1);
 }
 
+// The signed narrow-window recoding of the light tables (csrc/light_digits.h: the function k_light_msm runs), one scalar: for the CPU tests.
+int cg1_light_digits(const uint8_t* scalar32, int16_t* out) {
+  uint32_t k[8];
+  memcpy(k, scalar32, 32);
+  int8_t d[cg1::LT_WINDOWS];
+  (void)cg1::light_digits(k, d, 1);
+  for (int w = 0; w < cg1::LT_WINDOWS; ++w) out[w] = d[w];
+  return cg1::LT_WINDOWS;
+}
+
 // The scalar schedule and the folds of the device prover of the inner-product argument (csrc/ipa_rounds.h: the functions k_ipa_step
 // runs, one lane per term there, a loop here): for the CPU tests.
 int cg1_ipa_round_emulate(int op, size_t n0, size_t len, uint8_t* c32, uint8_t* d32, uint8_t* kg32, uint8_t* kgp32, const uint8_t* kh32,
@@ -502,6 +514,66 @@ int cg1_ipa_round_emulate(int op, size_t n0, size_t len, uint8_t* c32, uint8_t* 
   }
   for (size_t i = 0; i < len; ++i) { cg1fr::fr_to_le32(c[i], c32 + 32 * i); cg1fr::fr_to_le32(d[i], d32 + 32 * i); }
   for (size_t i = 0; i < n0; ++i) { cg1fr::fr_to_le32(kg[i], kg32 + 32 * i); cg1fr::fr_to_le32(kgp[i], kgp32 + 32 * i); }
+  return CG1_OK;
+}
+
+// The scalar schedule and the fold of the device prover of the same-MSM argument (csrc/same_msm_rounds.h: the functions k_smsm_step
+// runs, one lane per term there, a loop here): for the CPU tests.  The two term arrays of a launch come back as ONE, in the
+// transcript's order.
+int cg1_same_msm_round_emulate(int op, size_t n0, size_t len, uint8_t* x32, uint8_t* k32, const uint8_t* challenge32, const uint8_t* r32,
+                               const uint32_t* g_index, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets) {
+  using cg1fr::fr;
+  auto pow2 = [](size_t v) { return v >= 2 && (v & (v - 1)) == 0; };
+  if (op < 0 || op > 2 || !pow2(n0) || n0 > CG1_SAME_MSM_MAX_N || !pow2(len) || len > n0 || (op != 2 && len != n0) || !x32 || !k32) return CG1_ERR_ARG;
+  if (op != 2 && !r32) return CG1_ERR_ARG;
+  if (op == 1 && !challenge32) return CG1_ERR_ARG;
+  if (op != 1 && (!g_index || !out_term_base || !out_term_scalars32 || !out_offsets)) return CG1_ERR_ARG;
+  bool ok = true;
+  auto load = [&](const uint8_t* src, size_t count) {
+    std::vector<fr> v(count);
+    for (size_t i = 0; i < count; ++i) ok = cg1fr::fr_from_le32(src + 32 * i, v[i]) && ok;
+    return v;
+  };
+  std::vector<fr> x = load(x32, len), k = load(k32, n0);
+  std::vector<fr> ch = challenge32 ? load(challenge32, 1) : std::vector<fr>(), r = op != 2 ? load(r32, n0) : std::vector<fr>();
+  if (!ok) return CG1_ERR_ENCODING;
+  cg1smsm::View v{x.data(), k.data(), g_index, 0u, (uint32_t)n0};
+  const uint32_t n = (uint32_t)n0, h = n / 2;
+  std::vector<uint32_t> tba(n), tbl(2 * n);
+  std::vector<uint64_t> sca(4 * (size_t)n), scl(8 * (size_t)n);
+  // one array in the transcript's order: `lists` MSMs of `each` terms, list q from the A array (q % 3 == 0) or the T | U array
+  auto merge = [&](uint32_t lists, uint32_t each) {
+    for (uint32_t q = 0; q < lists; ++q) {
+      const uint32_t g = q / 3, m = q % 3;
+      const uint32_t* tb = m == 0 ? tba.data() + g * each : tbl.data() + (2 * g + m - 1) * each;
+      const uint64_t* sc = m == 0 ? sca.data() + 4 * (size_t)g * each : scl.data() + 4 * (size_t)(2 * g + m - 1) * each;
+      memcpy(out_term_base + (size_t)q * each, tb, 4 * (size_t)each);
+      memcpy(out_term_scalars32 + 32 * (size_t)q * each, sc, 32 * (size_t)each);
+      out_offsets[q] = q * each;
+    }
+    out_offsets[lists] = lists * each;
+  };
+  if (op == 0) {
+    for (uint32_t j = 0; j < n; ++j) cg1smsm::begin_term(v, j, r[j], tba.data(), sca.data(), tbl.data(), scl.data());
+    merge(3, n);
+    return CG1_OK;
+  }
+  if (op == 1) {
+    for (uint32_t j = 0; j < n; ++j) cg1smsm::blind_elem(v, j, ch[0], r[j]);
+  } else {
+    const uint32_t half = (uint32_t)len / 2;
+    for (uint32_t t = 0; t < h; ++t) cg1smsm::round_term(v, half, t, tba.data(), sca.data(), tbl.data(), scl.data());
+    merge(6, h);
+    if (challenge32) {
+      if (cg1fr::fr_is_zero(ch[0])) return CG1_ERR_ARG;
+      const fr ginv = cg1ipa::fr_inv_binary(ch[0]);
+      if (!cg1fr::fr_eq(ginv, cg1fr::fr_inv(ch[0]))) return CG1_ERR_ARG;          // the two inversions agree, or the test hears of it
+      for (uint32_t t = 0; t < h; ++t) cg1smsm::fold_elem(v, half, t, ch[0], ginv);
+      len = half;
+    }
+  }
+  for (size_t i = 0; i < len; ++i) cg1fr::fr_to_le32(x[i], x32 + 32 * i);
+  for (size_t i = 0; i < n0; ++i) cg1fr::fr_to_le32(k[i], k32 + 32 * i);
   return CG1_OK;
 }
 

@@ -65,12 +65,15 @@ int pick_window(size_t n);
 #include "kernels_generator.h"
 #include "fixed_digits.h"
 #include "kernels_fixed.h"
+#include "light_digits.h"
+#include "kernels_light.h"
 }  // namespace cg1
 #include "kernels_rows.h"
 #include "kernels_merlin.h"
 #include "kernels_frontend.h"
 #include "kernels_opening.h"
 #include "kernels_ipa.h"           // k_ipa_step: the Fr and transcript half of the inner-product argument's prover
+#include "kernels_same_msm.h"      // k_smsm_step: the Fr and transcript half of the same-MSM argument's prover
 #include "host_context.h"          // Ctx: streams, helper threads, scratch buffers
 #include "host_chains.h"           // planner + launch chains: regime A, k_msm_small, regime B
 #include "capi_core_msm.h"         // cg1_* : host operators, context, memory, parameters, MSM entry points
@@ -82,3 +85,5 @@ int pick_window(size_t n);
 #include "capi_rows_probes.h"      // scalar rows, compression, synthetic scalars, probes
 #include "capi_fixed.h"            // resident fixed-base tables: cg1_fixed_*
 #include "capi_ipa.h"              // the inner-product argument proved on the device: cg1_ipa_prove_device
+#include "capi_light.h"            // light tables of variable bases: cg1_light_*
+#include "capi_same_msm.h"         // the same-MSM argument proved on the device: cg1_same_msm_prove_device

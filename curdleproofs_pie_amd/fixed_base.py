@@ -12,6 +12,10 @@ and folds the challenges into the scalars), yet `compute_MSM` pays a full Pippen
 A table holds the 32 x 128 multiples d * 2^(8 w) * B of every base (512 KiB each: 66.5 MiB for the 133 points of an ell = 124 CRS); a term
 is then at most 32 additions and the sum is finished on the device.  There is no CPU path: without a GPU the constructor raises
 `NativeError`, like every MSM of this package.
+
+    lt = LightTable(points)                 # the same surface over a LIGHT table (csrc/kernels_light.h): for points that live for one
+                                            # proof (vec_T, vec_U).  Built on the device in the constructor, 128 KiB per base, a term
+                                            # is at most 64 additions
 """
 from __future__ import annotations
 
@@ -34,15 +38,19 @@ class FixedBaseTable:
     """A table of fixed bases on the default context's GPU.  Thread-safe; freed at close(), at garbage collection and before
     N.close_default_context()."""
 
+    _KIND, _MAX_BASES, _MAX_MSMS, _MAX_TERMS = "fixed-base", N.FIXED_MAX_BASES, N.FIXED_MAX_MSMS, N.FIXED_MAX_TERMS
+    _create = staticmethod(lambda ctx, raw, n: ctx.fixed_table(raw, n))
+    _native_msm = staticmethod(N.cg1_fixed_msm)
+
     def __init__(self, points: Iterable[G1Point]):
         with _LOCK:
             ctx = N.default_context()    # no GPU: NativeError here -- there is no CPU fallback for an MSM
             pts = list(points)
-            if not 1 <= len(pts) <= N.FIXED_MAX_BASES:
-                raise ValueError(f"a fixed-base table holds 1 .. {N.FIXED_MAX_BASES} points, not {len(pts)}")
+            if not 1 <= len(pts) <= self._MAX_BASES:
+                raise ValueError(f"a {self._KIND} table holds 1 .. {self._MAX_BASES} points, not {len(pts)}")
             for p in pts:
                 if type(p) is not G1Point:
-                    raise TypeError("FixedBaseTable takes G1Point objects")
+                    raise TypeError(f"{type(self).__name__} takes G1Point objects")
             raw = points_to_affine96(pts)                     # forces deferred values, one shared inversion
             self._points = tuple(pts)                         # held: the identities below stay valid
             self._pos = {}
@@ -51,7 +59,7 @@ class FixedBaseTable:
             self._sg = [p._sg is True for p in pts]           # certified in G1? (unknown counts as no)
             self._all = array("I", range(len(pts)))
             self._ctx = ctx
-            self._tab = ctx.fixed_table(raw, len(pts))
+            self._tab = self._create(ctx, raw, len(pts))
             _tables.add(self)
 
     @classmethod
@@ -89,7 +97,7 @@ class FixedBaseTable:
     def _ctx_lock(self):
         """The lock every call on this table's context runs under; raises when the table is closed."""
         if self._tab is None or not self._tab.handle or not self._ctx.handle:
-            raise N.NativeError("the fixed-base table is closed")
+            raise N.NativeError(f"the {self._KIND} table is closed")
         return _LOCK
 
     def _indices(self, bases: Sequence[Base], n: int):
@@ -114,11 +122,11 @@ class FixedBaseTable:
         return self.msm_many([(bases, scalars)])[0]
 
     def msm_many(self, jobs: Iterable[Tuple[Sequence[Base], Sequence[Scalar]]]) -> List[G1Point]:
-        """[sum_i scalars[i] * bases[i] for (bases, scalars) in jobs] as ONE launch chain (k_fixed_msm).  bases: G1Point objects of the
+        """[sum_i scalars[i] * bases[i] for (bases, scalars) in jobs] as ONE launch chain (k_fixed_msm; k_light_msm for a LightTable).  bases: G1Point objects of the
         table or indices into it, None = the table in order.  A result is certified in G1 only when every base it used was."""
         with _LOCK:
             if self._tab is None or not self._tab.handle or not self._ctx.handle:
-                raise N.NativeError("the fixed-base table is closed")
+                raise N.NativeError(f"the {self._KIND} table is closed")
             idx = array("I")
             offsets = array("I", [0])
             all_sc: list = []
@@ -135,8 +143,8 @@ class FixedBaseTable:
                         bases = list(bases)
                     n = min(len(scalars), len(bases))
                     part = self._indices(bases, n)
-                if n > N.FIXED_MAX_TERMS:
-                    raise ValueError(f"an MSM over a fixed-base table takes at most {N.FIXED_MAX_TERMS} terms")
+                if n > self._MAX_TERMS:
+                    raise ValueError(f"an MSM over a {self._KIND} table takes at most {self._MAX_TERMS} terms")
                 idx.extend(part)
                 all_sc.extend(scalars if len(scalars) == n else scalars[:n])
                 offsets.append(len(idx))
@@ -145,8 +153,8 @@ class FixedBaseTable:
             if m == 0:
                 return []
             out: List[G1Point] = []
-            for lo in range(0, m, N.FIXED_MAX_MSMS):          # (more MSMs than one launch carries: several calls)
-                hi = min(m, lo + N.FIXED_MAX_MSMS)
+            for lo in range(0, m, self._MAX_MSMS):            # (more MSMs than one launch carries: several calls)
+                hi = min(m, lo + self._MAX_MSMS)
                 t0, t1 = offsets[lo], offsets[hi]
                 nt = t1 - t0
                 scb = ctypes.create_string_buffer(32 * max(nt, 1))
@@ -156,13 +164,27 @@ class FixedBaseTable:
                 blobs = ctypes.create_string_buffer(N.POINT_BYTES * (hi - lo))
                 ia, _ = part_idx.buffer_info()
                 oa, _ = offs.buffer_info()
-                self._ctx.check(N.cg1_fixed_msm(self._ctx.handle, self._tab.handle, ia if nt else None, ctypes.addressof(scb), oa, hi - lo,
+                self._ctx.check(self._native_msm(self._ctx.handle, self._tab.handle, ia if nt else None, ctypes.addressof(scb), oa, hi - lo,
                                                 ctypes.addressof(blobs), None))
                 out.extend(points_from_blobs(blobs, hi - lo))
             for p, ok in zip(out, certified):
                 if ok and p._sg is not True:
                     B._set(p, "_sg", True)
             return out
+
+
+class LightTable(FixedBaseTable):
+    """A LIGHT table (csrc/kernels_light.h) over points that live for one proof -- vec_T, vec_U -- with FixedBaseTable's whole surface
+    (msm, msm_many, index, close, _indices, _ctx_lock): the two are interchangeable for callers.  Built on the device inside the
+    constructor (two launches, 128 KiB per base instead of 512), a term costs up to 64 additions instead of 32."""
+
+    _KIND, _MAX_BASES, _MAX_MSMS, _MAX_TERMS = "light", N.LIGHT_MAX_BASES, N.LIGHT_MAX_MSMS, N.LIGHT_MAX_TERMS
+    _create = staticmethod(lambda ctx, raw, n: ctx.light_table(raw, n))
+    _native_msm = staticmethod(N.cg1_light_msm)
+
+    @classmethod
+    def for_crs(cls, crs):
+        raise TypeError("the CRS lives as long as the process: FixedBaseTable.for_crs(crs)")
 
 
 def _close_all() -> None:

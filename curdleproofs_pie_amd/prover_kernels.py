@@ -145,6 +145,8 @@ def ipa_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence
     enc = iter(points_to_compressed(pts))
     out: List[tuple] = []
     with table._ctx_lock():
+        if table._KIND != "fixed-base":                                  # a LightTable: its records are not what k_fixed_msm reads
+            raise TypeError("the device chain of the inner-product argument runs over a FixedBaseTable")
         for lo in range(0, len(provers), N.IPA_MAX_PROVERS):             # (more provers than one chain carries: several calls)
             part, P = provers[lo: lo + N.IPA_MAX_PROVERS], len(provers[lo: lo + N.IPA_MAX_PROVERS])
             gi, gpi, hi, cd, flat = [], [], [], [], [[] for _ in range(6)]
@@ -227,6 +229,76 @@ def same_msm_rounds(crs_G_vec: Sequence[G1Point], vec_T: Sequence[G1Point], vec_
                     next_gamma: Callable[[G1Point, G1Point, G1Point, G1Point, G1Point, G1Point], Scalar]):
     """same_msm.py:93-130 (vec_x already blinded, :89-91).  -> (vec_L_A, vec_L_T, vec_L_U, vec_R_A, vec_R_T, vec_R_U, x_final)."""
     return same_msm_rounds_many([(crs_G_vec, vec_T, vec_U, vec_x)], [next_gamma])[0]
+
+
+def same_msm_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence) -> List[tuple]:
+    """SameMSMProof.new (same_msm.py:50-143) after its `generate_blinders(n)` draw, for SEVERAL independent provers of one length in step,
+    proved ON THE DEVICE: one launch chain (csrc/kernels_same_msm.h), one wait.  crs_G_vec comes from the resident `table` (a
+    fixed_base.FixedBaseTable); vec_T and vec_U are per-proof points, over which the call builds one light table on the device.
+    provers[p] = (crs_G_vec, A, Z_t, Z_u, vec_T, vec_U, vec_x, vec_r): crs_G_vec as objects of the table or indices into it (KeyError /
+    IndexError); A, Z_t, Z_u are G1Points or their 48-byte encodings (only hashed); vec_T / vec_U are G1Points (deferred ones are
+    materialised in one batch; any curve point, the identity included); vec_x UNBLINDED and not mutated (the call blinds a copy with the
+    alpha it draws), vec_r the caller's own blinders.
+    transcripts[p]: that prover's CurdleproofsTranscript, advanced to the state after the last same_msm_gamma.
+    -> per prover (B_a, B_t, B_u, vec_L_A, vec_L_T, vec_L_U, vec_R_A, vec_R_T, vec_R_U, x_final), the fields of SameMSMProof.
+    A refused call (ValueError: n not a power of two >= 2; NativeError: a scalar >= r, an undecodable A, Z_t or Z_u) changes nothing."""
+    import ctypes
+
+    from . import _native as N
+    from .py_arkworks_bls12381 import pack_scalars, points_to_affine96, points_to_compressed
+
+    provers = [tuple(pr) for pr in provers]
+    if len(provers) != len(transcripts):
+        raise ValueError("one transcript per prover")
+    if not provers:
+        return []
+    n = len(provers[0][6])
+    if n < 2 or n & (n - 1) or n > N.SAME_MSM_MAX_N:
+        raise ValueError(f"the vectors of a same-MSM argument have a power-of-two length in 2 .. {N.SAME_MSM_MAX_N}, not {n}")
+    if any(not (len(pr[0]) == len(pr[4]) == len(pr[5]) == len(pr[6]) == len(pr[7]) == n) for pr in provers):
+        raise ValueError("provers in step share one vector length")
+    if any(type(x) is not G1Point for pr in provers for x in list(pr[4]) + list(pr[5])):
+        raise TypeError("vec_T and vec_U are G1Points")
+    enc = iter(points_to_compressed([x for pr in provers for x in pr[1:4] if type(x) is G1Point]))
+    step = min(N.SAME_MSM_MAX_PROVERS, N.LIGHT_MAX_BASES // (2 * n))     # (more provers than one chain carries: several calls)
+    out: List[tuple] = []
+    with table._ctx_lock():
+        if table._KIND != "fixed-base":
+            raise TypeError("the device chain of the same-MSM argument takes crs_G_vec from a FixedBaseTable")
+        for lo in range(0, len(provers), step):
+            part = provers[lo: lo + step]
+            P = len(part)
+            gi, azz, tu, xs, rs = [], [], [], [], []
+            for pr in part:
+                gi.extend(table._indices(pr[0], n))
+                azz.extend(bytes(x) if type(x) is not G1Point else next(enc) for x in pr[1:4])
+                if any(len(e) != 48 for e in azz[-3:]):
+                    raise ValueError("A, Z_t and Z_u are G1Points or 48-byte encodings")
+                tu.extend(pr[4]); tu.extend(pr[5])
+                xs.extend(pr[6]); rs.extend(pr[7])
+            bufs = []
+            for vals in (xs, rs):
+                b = ctypes.create_string_buffer(32 * len(vals))
+                pack_scalars(vals, ctypes.addressof(b), len(vals))
+                bufs.append(b)
+            states = b"".join(bytes(t.strobe._st.raw[:N.MERLIN_STATE_BYTES]) for t in transcripts[lo: lo + P])
+            proofs, new_states = table._ctx.same_msm_prove_device(table._tab, n, P, gi, b"".join(azz), bytes(points_to_affine96(tu)), bufs[0], bufs[1], states)
+            lg, pb, S = n.bit_length() - 1, len(proofs) // P, N.MERLIN_STATE_BYTES
+            for i, t in enumerate(transcripts[lo: lo + P]):
+                ctypes.memmove(t.strobe._st, new_states[S * i: S * i + S], S)
+                raw = proofs[pb * i: pb * i + pb]
+                P48 = [G1Point.from_compressed_bytes_unchecked(raw[48 * j: 48 * j + 48]) for j in range(3 + 6 * lg)]
+                vecs = [P48[3 + q * lg: 3 + (q + 1) * lg] for q in range(6)]
+                out.append((P48[0], P48[1], P48[2], *vecs, Scalar.from_le_bytes(raw[pb - 32:])))
+    return out
+
+
+def same_msm_prove_device(table, crs_G_vec, A, Z_t, Z_u, vec_T: Sequence[G1Point], vec_U: Sequence[G1Point], vec_x: Sequence[Scalar],
+                          vec_r: Sequence[Scalar], transcript):
+    """SameMSMProof.new (same_msm.py:50-143) after `vec_r = generate_blinders(n)`, on the device: see same_msm_prove_device_many.
+    `transcript` is advanced as the reference advances it; vec_x is not mutated.
+    -> (B_a, B_t, B_u, vec_L_A, vec_L_T, vec_L_U, vec_R_A, vec_R_T, vec_R_U, x_final)."""
+    return same_msm_prove_device_many(table, [(crs_G_vec, A, Z_t, Z_u, vec_T, vec_U, vec_x, vec_r)], [transcript])[0]
 
 
 def shuffle_permute_and_commit_input(crs, vec_R: Sequence[G1Point], vec_S: Sequence[G1Point], permutation: Sequence[int], k: Scalar,

@@ -591,6 +591,87 @@ int cg1_ipa_round_emulate(int op, size_t n0, size_t len, uint8_t* c32, uint8_t* 
                           const uint8_t* challenge32 /* nullable for op 2 */, const uint8_t* r_c32, const uint8_t* r_d32, const uint32_t* g_index,
                           const uint32_t* g_prime_index, uint32_t h_index, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets);
 
+/* ---- LIGHT tables: window multiples of VARIABLE bases, built on the device inside the call, and MSMs over them without a doubling
+ * (csrc/kernels_light.h).  For bases that live for one proof and enter several MSMs each -- vec_T / vec_U of the same-MSM argument -- a
+ * cg1_fixed table (512 KiB, ~0.35 ms per base) is unaffordable.  A light table uses signed windows of CG1_LIGHT_WINDOW_BITS = 4 bits:
+ * per base 64 windows x 8 multiples d * 2^(4 w) * B as 256-byte XYZZ records (no inversion in the build), 128 KiB; a term k * B is then
+ * at most 64 additions.  Built by two launches: one wave per base walks the 252 doublings, then one wave per (base, window) fills the
+ * multiples; every addition is complete and every record carries its own identity flag, so the table is exact for ANY curve point.
+ *   cg1_light_create   n_bases = 1 .. CG1_LIGHT_MAX_BASES; the coordinate and on-curve errors, the all-zero identity record and the
+ *                      device rules of cg1_fixed_create.
+ *   cg1_light_msm, cg1_light_msm_device   the arguments, outputs, limits and refusals of cg1_fixed_msm / cg1_fixed_msm_device (bit 31
+ *                      of an index = the negated base; a scalar >= r: CG1_ERR_ENCODING for the whole call, never reduced; an index
+ *                      outside the table or bad offsets: CG1_ERR_ARG; a refused call writes nothing), with CG1_LIGHT_MAX_MSMS and
+ *                      CG1_LIGHT_MAX_TERMS in place of the fixed tables' limits.
+ *   cg1_light_digits   host only, test support: the recoding k = sum_w out[w] 2^(CG1_LIGHT_WINDOW_BITS w), |out[w]| <= 2^(bits - 1),
+ *                      compiled from the function the kernel runs (csrc/light_digits.h); writes and returns CG1_LIGHT_WINDOWS digits.
+ *                      Meaningful for scalars below r.
+ * Limits: CG1_LIGHT_MAX_BASES = 16 384 = 64 provers x 2 n bases at n = 128, the largest batch the prover's records hold; at 128 KiB each
+ * that is 2 GiB of records.  CG1_LIGHT_MAX_MSMS and CG1_LIGHT_MAX_TERMS equal the fixed tables': the kernels share the ticket words (one
+ * per MSM), the finishing kernel's records and the slices of at most 128 terms whose partial sums one workgroup joins.
+ * CG1_LIGHT_WINDOW_BITS may be overridden when the library is built (3 .. 7; an A/B switch for the window plan: tools/gpu_light_table_timing.py). */
+#ifndef CG1_LIGHT_WINDOW_BITS
+#define CG1_LIGHT_WINDOW_BITS 4
+#endif
+#define CG1_LIGHT_WINDOWS ((256 + CG1_LIGHT_WINDOW_BITS - 1) / CG1_LIGHT_WINDOW_BITS)
+#define CG1_LIGHT_MAX_BASES 16384
+#define CG1_LIGHT_MAX_MSMS  1024
+#define CG1_LIGHT_MAX_TERMS 2048
+typedef struct cg1_light cg1_light;
+cg1_light* cg1_light_create(cg1_ctx* ctx, const uint8_t* bases_affine96, size_t n_bases, int* status /* nullable */);
+void   cg1_light_destroy(cg1_light* tab);
+size_t cg1_light_len(const cg1_light* tab);
+size_t cg1_light_bytes(const cg1_light* tab);                        /* device bytes of the table's records */
+int cg1_light_msm(cg1_ctx* ctx, cg1_light* tab, const uint32_t* term_base, const uint8_t* term_scalars32, const uint32_t* offsets, size_t n_msm,
+                  uint8_t* out_blobs144 /* nullable */, uint8_t* out_comp48 /* nullable */);
+int cg1_light_msm_device(cg1_ctx* ctx, cg1_light* tab, const void* d_term_base, const void* d_term_scalars32, const void* d_offsets, size_t n_msm,
+                         size_t n_terms, size_t max_terms, void* d_out_affine96 /* nullable */, void* d_out_comp48 /* nullable */);
+int cg1_light_digits(const uint8_t scalar32[32], int16_t out[CG1_LIGHT_WINDOWS]);
+
+/* ---- The same-MSM argument PROVED on the device: SameMSMProof.new (same_msm.py:50-143) after its generate_blinders(n) draw, for
+ * n_provers independent provers of one length n in step, as ONE launch chain with one host wait (csrc/kernels_same_msm.h,
+ * csrc/same_msm_rounds.h).  All bases stay what they are and the round challenges fold into the scalars through one coefficient vector
+ * per prover.  crs_G_vec are entries of a cg1_fixed table; vec_T | vec_U are per-proof points: the call builds ONE light table over all
+ * provers' T and U (scratch kept with the cg1_fixed handle, regrown only when too small).  Per step two MSM launches -- k_fixed_msm for
+ * the A side, k_light_msm for T and U --, their two k_fixed_finish and one k_smsm_step (the transcript over the prover's own state,
+ * gamma^-1, the fold, the next terms): 3 + 5 (lg n + 1) launches in all.
+ *   per prover p, host buffers:
+ *     g_index[p n ..]     table indices of crs_G_vec
+ *     azz48               A | Z_t | Z_u as 48-byte encodings.  They are only HASHED: validated (compression flag, x < p, on the curve; no
+ *                         subgroup test) and absorbed re-serialised as the reference does (an identity as C0 00 .. 00)
+ *     tu_affine96         vec_T | vec_U: 2 n affine96 records (all-zero = the identity); any curve point, nothing is decoded or subgroup-tested
+ *     vec_x32, vec_r32    canonical scalars; vec_r is the caller's generate_blinders(n); vec_x is not written
+ *     states208           in: the transcript where SameMSMProof.new would find it; out: after the last same_msm_gamma.  The first two
+ *                         same_msm_step1 lists ([A, Z_t, Z_u]; vec_T + vec_U) depend on nothing the device computes and are absorbed on
+ *                         the host into the states that are uploaded; the third list and everything after it on the device
+ *     out_proofs          cg1_same_msm_proof_bytes(n) = (3 + 6 lg n) 48 + 32 bytes each, SameMSMProof.to_bytes order:
+ *                         B_a | B_t | B_u | vec_L_A | vec_L_T | vec_L_U | vec_R_A | vec_R_T | vec_R_U | x_final
+ *     out_clocks          NULL, or 4 words per prover, as cg1_ipa_prove_device
+ *   The returned status covers the whole call, and a refused call leaves out_proofs and states208 untouched.  Refused before anything
+ *   is written: n not a power of two in 2 .. CG1_SAME_MSM_MAX_N, more than CG1_SAME_MSM_MAX_PROVERS provers or n_provers 2 n >
+ *   CG1_LIGHT_MAX_BASES (REFUSED, not chunked -- the caller splits), an index outside the table, a table of another device: CG1_ERR_ARG;
+ *   a scalar >= r: CG1_ERR_ENCODING (never reduced); a T or U coordinate >= p or a point off the curve: cg1_from_affine96's status; an
+ *   undecodable A, Z_t or Z_u: cg1_validate_compressed's status.
+ * Limits: CG1_SAME_MSM_MAX_N = 1024: one prover's 2 n = 2048 light records are 256 MiB, and an MSM of step B has n terms <=
+ * CG1_FIXED_MAX_TERMS.  CG1_SAME_MSM_MAX_PROVERS = 64: 64 provers x 2 n at n = 128 is CG1_LIGHT_MAX_BASES (2 GiB of records), and the 4
+ * MSMs per prover of a launch over T | U stay within CG1_LIGHT_MAX_MSMS.
+ *   cg1_same_msm_round_emulate   host only, test support: the scalar schedule and the fold compiled from the header the kernel runs
+ *                         (csrc/same_msm_rounds.h).  State: x32 (len scalars, in and out), k32 (n0 coefficients, in and out).
+ *                         op 0: the terms of step B over r32 (3 MSMs B_a, B_t, B_u; 4 offsets 0, n0, 2 n0, 3 n0; len = n0).
+ *                         op 1: x <- r + a x with a = challenge32 (alpha).  op 2: the round's terms at the current length len (6 MSMs
+ *                         in the transcript's order L_A, L_T, L_U, R_A, R_T, R_U; 7 offsets 0, h, .., 6 h with h = n0 / 2), then, when
+ *                         challenge32 (gamma) is not NULL, the fold: x32 holds len / 2 scalars afterwards.  Indices of the A lists are
+ *                         g_index's (the fixed table); those of the T and U lists are light-table indices, T[j] at j and U[j] at n0 + j.
+ *                         The same refusals: CG1_ERR_ARG / CG1_ERR_ENCODING. */
+#define CG1_SAME_MSM_MAX_N       1024
+#define CG1_SAME_MSM_MAX_PROVERS 64
+size_t cg1_same_msm_proof_bytes(size_t n);                          /* 0 when n is not a power of two >= 2 */
+int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t n, size_t n_provers, const uint32_t* g_index, const uint8_t* azz48,
+                              const uint8_t* tu_affine96, const uint8_t* vec_x32, const uint8_t* vec_r32, uint8_t* states208, uint8_t* out_proofs,
+                              uint32_t* out_clocks /* nullable */);
+int cg1_same_msm_round_emulate(int op, size_t n0, size_t len, uint8_t* x32, uint8_t* k32, const uint8_t* challenge32 /* nullable for op 2 */,
+                               const uint8_t* r32, const uint32_t* g_index, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets);
+
 #ifdef __cplusplus
 }
 #endif
