@@ -483,11 +483,9 @@ class Context:
         """A resident table of `n_bases` fixed bases (cg1_fixed): 512 KiB of prepared records per base."""
         return FixedTable(self, bases_affine96, n_bases)
 
-    def fixed_msm_host(self, tab: "FixedTable", term_base, scalars32: bytes, offsets, compressed: bool = False) -> list:
-        """cg1_fixed_msm: MSM j over the table entries term_base[offsets[j] : offsets[j + 1]] (bit 31 = the negated base); one 144-byte
-        blob per MSM, or one compressed48 each."""
+    def _table_msm_host(self, fn, tab, term_base, scalars32: bytes, offsets, compressed: bool) -> list:
         if not tab.handle:
-            raise NativeError("the fixed-base table is closed")
+            raise NativeError(f"the {tab._KIND} table is closed")
         m = len(offsets) - 1
         n = offsets[-1]
         assert len(term_base) >= n and len(scalars32) >= 32 * n
@@ -495,18 +493,25 @@ class Context:
         arr = (ctypes.c_uint32 * (m + 1))(*offsets)
         w = 48 if compressed else POINT_BYTES
         out = ctypes.create_string_buffer(w * max(m, 1))
-        self.check(cg1_fixed_msm(self.handle, tab.handle, tb, scalars32, arr, m, None if compressed else out, out if compressed else None))
+        self.check(fn(self.handle, tab.handle, tb, scalars32, arr, m, None if compressed else out, out if compressed else None))
         raw = out.raw
         return [raw[w * j: w * (j + 1)] for j in range(m)]
+
+    def _table_msm_device(self, fn, tab, d_term_base, d_scalars32, d_offsets, n_msm: int, n_terms: int, max_terms: int, d_out_affine96, d_out_comp48) -> None:
+        if not tab.handle:
+            raise NativeError(f"the {tab._KIND} table is closed")
+        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
+        self.check(fn(self.handle, tab.handle, g(d_term_base), g(d_scalars32), g(d_offsets), n_msm, n_terms, max_terms, g(d_out_affine96), g(d_out_comp48)))
+
+    def fixed_msm_host(self, tab: "FixedTable", term_base, scalars32: bytes, offsets, compressed: bool = False) -> list:
+        """cg1_fixed_msm: MSM j over the table entries term_base[offsets[j] : offsets[j + 1]] (bit 31 = the negated base); one 144-byte
+        blob per MSM, or one compressed48 each."""
+        return self._table_msm_host(cg1_fixed_msm, tab, term_base, scalars32, offsets, compressed)
 
     def fixed_msm_device(self, tab: "FixedTable", d_term_base, d_scalars32, d_offsets, n_msm: int, n_terms: int, max_terms: int,
                          d_out_affine96=None, d_out_comp48=None) -> None:
         """cg1_fixed_msm_device: device arrays in, affine96 and / or compressed48 left in device buffers."""
-        if not tab.handle:
-            raise NativeError("the fixed-base table is closed")
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
-        self.check(cg1_fixed_msm_device(self.handle, tab.handle, g(d_term_base), g(d_scalars32), g(d_offsets), n_msm, n_terms, max_terms,
-                                        g(d_out_affine96), g(d_out_comp48)))
+        self._table_msm_device(cg1_fixed_msm_device, tab, d_term_base, d_scalars32, d_offsets, n_msm, n_terms, max_terms, d_out_affine96, d_out_comp48)
 
     def light_table(self, bases_affine96: bytes, n_bases: int) -> "LightTable":
         """A light table of `n_bases` variable bases (cg1_light): built on the device in the call, 128 KiB of XYZZ records per base."""
@@ -514,27 +519,12 @@ class Context:
 
     def light_msm_host(self, tab: "LightTable", term_base, scalars32: bytes, offsets, compressed: bool = False) -> list:
         """cg1_light_msm: fixed_msm_host over a light table."""
-        if not tab.handle:
-            raise NativeError("the light table is closed")
-        m = len(offsets) - 1
-        n = offsets[-1]
-        assert len(term_base) >= n and len(scalars32) >= 32 * n
-        tb = (ctypes.c_uint32 * max(n, 1))(*term_base[:n])
-        arr = (ctypes.c_uint32 * (m + 1))(*offsets)
-        w = 48 if compressed else POINT_BYTES
-        out = ctypes.create_string_buffer(w * max(m, 1))
-        self.check(cg1_light_msm(self.handle, tab.handle, tb, scalars32, arr, m, None if compressed else out, out if compressed else None))
-        raw = out.raw
-        return [raw[w * j: w * (j + 1)] for j in range(m)]
+        return self._table_msm_host(cg1_light_msm, tab, term_base, scalars32, offsets, compressed)
 
     def light_msm_device(self, tab: "LightTable", d_term_base, d_scalars32, d_offsets, n_msm: int, n_terms: int, max_terms: int,
                          d_out_affine96=None, d_out_comp48=None) -> None:
         """cg1_light_msm_device: device arrays in, affine96 and / or compressed48 left in device buffers."""
-        if not tab.handle:
-            raise NativeError("the light table is closed")
-        g = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else int(b))
-        self.check(cg1_light_msm_device(self.handle, tab.handle, g(d_term_base), g(d_scalars32), g(d_offsets), n_msm, n_terms, max_terms,
-                                        g(d_out_affine96), g(d_out_comp48)))
+        self._table_msm_device(cg1_light_msm_device, tab, d_term_base, d_scalars32, d_offsets, n_msm, n_terms, max_terms, d_out_affine96, d_out_comp48)
 
     def ipa_prove_device(self, tab: "FixedTable", n: int, n_provers: int, g_index, g_prime_index, h_index, g_prime_coeffs32, cd48: bytes, z32: bytes,
                          vec_c32: bytes, vec_d32: bytes, vec_r_c32: bytes, vec_r_d32: bytes, states208: bytes, want_clocks: bool = False):
@@ -677,25 +667,28 @@ class Vec:
 class FixedTable:
     """A table of fixed bases resident on the device (cg1_fixed): for each base the 32 x 128 multiples d * 2^(8 w) * B."""
 
+    _KIND = "fixed-base"
+    _create, _bytes, _destroy = cg1_fixed_create, cg1_fixed_bytes, cg1_fixed_destroy
+
     def __init__(self, ctx: Context, bases_affine96: bytes, n_bases: int):
         assert len(bases_affine96) >= 96 * n_bases
         self.ctx, self.n = ctx, int(n_bases)
         st = c_int(0)
-        self.handle = cg1_fixed_create(ctx.handle, bases_affine96, self.n, ctypes.byref(st))
+        self.handle = self._create(ctx.handle, bases_affine96, self.n, ctypes.byref(st))
         if not self.handle:
             msg = cg1_ctx_error(ctx.handle)
-            err = f"cg1_fixed_create({n_bases} bases) failed ({st.value}): {msg.decode() if msg else ''}"
+            err = f"{self._create.__name__}({n_bases} bases) failed ({st.value}): {msg.decode() if msg else ''}"
             if st.value in (ERR_ENCODING, ERR_NOT_ON_CURVE):
                 raise ValueError(err)
             raise NativeError(err)
 
     @property
     def nbytes(self) -> int:
-        return int(cg1_fixed_bytes(self.handle)) if self.handle else 0
+        return int(self._bytes(self.handle)) if self.handle else 0
 
     def free(self) -> None:
         if self.handle:
-            cg1_fixed_destroy(self.handle)
+            self._destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -705,35 +698,11 @@ class FixedTable:
             pass
 
 
-class LightTable:
+class LightTable(FixedTable):
     """A light table of variable bases on the device (cg1_light): for each base the 64 x 8 multiples d * 2^(4 w) * B as XYZZ records."""
 
-    def __init__(self, ctx: Context, bases_affine96: bytes, n_bases: int):
-        assert len(bases_affine96) >= 96 * n_bases
-        self.ctx, self.n = ctx, int(n_bases)
-        st = c_int(0)
-        self.handle = cg1_light_create(ctx.handle, bases_affine96, self.n, ctypes.byref(st))
-        if not self.handle:
-            msg = cg1_ctx_error(ctx.handle)
-            err = f"cg1_light_create({n_bases} bases) failed ({st.value}): {msg.decode() if msg else ''}"
-            if st.value in (ERR_ENCODING, ERR_NOT_ON_CURVE):
-                raise ValueError(err)
-            raise NativeError(err)
-
-    @property
-    def nbytes(self) -> int:
-        return int(cg1_light_bytes(self.handle)) if self.handle else 0
-
-    def free(self) -> None:
-        if self.handle:
-            cg1_light_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    _KIND = "light"
+    _create, _bytes, _destroy = cg1_light_create, cg1_light_bytes, cg1_light_destroy
 
 
 class Staging:

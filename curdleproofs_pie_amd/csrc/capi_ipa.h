@@ -77,14 +77,7 @@ int cg1_ipa_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_provers,
   while (((size_t)1 << lg) < n) ++lg;
   const size_t pb = cg1_ipa_proof_bytes(n);
   const IpaLayout L = ipa_layout(n, P, pb);
-  if (L.total > t->cap_ipa) {
-    if (t->h_ipa) (void)hipHostFree(t->h_ipa);
-    if (t->d_ipa) (void)hipFree(t->d_ipa);
-    t->h_ipa = nullptr; t->d_ipa = nullptr; t->cap_ipa = 0;
-    HIPCHK(hipHostMalloc((void**)&t->h_ipa, L.total, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&t->d_ipa, L.total));
-    t->cap_ipa = L.total;
-  }
+  { const int rc = cg1::grow_pinned_pair(ctx, t->h_ipa, nullptr, t->d_ipa, t->cap_ipa, L.total, L.total, hipHostMallocDefault); if (rc) return rc; }
   // ---- stage the inputs: one block, one copy
   uint8_t* H = t->h_ipa;
   uint8_t* D = t->d_ipa;
@@ -122,22 +115,20 @@ int cg1_ipa_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_provers,
   hipLaunchKernelGGL(cg1ipa::k_ipa_step, dim3(Pn), dim3(cg1ipa::IPA_THREADS), 0, ctx->stream, a, cg1ipa::IPA_BEGIN, nn, 0u);
   {
     const uint32_t M = 2 * Pn;
-    const FixedShape sh = fixed_pick_shape(ctx, [&](uint32_t s) { return (size_t)M * std::max<uint32_t>(1u, (nn + s - 1) / s); }, M, nn);
-    const int rc = fixed_enqueue(ctx, t, a.tb, (const uint32_t*)a.sc, (const uint32_t*)(D + L.offs1), M, Pn * cg1ipa::step1_terms(nn), nn, sh, false, nullptr, D + L.pts);
+    const int rc = table_enqueue<FixedKind>(ctx, t, a.tb, (const uint32_t*)a.sc, (const uint32_t*)(D + L.offs1), M, Pn * cg1ipa::step1_terms(nn), nn, table_pick_shape<FixedKind>(ctx, M, nn), false, nullptr, D + L.pts);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(cg1ipa::k_ipa_step, dim3(Pn), dim3(cg1ipa::IPA_THREADS), 0, ctx->stream, a, cg1ipa::IPA_STEP1, nn, 0u);
   for (uint32_t r = 0; r < (uint32_t)lg; ++r) {
     const uint32_t M = 4 * Pn, mt = nn / 2 + 1;
-    const FixedShape sh = fixed_pick_shape(ctx, [&](uint32_t s) { return (size_t)M * std::max<uint32_t>(1u, (mt + s - 1) / s); }, M, mt);
-    const int rc = fixed_enqueue(ctx, t, a.tb, (const uint32_t*)a.sc, (const uint32_t*)(D + L.offsr), M, Pn * cg1ipa::round_terms(nn), mt, sh, false, nullptr, D + L.pts);
+    const int rc = table_enqueue<FixedKind>(ctx, t, a.tb, (const uint32_t*)a.sc, (const uint32_t*)(D + L.offsr), M, Pn * cg1ipa::round_terms(nn), mt, table_pick_shape<FixedKind>(ctx, M, mt), false, nullptr, D + L.pts);
     if (rc) return rc;
     hipLaunchKernelGGL(cg1ipa::k_ipa_step, dim3(Pn), dim3(cg1ipa::IPA_THREADS), 0, ctx->stream, a, cg1ipa::IPA_ROUND, nn >> r, r);
   }
   HIPCHK(hipMemcpyAsync(H + L.down_begin, D + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));                 // the one wait
   HIPCHK(hipGetLastError());
-  { const int rc = fixed_status_error(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
+  { const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
   memcpy(out_proofs, H + L.proof, P * pb);
   memcpy(states208, H + L.states, P * 208);
   if (out_clocks) memcpy(out_clocks, H + L.clocks, P * 16);

@@ -75,14 +75,7 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
   while (((size_t)1 << lg) < n) ++lg;
   const size_t pb = cg1_same_msm_proof_bytes(n);
   const SmsmLayout L = smsm_layout(n, P, pb);
-  if (L.total > t->cap_smsm) {
-    if (t->h_smsm) (void)hipHostFree(t->h_smsm);
-    if (t->d_smsm) (void)hipFree(t->d_smsm);
-    t->h_smsm = nullptr; t->d_smsm = nullptr; t->cap_smsm = 0;
-    HIPCHK(hipHostMalloc((void**)&t->h_smsm, L.total, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&t->d_smsm, L.total));
-    t->cap_smsm = L.total;
-  }
+  { const int rc = cg1::grow_pinned_pair(ctx, t->h_smsm, nullptr, t->d_smsm, t->cap_smsm, L.total, L.total, hipHostMallocDefault); if (rc) return rc; }
   if (P * 2 * n > t->cap_smsm_bases) {                      // the light table's records: kept with the handle, regrown only when too small
     if (t->smsm_light) cg1_light_destroy(t->smsm_light);
     t->smsm_light = new cg1_light();
@@ -127,35 +120,25 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
   a.tba = (uint32_t*)(D + L.tba); a.sca = (uint64_t*)(D + L.sca); a.tbl = (uint32_t*)(D + L.tbl); a.scl = (uint64_t*)(D + L.scl);
   a.status_a = t->d_status; a.status_tu = lt->d_status; a.chain_status = (uint32_t*)(D + L.status); a.clocks = (uint32_t*)(D + L.clocks);
 
-  // ---- the slice sums of the chain's largest launches (step B: n terms per MSM), reserved BEFORE the first launch: fixed_enqueue /
-  // light_enqueue would otherwise free and allocate in mid-chain, which waits for the device
-  auto shapes = [&](uint32_t per_a, uint32_t mt, FixedShape& sa, FixedShape& sl) {
+  // ---- the slice sums of the chain's largest launches (step B: n terms per MSM), reserved BEFORE the first launch: table_enqueue
+  // would otherwise free and allocate in mid-chain, which waits for the device
+  auto shapes = [&](uint32_t per_a, uint32_t mt, TableShape& sa, TableShape& sl) {
     const uint32_t Ma = per_a * Pn, Ml = 2 * per_a * Pn;
-    sa = fixed_pick_shape(ctx, [&](uint32_t s) { return (size_t)Ma * std::max<uint32_t>(1u, (mt + s - 1) / s); }, Ma, mt);
-    sl = light_pick_shape(ctx, [&](uint32_t s) { return (size_t)Ml * std::max<uint32_t>(1u, (mt + s - 1) / s); }, Ml, mt);
+    sa = table_pick_shape<FixedKind>(ctx, Ma, mt);
+    sl = table_pick_shape<LightKind>(ctx, Ml, mt);
   };
   {
     size_t need_a = 0, need_l = 0;
     for (uint32_t per_a = 1; per_a <= 2; ++per_a) {
       const uint32_t mt = per_a == 1 ? nn : hh;
-      FixedShape sa, sl;
+      TableShape sa, sl;
       shapes(per_a, mt, sa, sl);
       const size_t Sa = (mt + sa.slice - 1) / sa.slice, Sl = (mt + sl.slice - 1) / sl.slice;
       if (Sa > 1) need_a = std::max(need_a, (size_t)per_a * Pn * Sa);
       if (Sl > 1) need_l = std::max(need_l, (size_t)2 * per_a * Pn * Sl);
     }
-    if (need_a > t->cap_partial) {
-      if (t->d_partial) (void)hipFree(t->d_partial);
-      t->d_partial = nullptr; t->cap_partial = 0;
-      HIPCHK(hipMalloc(&t->d_partial, need_a * sizeof(cg1::PointSum)));
-      t->cap_partial = need_a;
-    }
-    if (need_l > lt->cap_partial) {
-      if (lt->d_partial) (void)hipFree(lt->d_partial);
-      lt->d_partial = nullptr; lt->cap_partial = 0;
-      HIPCHK(hipMalloc(&lt->d_partial, need_l * sizeof(cg1::PointSum)));
-      lt->cap_partial = need_l;
-    }
+    { const int rc = cg1::grow_device(ctx, t->d_partial, t->cap_partial, need_a, need_a); if (rc) return rc; }
+    { const int rc = cg1::grow_device(ctx, lt->d_partial, lt->cap_partial, need_l, need_l); if (rc) return rc; }
   }
 
   // ---- the chain: begin, build | MSMs finish stepB | (MSMs finish round) x lg n -- plain launches on the context's stream, no host wait between
@@ -163,10 +146,10 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
   light_build(ctx, D + L.tu96, P * 2 * n, lt->d_tab);
   auto msms = [&](uint32_t per_a, uint32_t mt, const uint32_t* d_oa, const uint32_t* d_ol) -> int {
     const uint32_t Ma = per_a * Pn, Ml = 2 * per_a * Pn;
-    FixedShape sa, sl;
+    TableShape sa, sl;
     shapes(per_a, mt, sa, sl);
-    { const int rc = fixed_enqueue(ctx, t, a.tba, (const uint32_t*)a.sca, d_oa, Ma, Pn * nn, mt, sa, false, nullptr, D + L.pts_a); if (rc) return rc; }
-    return light_enqueue(ctx, lt, a.tbl, (const uint32_t*)a.scl, d_ol, Ml, Pn * 2 * nn, mt, sl, false, nullptr, D + L.pts_tu);
+    { const int rc = table_enqueue<FixedKind>(ctx, t, a.tba, (const uint32_t*)a.sca, d_oa, Ma, Pn * nn, mt, sa, false, nullptr, D + L.pts_a); if (rc) return rc; }
+    return table_enqueue<LightKind>(ctx, lt, a.tbl, (const uint32_t*)a.scl, d_ol, Ml, Pn * 2 * nn, mt, sl, false, nullptr, D + L.pts_tu);
   };
   { const int rc = msms(1, nn, (const uint32_t*)(D + L.offs_a1), (const uint32_t*)(D + L.offs_l2)); if (rc) return rc; }
   hipLaunchKernelGGL(cg1smsm::k_smsm_step, dim3(Pn), dim3(cg1smsm::SMSM_THREADS), 0, ctx->stream, a, cg1smsm::SMSM_STEPB, nn, 0u);
@@ -177,7 +160,7 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
   HIPCHK(hipMemcpyAsync(H + L.down_begin, D + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));                 // the one wait
   HIPCHK(hipGetLastError());
-  { const int rc = fixed_status_error(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
+  { const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
   memcpy(out_proofs, H + L.proof, P * pb);
   memcpy(states208, H + L.states, P * 208);
   if (out_clocks) memcpy(out_clocks, H + L.clocks, P * 16);

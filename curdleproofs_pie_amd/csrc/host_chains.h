@@ -52,6 +52,46 @@ static int wait_stream(Ctx* ctx) {
   return CG1_OK;
 }
 
+// Wait, spinning, for the sequence number a call's last kernel stores into the context's flag word (mapped host memory) once everything
+// it exports is there; look at the stream now and then so that a failed launch cannot hang us.
+static int wait_export_flag(Ctx* ctx, uint32_t seq) {
+  volatile uint32_t* flag = ctx->h_flag;
+  for (uint32_t spins = 0; *flag != seq; ++spins) {
+    if ((spins & 0x3fffu) == 0x3fffu) {
+      hipError_t q = hipStreamQuery(ctx->stream);
+      if (q == hipSuccess) { if (*flag != seq) { snprintf(ctx->err, sizeof ctx->err, "the stream drained without the export flag"); return CG1_ERR_HIP; } break; }
+      if (q != hipErrorNotReady) { snprintf(ctx->err, sizeof ctx->err, "stream failed: %s", hipGetErrorString(q)); return CG1_ERR_HIP; }
+    }
+    __builtin_ia32_pause();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return CG1_OK;
+}
+
+// Regrow a buffer a handle keeps between calls, only when it is too small for `need`: freed, then `grown` (>= need: the site's growth
+// policy) allocated; a failure leaves it empty.  A device buffer of T ...
+template <class T>
+static int grow_device(Ctx* ctx, T*& d, size_t& cap, size_t need, size_t grown) {
+  if (need <= cap) return CG1_OK;
+  if (d) (void)hipFree(d);
+  d = nullptr; cap = 0;
+  HIPCHK(hipMalloc((void**)&d, grown * sizeof(T)));
+  cap = grown;
+  return CG1_OK;
+}
+// ... and a page-locked block with its device twin.  flags: hipHostMalloc's; h_dev (nullable): where a mapped block's device address goes
+static int grow_pinned_pair(Ctx* ctx, uint8_t*& h, uint8_t** h_dev, uint8_t*& d, size_t& cap, size_t need, size_t grown, unsigned flags) {
+  if (need <= cap) return CG1_OK;
+  if (h) (void)hipHostFree(h);
+  if (d) (void)hipFree(d);
+  h = nullptr; d = nullptr; cap = 0;
+  HIPCHK(hipHostMalloc((void**)&h, grown, flags));
+  if (h_dev) HIPCHK(hipHostGetDevicePointer((void**)h_dev, h, 0));
+  HIPCHK(hipMalloc((void**)&d, grown));
+  cap = grown;
+  return CG1_OK;
+}
+
 // Where an MSM's points come from (all device memory):
 //   AFFINE96  n x 96 B standard-form affine records (the C ABI's "affine96")                      -> k_prepare_points
 //   BLOBS     n x 144 B host point blobs as G1Point objects hold them (Jacobian, radix 2^384)     -> k_prepare_blobs
@@ -325,17 +365,7 @@ static int msm_finish(Ctx* ctx, cg1h::jac& result) {
   if (pd.zero_copy && !ctx->blocking_sync && pd.profile < 2) {
     if (pd.arm_helpers) for (int j = 0; j < 3 && j + 1 < ctx->horner_threads; ++j) ctx->helper[j].arm();
     stand_down.on = pd.arm_helpers;
-    // poll the flag word k_export_host writes last; look at the stream now and then so that a failed launch cannot hang us
-    volatile uint32_t* flag = ctx->h_flag;
-    for (uint32_t spins = 0; *flag != pd.seq; ++spins) {
-      if ((spins & 0x3fffu) == 0x3fffu) {
-        hipError_t q = hipStreamQuery(ctx->stream);
-        if (q == hipSuccess) { if (*flag != pd.seq) { snprintf(ctx->err, sizeof ctx->err, "the stream drained without the export flag"); return CG1_ERR_HIP; } break; }
-        if (q != hipErrorNotReady) { snprintf(ctx->err, sizeof ctx->err, "stream failed: %s", hipGetErrorString(q)); return CG1_ERR_HIP; }
-      }
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    int wrc = wait_export_flag(ctx, pd.seq); if (wrc) return wrc;
   } else {
     int wrc = wait_stream(ctx); if (wrc) return wrc;
   }
@@ -566,16 +596,7 @@ static int msm_small_batched_finish(Ctx* ctx, uint32_t M, std::vector<cg1h::jac>
   ctx->pend.active = false;
   HIPCHK(hipSetDevice(ctx->device));
   if (!ctx->blocking_sync) {
-    volatile uint32_t* flag = ctx->h_flag;
-    for (uint32_t spins = 0; *flag != pd.seq; ++spins) {
-      if ((spins & 0x3fffu) == 0x3fffu) {
-        hipError_t q = hipStreamQuery(ctx->stream);
-        if (q == hipSuccess) { if (*flag != pd.seq) { snprintf(ctx->err, sizeof ctx->err, "the stream drained without the export flag"); return CG1_ERR_HIP; } break; }
-        if (q != hipErrorNotReady) { snprintf(ctx->err, sizeof ctx->err, "stream failed: %s", hipGetErrorString(q)); return CG1_ERR_HIP; }
-      }
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    int wrc = wait_export_flag(ctx, pd.seq); if (wrc) return wrc;
   } else {
     int wrc = wait_stream(ctx); if (wrc) return wrc;
   }

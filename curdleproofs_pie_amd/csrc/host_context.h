@@ -121,8 +121,8 @@ struct Ctx {
   void* d_opening = nullptr; size_t cap_opening = 0;              // cg1_opening_prepare_device's scratch (940 B per proof)
   void* d_prover = nullptr; size_t cap_prover = 0;                // cg1_opening_prove_device's scratch (1 252 B per proof)
   PreparedPoint* d_gen_tab = nullptr;   // k_generator_mul's table of G (GEN_ENTRIES records), built at the first use (cg1_generator_mul_device)
-  int fixed_slice = 0;                  // "fixed_slice": terms per workgroup of k_fixed_msm (1 .. 128; 0 = by the size of the call).  A/B switch
-  int fixed_waves = 0;                  // "fixed_waves": waves per workgroup of k_fixed_msm (4, 8, 16; 0 = by the size of the call).  A/B switch
+  int fixed_slice = 0;                  // "fixed_slice": terms per workgroup of k_table_msm (1 .. 128; 0 = by the size of the call).  A/B switch
+  int fixed_waves = 0;                  // "fixed_waves": waves per workgroup of k_table_msm (4, 8, 16; 0 = by the size of the call).  A/B switch
   int ipa_inv = 0;                      // "ipa_inv": how k_ipa_step inverts a round challenge (0: binary Euclid, 1: a^(r-2)).  A/B switch
   int merlin_last_kernel = 0;           // which kernel served the last cg1_merlin_batch_device call: 2 block program, 1 byte machine, 0 one lane at a time
   int merlin_rows = 1;                  // "merlin_rows": 1 = cg1_merlin_batch_device hashes whole rate blocks (k_merlin_batch_rows) when the program fits, 0 = byte machine

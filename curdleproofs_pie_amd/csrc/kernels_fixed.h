@@ -1,4 +1,6 @@
-// k_fixed_msm: MSMs over a RESIDENT table of fixed bases -- no doubling anywhere, the sum finished on the device.
+// k_table_msm: MSMs over a RESIDENT table of window multiples -- no doubling anywhere, the sum finished on the device.  One kernel body,
+// instantiated per PLAN (what a table's records and digits are): FixedPlan here, for the tables of fixed bases described below, and
+// LightPlan (kernels_light.h) for the light tables of bases that live for one proof.
 // Part of the single translation unit csrc/msm_gpu.hip (included inside namespace cg1, after kernels_generator.h).
 //
 // The protocol's small MSMs run over points that never change (the CRS: crs.py:92-101), yet k_msm_small pays a full Pippenger pass --
@@ -11,7 +13,7 @@
 //
 // Grid = (slices of `slice` terms of one MSM, MSMs of the call); W = 8 or 16 waves per workgroup (the launch's choice, below):
 //   digits   one lane per term: scalar < r and index < n_bases checked (a bad term sets the call's status word and contributes
-//            nothing), 32 digits into LDS, window-major -- pair p = w * ns + t, so that the waves share the terms evenly whatever
+//            nothing), the plan's digits (32 here) into LDS, window-major -- pair p = w * ns + t, so that the waves share the terms evenly whatever
 //            windows the scalars leave empty (small scalars: only window 0)
 //   sum      wave v adds the records of pairs v, v + W, ... one after the other; zero digits are skipped (wave-uniform)
 //   tree     W waves -> 1 through LDS (log2 W levels)
@@ -31,7 +33,7 @@
 // 64 provers in step (532 480 additions, ~0.6 ms at the chip's row rate), is where a quad variant would start to pay -- not built.
 // The launch shape (slice, waves per workgroup) was then picked by timing this kernel itself (tools/gpu_fixed_base_timing.py --shapes ->
 // profiles/r06_fixed_base_timing.txt: 4 x 65 terms 0.112 ms at 8 waves x 2 terms against 0.154 at 16 x 8 and 0.224 at 16 x 16; the
-// rule is fixed_pick_shape, capi_fixed.h).  All additions are complete (row_add: identity,
+// rule is table_pick_shape, capi_fixed.h).  All additions are complete (row_add: identity,
 // equal and opposite operands take the exact one-lane formulas).
 #pragma once
 
@@ -44,8 +46,9 @@ constexpr uint32_t FX_MAX_TERMS = CG1_FIXED_MAX_TERMS;     // per MSM
 constexpr uint32_t FX_MAX_MSMS = CG1_FIXED_MAX_MSMS;       // per call
 constexpr uint32_t FX_BAD_SCALAR = 1u, FX_BAD_INDEX = 2u, FX_BAD_OFFSETS = 4u;      // bits of the call's status word
 
-struct FixedArgs {
-  const PreparedPoint* tab;
+template <class Record>
+struct TableArgs {
+  const Record* tab;
   uint32_t n_bases;
   const uint32_t* term_base;              // per term: index into the table; bit 31 = the negated base
   const uint32_t* scalars;                // per term: 8 words, little-endian
@@ -59,6 +62,20 @@ struct FixedArgs {
   uint32_t* flag_host;
   uint32_t seq;
   PointSum* out_sum;                      // nullable: M XYZZ records (strictly normal limbs) for k_fixed_finish
+};
+
+// The fixed plan: 32 signed 8-bit digits per scalar (two bytes each in LDS: -128 .. 128), affine prepared records -- ZZ = ZZZ = one.
+struct FixedPlan {
+  using Record = PreparedPoint;
+  using Digit = int16_t;
+  static constexpr int WINDOWS = FIX_WINDOWS;
+  static __device__ __forceinline__ void digits(const uint32_t s[8], Digit* dst, int stride) { (void)fixed_digits(s, dst, stride); }
+  static __device__ __forceinline__ xyzz_row load(const Record* tab, uint32_t base, uint32_t window, uint32_t magnitude, const RowK& k) {
+    const Record* rec = tab + ((size_t)base * GEN_WINDOWS + window) * GEN_HALF + (magnitude - 1u);
+    xyzz_row o;
+    o.X = row_load14(rec->x, k.lane16); o.Y = row_load14(rec->y, k.lane16); o.ZZ = k.one; o.ZZZ = k.one; o.inf = rec->flags & 1u;
+    return o;
+  }
 };
 
 // the one addition of the kernel, out of line: four call sites share ~5 KB of code (arguments and result travel in registers)
@@ -75,8 +92,12 @@ __device__ __forceinline__ xyzz_row fixed_tree(xyzz_row acc, PointSum* sh, uint3
   return acc;
 }
 
-__global__ void __launch_bounds__(FX_THREADS) k_fixed_msm(FixedArgs a) {
-  __shared__ int16_t s_dig[FX_MAX_SLICE * FIX_WINDOWS];
+// A plan is what differs between the tables: Record (the type of tab), Digit (the LDS element of a digit), WINDOWS, digits(s, dst, stride)
+// and load(tab, base, window, magnitude, k) -> the record as a row.  Compile-time facts and inlined functions only: each instantiation
+// is the kernel written out for its table.
+template <class Plan>
+__global__ void __launch_bounds__(FX_THREADS) k_table_msm(TableArgs<typename Plan::Record> a) {
+  __shared__ typename Plan::Digit s_dig[FX_MAX_SLICE * Plan::WINDOWS];
   __shared__ uint32_t s_base[FX_MAX_SLICE];
   __shared__ PointSum s_sum[FX_WAVES / 2];
   __shared__ uint32_t s_ticket;
@@ -107,7 +128,7 @@ __global__ void __launch_bounds__(FX_THREADS) k_fixed_msm(FixedArgs a) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) s[k] = 0;
     }
-    (void)fixed_digits(s, &s_dig[t], (int)ns);
+    Plan::digits(s, &s_dig[t], (int)ns);
     s_base[t] = bad ? 0u : tb;
   }
   __syncthreads();
@@ -116,17 +137,14 @@ __global__ void __launch_bounds__(FX_THREADS) k_fixed_msm(FixedArgs a) {
   const RowK k = row_constants();
   const uint32_t l = k.lane16;
   xyzz_row acc; acc.X = acc.Y = acc.ZZ = acc.ZZZ = 0; acc.inf = 1;
-  const uint32_t npairs = ns * (uint32_t)FIX_WINDOWS;
+  const uint32_t npairs = ns * (uint32_t)Plan::WINDOWS;
 #pragma unroll 1
   for (uint32_t p = wv; p < npairs; p += W) {
     const int d = __builtin_amdgcn_readfirstlane((int)s_dig[p]);
     if (d == 0) continue;
     const uint32_t w = p / ns, t = p - w * ns;
     const uint32_t tb = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_base[t]);
-    const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-    const PreparedPoint* rec = a.tab + ((size_t)(tb & 0x7fffffffu) * GEN_WINDOWS + w) * GEN_HALF + (mag - 1u);
-    xyzz_row o;
-    o.X = row_load14(rec->x, l); o.Y = row_load14(rec->y, l); o.ZZ = k.one; o.ZZZ = k.one; o.inf = rec->flags & 1u;
+    xyzz_row o = Plan::load(a.tab, tb & 0x7fffffffu, w, (uint32_t)(d < 0 ? -d : d), k);
     if ((d < 0) != ((tb >> 31) != 0u)) o.Y = row_norm_pass(row_norm_pass(k.kp3 - o.Y, l), l);
     acc = fixed_add(acc, o, k);
   }
@@ -202,7 +220,7 @@ __device__ __noinline__ uint32_t row_inv(uint32_t a, const RowK k) {
   return r;
 }
 
-// The sums k_fixed_msm left on the device -> affine96 (standard words, zeros = identity) and / or compressed48: one ROW of a wave per
+// The sums k_table_msm left on the device -> affine96 (standard words, zeros = identity) and / or compressed48: one ROW of a wave per
 // output (four outputs per workgroup), one inversion each -- row_inv above -- and lane 0 of the row finishes on the one-lane form
 // (k_generator_mul's tail).  A call whose status word is set writes nothing.
 __global__ void __launch_bounds__(64) k_fixed_finish(const PointSum* __restrict__ sums, const uint32_t* __restrict__ status, uint32_t M,

@@ -1,5 +1,5 @@
 // k_ipa_step: everything of the inner-product argument's prover (ipa.py:97-153) that is NOT a group operation, as the kernel that
-// sits between two k_fixed_msm / k_fixed_finish launches -- so that the whole argument is one launch chain with one host wait.
+// sits between two k_table_msm / k_fixed_finish launches -- so that the whole argument is one launch chain with one host wait.
 // Part of the single translation unit csrc/msm_gpu.hip (after kernels_merlin.h and kernels_fixed.h).
 //
 // One workgroup per prover, three phases (the host enqueues  begin | MSM finish step1 | (MSM finish round) x lg n):
@@ -35,7 +35,7 @@ struct IpaArgs {
   uint8_t* chal;                             // [P][64]: where the transcript writes its draws
   const uint32_t* pts48;                     // k_fixed_finish's encodings of the launch before: [P][2 or 4][12 words]
   uint32_t* proof; uint32_t proof_words;     // [P][proof_words]: IPA.to_bytes order
-  uint32_t* tb; uint64_t* sc;                // the term arrays k_fixed_msm reads: indices, scalars
+  uint32_t* tb; uint64_t* sc;                // the term arrays k_table_msm reads: indices, scalars
   const uint32_t* msm_status;                // the status word of the MSM launch before
   uint32_t* chain_status;                    // accumulated over the chain, read once at its end
   uint32_t* clocks;                          // [P][4]: lane 0's clock ticks (s_memtime) in the transcript | the inversions of gamma | whole steps that emit terms | steps counted

@@ -1,4 +1,4 @@
-// Light tables: window multiples of VARIABLE bases, built on the device in two launches, and k_light_msm over them -- no doubling at MSM time.
+// Light tables: window multiples of VARIABLE bases, built on the device in two launches, and the light plan of k_table_msm -- no doubling at MSM time.
 // Part of the single translation unit csrc/msm_gpu.hip (included inside namespace cg1, after kernels_fixed.h).
 //
 // A cg1_fixed table (kernels_fixed.h) costs 512 KiB and ~0.35 ms per base: right for the CRS, which lives as long as the process, and
@@ -17,32 +17,14 @@
 //                       latency of the build (1.25 us each measured for this kernel: 315 us / 252, profiles/r08_light_table_kernels.txt)
 //   k_light_multiples   one wave per (base, window): Q = 2^(c w) B is there; 2 Q = dbl(Q), 3 Q = 2 Q + Q, 4 Q = dbl(2 Q), ... one
 //                       operation per record, the earlier multiples kept by the wave in row form (five words per lane and point).  The
-//                       row arithmetic itself spills: the record shows 716 B of scratch here and 780 B in k_light_msm
+//                       row arithmetic itself spills: the record shows 716 B of scratch here and 780 B in k_table_msm<LightPlan>
 // One wave per RECORD, each walking its own double-and-add from Q (depth 3 to 4 at c = 4), would shorten the second chain from 7 steps
 // to 4 at 22 operations per window instead of 7 -- and already one proof's table (256 bases x 64 windows = 16 384 waves, sixteen per
 // SIMD) fills the chip, where the number of operations is what is paid: not built.
 //
-// k_light_msm is k_fixed_msm over these records: the same grid (slices, MSMs), digits in LDS window-major, one row_add per non-zero
-// digit, the LDS tree, the ticketed slice join, the same exports and the same status bits -- it shares fixed_add, fixed_tree and
-// k_fixed_finish.  No workgroup waits for another; nothing spins.
+// The MSM over these records is k_table_msm (kernels_fixed.h) with LightPlan, below: the one kernel body -- grid, digits in LDS, one
+// row_add per non-zero digit, the LDS tree, the ticketed slice join, the exports, the status bits -- and k_fixed_finish after it.
 #pragma once
-
-struct LightArgs {
-  const PointSum* tab;
-  uint32_t n_bases;
-  const uint32_t* term_base;              // per term: index into the table; bit 31 = the negated base
-  const uint32_t* scalars;                // per term: 8 words, little-endian
-  const uint32_t* offs;                   // M + 1 term offsets
-  uint32_t M, n_terms, max_terms;         // max_terms: the longest MSM the grid was sized for
-  uint32_t slice, Smax;                   // terms per workgroup; slices of the longest MSM (= gridDim.x)
-  PointSum* partial;                      // [M][Smax]  (Smax > 1)
-  uint32_t* counters;                     // [0, M): slice tickets; [M]: finished MSMs; [M + 1]: status bits.  Zero between calls.
-  uint32_t* status_out;                   // 4 words: [0] = status bits of the call
-  PointWords* out_host;                   // nullable: M records in mapped host memory
-  uint32_t* flag_host;
-  uint32_t seq;
-  PointSum* out_sum;                      // nullable: M XYZZ records (strictly normal limbs) for k_fixed_finish
-};
 
 __device__ __forceinline__ size_t light_record(uint32_t b, uint32_t w, uint32_t mag) {      // index of |d| = mag, window w, base b
   return ((size_t)b * LT_WINDOWS + w) * LT_HALF + (mag - 1u);
@@ -90,92 +72,14 @@ __global__ void __launch_bounds__(64) k_light_multiples(PointSum* __restrict__ t
   }
 }
 
-__global__ void __launch_bounds__(FX_THREADS) k_light_msm(LightArgs a) {
-  __shared__ int8_t s_dig[FX_MAX_SLICE * LT_WINDOWS];
-  __shared__ uint32_t s_base[FX_MAX_SLICE];
-  __shared__ PointSum s_sum[FX_WAVES / 2];
-  __shared__ uint32_t s_ticket;
-
-  const uint32_t tid = threadIdx.x, wv = tid >> 6, W = blockDim.x >> 6, sl = blockIdx.x, msm = blockIdx.y, M = a.M;
-  uint32_t first = a.offs[msm], n = a.offs[msm + 1] - first;
-  if (a.offs[msm + 1] < first || a.offs[msm + 1] > a.n_terms || n > a.max_terms) {       // never read past the term arrays
-    if (tid == 0 && sl == 0) atomicOr(&a.counters[M + 1], FX_BAD_OFFSETS);
-    first = 0; n = 0;
+// The light plan: LT_WINDOWS signed c-bit digits per scalar (one byte each in LDS: the slice's digits are 8 KiB at c = 4, as the fixed
+// plan's), full XYZZ records with their own infinity flags.
+struct LightPlan {
+  using Record = PointSum;
+  using Digit = int8_t;
+  static constexpr int WINDOWS = LT_WINDOWS;
+  static __device__ __forceinline__ void digits(const uint32_t s[8], Digit* dst, int stride) { (void)light_digits(s, dst, stride); }
+  static __device__ __forceinline__ xyzz_row load(const Record* tab, uint32_t base, uint32_t window, uint32_t magnitude, const RowK& k) {
+    return row_load_sum(tab + light_record(base, window, magnitude), k.lane16);
   }
-  const uint32_t S = n ? (n + a.slice - 1u) / a.slice : 1u;                                 // an empty MSM: one workgroup exports the identity
-  if (sl >= S) return;
-  const uint32_t base = sl * a.slice;
-  const uint32_t ns = n - base < a.slice ? n - base : a.slice;
-
-  // ---- digits
-  for (uint32_t t = tid; t < ns; t += blockDim.x) {
-    const uint32_t i = first + base + t;
-    uint32_t s[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] = a.scalars[8ull * i + k];
-    const uint32_t tb = a.term_base[i], idx = tb & 0x7fffffffu;
-    uint32_t bad = 0;
-    if (!fixed_scalar_below_r(s)) bad |= FX_BAD_SCALAR;
-    if (idx >= a.n_bases) bad |= FX_BAD_INDEX;
-    if (bad) {
-      atomicOr(&a.counters[M + 1], bad);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s[k] = 0;
-    }
-    (void)light_digits(s, &s_dig[t], (int)ns);
-    s_base[t] = bad ? 0u : tb;
-  }
-  __syncthreads();
-
-  // ---- sum: one record per non-zero digit
-  const RowK k = row_constants();
-  const uint32_t l = k.lane16;
-  xyzz_row acc; acc.X = acc.Y = acc.ZZ = acc.ZZZ = 0; acc.inf = 1;
-  const uint32_t npairs = ns * (uint32_t)LT_WINDOWS;
-#pragma unroll 1
-  for (uint32_t p = wv; p < npairs; p += W) {
-    const int d = __builtin_amdgcn_readfirstlane((int)s_dig[p]);
-    if (d == 0) continue;
-    const uint32_t w = p / ns, t = p - w * ns;
-    const uint32_t tb = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_base[t]);
-    xyzz_row o = row_load_sum(a.tab + light_record(tb & 0x7fffffffu, w, (uint32_t)(d < 0 ? -d : d)), l);
-    if ((d < 0) != ((tb >> 31) != 0u)) o.Y = row_norm_pass(row_norm_pass(k.kp3 - o.Y, l), l);
-    acc = fixed_add(acc, o, k);
-  }
-  acc = fixed_tree(acc, s_sum, wv, W, k);
-
-  // ---- join the slices: the last workgroup of this MSM to arrive adds their partial sums
-  if (S > 1u) {
-    PointSum* mine = a.partial + (size_t)msm * a.Smax;
-    if (wv == 0u) row_store_sum(mine + sl, acc, l);
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) s_ticket = atomicAdd(&a.counters[msm], 1u);
-    __syncthreads();
-    if (s_ticket != S - 1u) return;
-    __threadfence();
-    acc.X = acc.Y = acc.ZZ = acc.ZZZ = 0; acc.inf = 1;
-#pragma unroll 1
-    for (uint32_t s2 = wv; s2 < S; s2 += W) acc = fixed_add(acc, row_load_sum(mine + s2, l), k);
-    acc = fixed_tree(acc, s_sum, wv, W, k);
-  }
-  if (wv != 0u) return;                                    // (past the last barrier)
-
-  // ---- export
-  if (a.out_sum) {
-    const xyzz r = row_to_xyzz(acc, l);
-    if (tid == 0) store_sum(a.out_sum + msm, r);
-  }
-  if (a.out_host) row_export4(acc, l, a.out_host + msm);
-  __threadfence_system();                                  // the exporting lanes' stores are visible before the ticket is drawn
-  if (tid == 0) {
-    a.counters[msm] = 0;                                   // this MSM's ticket word is free for the next call
-    if (atomicAdd(&a.counters[M], 1u) == M - 1u) {         // the last MSM of the call: status word, then the flag the host polls
-      a.status_out[0] = atomicAdd(&a.counters[M + 1], 0u);
-      a.status_out[1] = 0; a.status_out[2] = 0; a.status_out[3] = 0;
-      a.counters[M] = 0; a.counters[M + 1] = 0;
-      __threadfence_system();
-      if (a.flag_host) __hip_atomic_store(a.flag_host, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
+};

@@ -1,5 +1,5 @@
 // k_smsm_step: everything of the same-MSM argument's prover (same_msm.py:73-143) that is NOT a group operation, as the kernel that sits
-// between two MSM launches -- k_fixed_msm over the CRS table for the A side, k_light_msm over the proof's light table for T and U, each
+// between two MSM launches -- k_table_msm over the CRS table for the A side (FixedPlan) and over the proof's light table (LightPlan) for T and U, each
 // with its k_fixed_finish -- so that the whole argument is one launch chain with one host wait.
 // Part of the single translation unit csrc/msm_gpu.hip (after kernels_ipa.h, whose label / op helpers it reuses).
 //
@@ -34,8 +34,8 @@ struct SmsmArgs {
   const uint32_t* pts_a;                     // k_fixed_finish's encodings of the launch over G:     [P][1 or 2][12 words]
   const uint32_t* pts_tu;                    // k_fixed_finish's encodings of the launch over T | U: [P][2 or 4][12 words]
   uint32_t* proof; uint32_t proof_words;     // [P][proof_words]: SameMSMProof.to_bytes order
-  uint32_t* tba; uint64_t* sca;              // the term arrays k_fixed_msm reads
-  uint32_t* tbl; uint64_t* scl;              // the term arrays k_light_msm reads
+  uint32_t* tba; uint64_t* sca;              // the term arrays k_table_msm<FixedPlan> reads
+  uint32_t* tbl; uint64_t* scl;              // the term arrays k_table_msm<LightPlan> reads
   const uint32_t* status_a; const uint32_t* status_tu;     // the status words of the two MSM launches before
   uint32_t* chain_status;                    // accumulated over the chain, read once at its end
   uint32_t* clocks;                          // [P][4]: lane 0's clock ticks (s_memtime) in the transcript | the inversions of gamma | whole steps that emit terms | steps counted

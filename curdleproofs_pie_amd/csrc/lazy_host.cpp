@@ -443,14 +443,14 @@ void cg1_glv_split(const uint8_t* scalar32, uint8_t* k1_16, uint8_t* k2_16, int*
   *neg1 = (int)o.neg1; *neg2 = (int)o.neg2;
 }
 
-// The signed 8-bit recoding of the fixed-base tables (csrc/fixed_digits.h: the function k_fixed_msm runs), one scalar: for the CPU tests.
+// The signed 8-bit recoding of the fixed-base tables (csrc/fixed_digits.h: the function k_table_msm<FixedPlan> runs), one scalar: for the CPU tests.
 void cg1_fixed_digits(const uint8_t* scalar32, int16_t* out32) {
   uint32_t k[8];
   memcpy(k, scalar32, 32);
   (void)cg1::fixed_digits(k, out32, 1);
 }
 
-// The signed narrow-window recoding of the light tables (csrc/light_digits.h: the function k_light_msm runs), one scalar: for the CPU tests.
+// The signed narrow-window recoding of the light tables (csrc/light_digits.h: the function k_table_msm<LightPlan> runs), one scalar: for the CPU tests.
 int cg1_light_digits(const uint8_t* scalar32, int16_t* out) {
   uint32_t k[8];
   memcpy(k, scalar32, 32);

@@ -122,7 +122,7 @@ class FixedBaseTable:
         return self.msm_many([(bases, scalars)])[0]
 
     def msm_many(self, jobs: Iterable[Tuple[Sequence[Base], Sequence[Scalar]]]) -> List[G1Point]:
-        """[sum_i scalars[i] * bases[i] for (bases, scalars) in jobs] as ONE launch chain (k_fixed_msm; k_light_msm for a LightTable).  bases: G1Point objects of the
+        """[sum_i scalars[i] * bases[i] for (bases, scalars) in jobs] as ONE launch chain (k_table_msm with the table's plan).  bases: G1Point objects of the
         table or indices into it, None = the table in order.  A result is certified in G1 only when every base it used was."""
         with _LOCK:
             if self._tab is None or not self._tab.handle or not self._ctx.handle:

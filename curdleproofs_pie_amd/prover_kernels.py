@@ -145,7 +145,7 @@ def ipa_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence
     enc = iter(points_to_compressed(pts))
     out: List[tuple] = []
     with table._ctx_lock():
-        if table._KIND != "fixed-base":                                  # a LightTable: its records are not what k_fixed_msm reads
+        if table._KIND != "fixed-base":                                  # a LightTable: its records are not what the chain's MSM kernel reads
             raise TypeError("the device chain of the inner-product argument runs over a FixedBaseTable")
         for lo in range(0, len(provers), N.IPA_MAX_PROVERS):             # (more provers than one chain carries: several calls)
             part, P = provers[lo: lo + N.IPA_MAX_PROVERS], len(provers[lo: lo + N.IPA_MAX_PROVERS])

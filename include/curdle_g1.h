@@ -106,7 +106,7 @@ void* cg1_ctx_stream(cg1_ctx* ctx);                                  /* the cont
  *   transcripts         "merlin_rows" (1: block program when the operation list fits), "merlin_sync" (1: lanes of a wave permute together),
  *                       "merlin_lanes" (1..64 transcripts per wave)
  *   verifier front-end  "fe_rows" (1: block program, 0: byte-level machine), "fe_timed" (shader-clock split of a launch), "fe_prio" (0..3)
- *   fixed-base tables   "fixed_slice" (terms per workgroup of k_fixed_msm, 1..128; 0: by the size of the call), "fixed_waves" (4, 8, 16 waves per
+ *   fixed-base tables   "fixed_slice" (terms per workgroup of k_table_msm, 1..128; 0: by the size of the call), "fixed_waves" (4, 8, 16 waves per
  *                       workgroup; 0: by the size of the call)
  * Unknown names and out-of-range values return CG1_ERR_ARG. */
 int  cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value);
@@ -553,7 +553,7 @@ void cg1_fixed_digits(const uint8_t scalar32[32], int16_t out[32]);
 /* ---- The inner-product argument PROVED on the device: IPA.new (ipa.py:75-153) after its blinders are drawn, for n_provers independent
  * provers of one vector length n in step, as ONE launch chain with one host wait (csrc/kernels_ipa.h, csrc/ipa_rounds.h).
  * The bases stay what they are -- entries of a cg1_fixed table -- and the round challenges fold into the scalars: per round one
- * k_fixed_msm launch of 4 MSMs of n / 2 (+ 1) terms per prover, one k_fixed_finish (the encodings, on the device) and one k_ipa_step
+ * k_table_msm launch of 4 MSMs of n / 2 (+ 1) terms per prover, one k_fixed_finish (the encodings, on the device) and one k_ipa_step
  * (the transcript over the prover's own state, gamma^-1, the folds, the next round's scalars): 1 + 3 (lg n + 1) launches in all.
  *   per prover p, host buffers:
  *     g_index[p n ..], g_prime_index[p n ..]   table indices of crs_G_vec / crs_G_prime_vec;  h_index[p]  that of crs_H (crs_H * beta is
@@ -632,8 +632,8 @@ int cg1_light_digits(const uint8_t scalar32[32], int16_t out[CG1_LIGHT_WINDOWS])
  * n_provers independent provers of one length n in step, as ONE launch chain with one host wait (csrc/kernels_same_msm.h,
  * csrc/same_msm_rounds.h).  All bases stay what they are and the round challenges fold into the scalars through one coefficient vector
  * per prover.  crs_G_vec are entries of a cg1_fixed table; vec_T | vec_U are per-proof points: the call builds ONE light table over all
- * provers' T and U (scratch kept with the cg1_fixed handle, regrown only when too small).  Per step two MSM launches -- k_fixed_msm for
- * the A side, k_light_msm for T and U --, their two k_fixed_finish and one k_smsm_step (the transcript over the prover's own state,
+ * provers' T and U (scratch kept with the cg1_fixed handle, regrown only when too small).  Per step two MSM launches of k_table_msm -- the fixed plan for
+ * the A side, the light plan for T and U --, their two k_fixed_finish and one k_smsm_step (the transcript over the prover's own state,
  * gamma^-1, the fold, the next terms): 3 + 5 (lg n + 1) launches in all.
  *   per prover p, host buffers:
  *     g_index[p n ..]     table indices of crs_G_vec

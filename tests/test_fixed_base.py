@@ -1,5 +1,5 @@
 """Fixed-base tables, the parts that run without a GPU: the signed 8-bit recoding the kernel computes (cg1_fixed_digits is compiled
-from the function k_fixed_msm runs, csrc/fixed_digits.h), the three symbol lists, and the no-GPU failure mode of the Python class."""
+from the function the kernel runs, csrc/fixed_digits.h), the three symbol lists, and the no-GPU failure mode of the Python class."""
 import ctypes
 import os
 import random

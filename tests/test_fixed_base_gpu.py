@@ -1,4 +1,4 @@
-"""Fixed-base tables and k_fixed_msm (csrc/kernels_fixed.h) against the CPU oracle, bit for bit.  Needs an MI355X.
+"""Fixed-base tables and k_table_msm's fixed plan (csrc/kernels_fixed.h) against the CPU oracle, bit for bit.  Needs an MI355X.
 
 Every expected value comes from the oracle (C.msm_bucket / O.g1_mul / O.g1_add), never from another path of the product: a table of
 133 oracle-made points at every term count, batches of uneven MSMs, the callers' skewed scalar patterns, identity / repeated /

@@ -1,5 +1,5 @@
 """Light tables, the parts that run without a GPU: the signed narrow-window recoding the kernel computes (cg1_light_digits is compiled
-from the function k_light_msm runs, csrc/light_digits.h), the symbol lists and limits, and the no-GPU failure mode of the Python class."""
+from the function the kernel runs, csrc/light_digits.h), the symbol lists and limits, and the no-GPU failure mode of the Python class."""
 import ctypes
 import os
 import random
@@ -100,7 +100,7 @@ def test_symbols_and_limits(native_lib):
     for macro, value in (("CG1_LIGHT_WINDOW_BITS", N.LIGHT_WINDOW_BITS), ("CG1_LIGHT_MAX_BASES", N.LIGHT_MAX_BASES),
                          ("CG1_LIGHT_MAX_MSMS", N.LIGHT_MAX_MSMS), ("CG1_LIGHT_MAX_TERMS", N.LIGHT_MAX_TERMS)):
         assert re.search(r"#define\s+%s\s+%d\b" % (macro, value), src), macro
-    # the kernels share k_fixed_msm's ticket words and slices; the prover's largest batch (64 provers, 2 n = 256 bases each) fits
+    # the two plans of k_table_msm share the ticket words and slices; the prover's largest batch (64 provers, 2 n = 256 bases each) fits
     assert N.LIGHT_MAX_MSMS <= N.FIXED_MAX_MSMS and N.LIGHT_MAX_TERMS <= N.FIXED_MAX_TERMS and N.LIGHT_MAX_BASES >= 64 * 256
     assert N.cg1_light_len(None) == 0 and N.cg1_light_bytes(None) == 0
     N.cg1_light_destroy(None)

@@ -1,4 +1,4 @@
-"""Light tables and k_light_msm (csrc/kernels_light.h) against the CPU oracle, bit for bit.  Needs an MI355X.
+"""Light tables and k_table_msm's light plan (csrc/kernels_light.h) against the CPU oracle, bit for bit.  Needs an MI355X.
 
 Every expected value comes from the oracle (C.msm_bucket / O.g1_mul / O.g1_add), never from another path of the product -- except the
 last two tests, which are about the two table classes agreeing and about the recorded rounds of the reference prover.  The tables are built once per module: 40 oracle-made points, and a 12-base table of
@@ -259,6 +259,28 @@ def test_refusals_write_nothing(native_lib, ctx, tab40, pts40):
     assert not N.cg1_light_create(ctx.handle, off, 1, ctypes.byref(st)) and st.value == N.ERR_NOT_ON_CURVE
 
 
+def test_fixed_and_light_tables_alternate_on_one_context(ctx, pts40):
+    """The two kinds share one kernel and one host layer: the context's sequence number and flag wait, and each handle's OWN ticket
+    words and staging block.  Host entries on a fixed and a light table over the same 8 points, turn and turn about -- 3 MSMs of 1, 5
+    and 0 terms -- first at the calls' own shape, then with 2 terms per workgroup (the 5-term MSM goes through the ticketed join)."""
+    pts = pts40[:8]
+    raw = b"".join(raw96(p) for p in pts)
+    fixed, light = ctx.fixed_table(raw, 8), ctx.light_table(raw, 8)
+    rng = random.Random(4008)
+    try:
+        for fixed_slice in (0, 2):
+            ctx.set_param("fixed_slice", fixed_slice)
+            for turn in range(4):
+                for kind, entry, tab in (("fixed", ctx.fixed_msm_host, fixed), ("light", ctx.light_msm_host, light)):
+                    idx = [rng.randrange(8) | (NEG if rng.random() < 0.3 else 0) for _ in range(6)]
+                    sc = [rng.randrange(O.R) for _ in range(6)]
+                    got = entry(tab, idx, s32(sc), [0, 1, 6, 6], compressed=True)
+                    assert got == [want48(pts, idx[:1], sc[:1]), want48(pts, idx[1:], sc[1:]), O.g1_compress(None)], (fixed_slice, turn, kind)
+    finally:
+        ctx.set_param("fixed_slice", 0)
+        fixed.free(); light.free()
+
+
 def test_light_class_equals_fixed_class(native_lib, pts40):
     from curdleproofs_pie_amd import G1Point, Scalar
     from curdleproofs_pie_amd.fixed_base import FixedBaseTable, LightTable
@@ -298,7 +320,7 @@ def test_light_class_equals_fixed_class(native_lib, pts40):
 
 def test_ipa_rounds_over_a_light_table_and_the_device_chain_refuses_one(native_lib):
     """The host-driven halving rounds take either class (the reference prover's recorded rounds, byte for byte); the device chain of
-    the inner-product argument reads k_fixed_msm's records and refuses a LightTable before anything reaches the library."""
+    the inner-product argument reads the fixed plan's records and refuses a LightTable before anything reaches the library."""
     from curdleproofs_pie_amd.fixed_base import LightTable
     from curdleproofs_pie_amd.prover_kernels import ipa_prove_device_many, ipa_rounds
     from curdleproofs_pie_amd.py_arkworks_bls12381 import G1Point, Scalar

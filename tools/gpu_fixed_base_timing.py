@@ -10,7 +10,7 @@ ONE process on one GPU: the median of --reps (>= 20) repetitions after a warm-up
   ipa_rounds_many at n = 128, eight provers      table=                 no table
   table build time and nbytes for 133 bases      reported               --
 
-`--shapes` instead times the launch shapes of k_fixed_msm against each other on the IPA-round calls ("fixed_waves" x "fixed_slice"
+`--shapes` instead times the launch shapes of k_table_msm against each other on the IPA-round calls ("fixed_waves" x "fixed_slice"
 through cg1_ctx_set_param; 0 / 0 = the library's own choice): the measurement behind the rule in csrc/capi_fixed.h.
 
 One run prints one JSON line.  `--summarize a.json b.json c.json` reads three runs and prints the table with the verdict per shape:
@@ -61,7 +61,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--summarize", nargs="+")
-    ap.add_argument("--shapes", action="store_true", help="A/B of k_fixed_msm's launch shapes on the IPA-round calls")
+    ap.add_argument("--shapes", action="store_true", help="A/B of k_table_msm's launch shapes on the IPA-round calls")
     a = ap.parse_args()
     if a.summarize:
         return summarize(a.summarize)
