@@ -526,37 +526,33 @@ class Context:
         """cg1_light_msm_device: device arrays in, affine96 and / or compressed48 left in device buffers."""
         self._table_msm_device(cg1_light_msm_device, tab, d_term_base, d_scalars32, d_offsets, n_msm, n_terms, max_terms, d_out_affine96, d_out_comp48)
 
+    def _chain_prove_device(self, fn, proof_bytes, tab: "FixedTable", n: int, n_provers: int, head, tail, states208: bytes, want_clocks: bool):
+        """A device prover's C entry fn(ctx, table, n, n_provers, *head, *tail, states, proofs out, clocks out) with its state, proof and
+        clock buffers; head: index lists (as uint32 arrays), tail: byte arguments.  -> (proofs, states) as bytes [, clocks]."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        st = ctypes.create_string_buffer(bytes(states208), 208 * n_provers)
+        out = ctypes.create_string_buffer(max(1, int(proof_bytes(n)) * n_provers))
+        ck = (ctypes.c_uint32 * (4 * max(1, n_provers)))() if want_clocks else None
+        self.check(fn(self.handle, tab.handle, n, n_provers, *((ctypes.c_uint32 * max(1, len(v)))(*v) for v in head), *tail, st, out, ck))
+        return (out.raw, st.raw, list(ck)) if want_clocks else (out.raw, st.raw)
+
     def ipa_prove_device(self, tab: "FixedTable", n: int, n_provers: int, g_index, g_prime_index, h_index, g_prime_coeffs32, cd48: bytes, z32: bytes,
                          vec_c32: bytes, vec_d32: bytes, vec_r_c32: bytes, vec_r_d32: bytes, states208: bytes, want_clocks: bool = False):
         """cg1_ipa_prove_device: n_provers inner-product arguments of length n over the table, one launch chain, one wait.
         -> (proofs, states) as bytes [, clocks]; raises (check) on a refusal, and then nothing the caller holds has changed."""
-        if not tab.handle:
-            raise NativeError("the fixed-base table is closed")
         assert len(g_index) == len(g_prime_index) == n * n_provers and len(h_index) == n_provers
-        gi = (ctypes.c_uint32 * max(1, len(g_index)))(*g_index)
-        gpi = (ctypes.c_uint32 * max(1, len(g_prime_index)))(*g_prime_index)
-        hi = (ctypes.c_uint32 * max(1, n_provers))(*h_index)
-        st = ctypes.create_string_buffer(bytes(states208), 208 * n_provers)
-        out = ctypes.create_string_buffer(max(1, int(cg1_ipa_proof_bytes(n)) * n_provers))
-        ck = (ctypes.c_uint32 * (4 * max(1, n_provers)))() if want_clocks else None
-        self.check(cg1_ipa_prove_device(self.handle, tab.handle, n, n_provers, gi, gpi, hi, g_prime_coeffs32, cd48, z32, vec_c32, vec_d32, vec_r_c32, vec_r_d32,
-                                        st, out, ck))
-        return (out.raw, st.raw, list(ck)) if want_clocks else (out.raw, st.raw)
+        return self._chain_prove_device(cg1_ipa_prove_device, cg1_ipa_proof_bytes, tab, n, n_provers, (g_index, g_prime_index, h_index),
+                                        (g_prime_coeffs32, cd48, z32, vec_c32, vec_d32, vec_r_c32, vec_r_d32), states208, want_clocks)
 
     def same_msm_prove_device(self, tab: "FixedTable", n: int, n_provers: int, g_index, azz48: bytes, tu_affine96: bytes, vec_x32: bytes, vec_r32: bytes,
                               states208: bytes, want_clocks: bool = False):
         """cg1_same_msm_prove_device: n_provers same-MSM arguments of length n, crs_G_vec from the table and vec_T | vec_U as affine96
         records (a light table is built over them inside the call), one launch chain, one wait.
         -> (proofs, states) as bytes [, clocks]; raises (check) on a refusal, and then nothing the caller holds has changed."""
-        if not tab.handle:
-            raise NativeError("the fixed-base table is closed")
         assert len(g_index) == n * n_provers and len(azz48) == 144 * n_provers and len(tu_affine96) == 192 * n * n_provers
-        gi = (ctypes.c_uint32 * max(1, len(g_index)))(*g_index)
-        st = ctypes.create_string_buffer(bytes(states208), 208 * n_provers)
-        out = ctypes.create_string_buffer(max(1, int(cg1_same_msm_proof_bytes(n)) * n_provers))
-        ck = (ctypes.c_uint32 * (4 * max(1, n_provers)))() if want_clocks else None
-        self.check(cg1_same_msm_prove_device(self.handle, tab.handle, n, n_provers, gi, azz48, tu_affine96, vec_x32, vec_r32, st, out, ck))
-        return (out.raw, st.raw, list(ck)) if want_clocks else (out.raw, st.raw)
+        return self._chain_prove_device(cg1_same_msm_prove_device, cg1_same_msm_proof_bytes, tab, n, n_provers, (g_index,),
+                                        (azz48, tu_affine96, vec_x32, vec_r32), states208, want_clocks)
 
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""

@@ -38,9 +38,8 @@ struct cg1_table {
 
 struct cg1_fixed : cg1_table {
   cg1::PreparedPoint* d_tab = nullptr;                      // n_bases x GEN_ENTRIES records (build_fixed_table)
-  uint8_t* h_ipa = nullptr; uint8_t* d_ipa = nullptr; size_t cap_ipa = 0;      // cg1_ipa_prove_device's staging block and its device twin (capi_ipa.h)
-  uint8_t* h_smsm = nullptr; uint8_t* d_smsm = nullptr; size_t cap_smsm = 0;   // cg1_same_msm_prove_device's staging block and its device twin (capi_same_msm.h)
-  cg1_light* smsm_light = nullptr; size_t cap_smsm_bases = 0;                  // ... and its light table over the provers' T | U: regrown only when too small
+  uint8_t* h_chain = nullptr; uint8_t* d_chain = nullptr; size_t cap_chain = 0;      // the device provers' staging block and its device twin, re-laid-out by every call (capi_chain.h)
+  cg1_light* smsm_light = nullptr; size_t cap_smsm_bases = 0;                  // cg1_same_msm_prove_device's light table over the provers' T | U: regrown only when too small
 };
 
 namespace {
@@ -223,10 +222,8 @@ void cg1_fixed_destroy(cg1_fixed* t) {
   (void)hipSetDevice(t->device);
   if (t->d_tab) (void)hipFree(t->d_tab);
   t->release();
-  if (t->d_ipa) (void)hipFree(t->d_ipa);
-  if (t->h_ipa) (void)hipHostFree(t->h_ipa);
-  if (t->d_smsm) (void)hipFree(t->d_smsm);
-  if (t->h_smsm) (void)hipHostFree(t->h_smsm);
+  if (t->d_chain) (void)hipFree(t->d_chain);
+  if (t->h_chain) (void)hipHostFree(t->h_chain);
   if (t->smsm_light) cg1_light_destroy(t->smsm_light);
   delete t;
 }

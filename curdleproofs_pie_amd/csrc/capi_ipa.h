@@ -3,84 +3,47 @@
 #pragma once
 
 namespace {
-struct IpaLayout {                           // byte offsets into the staging block (pinned host memory and its device twin: the same layout)
+struct IpaLayout : ChainLayout {
   size_t gi, gpi, hi, coef, vc, vd, rc, rd, trow, offs1, offsr;       // uploaded
-  size_t status, clocks, states, proof;                               // uploaded (zeros | zeros | the callers' states | --) and read back
   size_t c, d, kG, kGp, kH, chal, pts, tb, sc;                        // device only
-  size_t up_end, down_begin, down_end, total;
 };
 IpaLayout ipa_layout(size_t n, size_t P, size_t proof_bytes) {
   IpaLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
-  L.gi = take(P * n * 4); L.gpi = take(P * n * 4); L.hi = take(P * 4);
-  L.coef = take(P * n * 32); L.vc = take(P * n * 32); L.vd = take(P * n * 32); L.rc = take(P * n * 32); L.rd = take(P * n * 32);
-  L.trow = take(P * cg1ipa::IPA_TROW); L.offs1 = take((2 * P + 1) * 4); L.offsr = take((4 * P + 1) * 4);
-  L.down_begin = o;
-  L.status = take(16); L.clocks = take(P * 16); L.states = take(P * 208);
-  L.up_end = o;
-  L.proof = take(P * proof_bytes);
-  L.down_end = o;
-  L.c = take(P * n * 32); L.d = take(P * n * 32); L.kG = take(P * n * 32); L.kGp = take(P * n * 32); L.kH = take(P * 32);
-  L.chal = take(P * 64); L.pts = take(P * 192);
-  L.tb = take(P * (2 * n + 2) * 4); L.sc = take(P * (2 * n + 2) * 32);
-  L.total = o;
+  L.gi = L.take(P * n * 4); L.gpi = L.take(P * n * 4); L.hi = L.take(P * 4);
+  L.coef = L.take(P * n * 32); L.vc = L.take(P * n * 32); L.vd = L.take(P * n * 32); L.rc = L.take(P * n * 32); L.rd = L.take(P * n * 32);
+  L.trow = L.take(P * cg1ipa::IPA_TROW); L.offs1 = L.take((2 * P + 1) * 4); L.offsr = L.take((4 * P + 1) * 4);
+  L.shared(P, proof_bytes);
+  L.c = L.take(P * n * 32); L.d = L.take(P * n * 32); L.kG = L.take(P * n * 32); L.kGp = L.take(P * n * 32); L.kH = L.take(P * 32);
+  L.chal = L.take(P * 64); L.pts = L.take(P * 192);
+  L.tb = L.take(P * (2 * n + 2) * 4); L.sc = L.take(P * (2 * n + 2) * 32);
   return L;
-}
-bool ipa_scalars_canonical(const uint8_t* s, size_t count) {
-  for (size_t i = 0; i < count; ++i) {
-    uint32_t w[8];
-    memcpy(w, s + 32 * i, 32);
-    if (!cg1::fixed_scalar_below_r(w)) return false;
-  }
-  return true;
 }
 }  // namespace
 
 extern "C" {
-size_t cg1_ipa_proof_bytes(size_t n) {
-  if (n < 2 || (n & (n - 1)) != 0) return 0;
-  size_t lg = 0;
-  while (((size_t)1 << lg) < n) ++lg;
-  return (2 + 4 * lg) * 48 + 64;
-}
+size_t cg1_ipa_proof_bytes(size_t n) { return chain_pow2(n) ? (2 + 4 * chain_lg(n)) * 48 + 64 : 0; }
 
 int cg1_ipa_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_provers, const uint32_t* g_index, const uint32_t* g_prime_index,
                          const uint32_t* h_index, const uint8_t* g_prime_coeffs32, const uint8_t* cd48, const uint8_t* z32, const uint8_t* vec_c32,
                          const uint8_t* vec_d32, const uint8_t* vec_r_c32, const uint8_t* vec_r_d32, uint8_t* states208, uint8_t* out_proofs,
                          uint32_t* out_clocks) {
+  static const char* const who = "cg1_ipa_prove_device";
+  static const char* const hashed[] = {"C", "D"};
   if (!ctx) return CG1_ERR_HIP;
   if (n_provers == 0) return CG1_OK;
   // ---- refusals: the whole call, before anything is written
-  if (!t || t->device != ctx->device || !g_index || !g_prime_index || !h_index || !cd48 || !z32 || !vec_c32 || !vec_d32 || !vec_r_c32 || !vec_r_d32 ||
-      !states208 || !out_proofs) { snprintf(ctx->err, sizeof ctx->err, "cg1_ipa_prove_device: bad argument"); return CG1_ERR_ARG; }
-  if (n < 2 || (n & (n - 1)) != 0 || n > CG1_IPA_MAX_N) {
-    snprintf(ctx->err, sizeof ctx->err, "cg1_ipa_prove_device: n must be a power of two in 2 .. %d", CG1_IPA_MAX_N); return CG1_ERR_ARG; }
-  if (n_provers > CG1_IPA_MAX_PROVERS) {
-    snprintf(ctx->err, sizeof ctx->err, "cg1_ipa_prove_device: more than %d provers in one call", CG1_IPA_MAX_PROVERS); return CG1_ERR_ARG; }
   const size_t P = n_provers;
-  for (size_t i = 0; i < P * n; ++i)
-    if (g_index[i] >= t->n_bases || g_prime_index[i] >= t->n_bases) { snprintf(ctx->err, sizeof ctx->err, "cg1_ipa_prove_device: a base index is outside the table"); return CG1_ERR_ARG; }
-  for (size_t i = 0; i < P; ++i)
-    if (h_index[i] >= t->n_bases) { snprintf(ctx->err, sizeof ctx->err, "cg1_ipa_prove_device: a base index is outside the table"); return CG1_ERR_ARG; }
-  if (!ipa_scalars_canonical(z32, P) || !ipa_scalars_canonical(vec_c32, P * n) || !ipa_scalars_canonical(vec_d32, P * n) ||
-      !ipa_scalars_canonical(vec_r_c32, P * n) || !ipa_scalars_canonical(vec_r_d32, P * n) || (g_prime_coeffs32 && !ipa_scalars_canonical(g_prime_coeffs32, P * n))) {
-    snprintf(ctx->err, sizeof ctx->err, "cg1_ipa_prove_device: a scalar is >= r: scalar32 must be a canonical Fr element"); return CG1_ERR_ENCODING; }
-  for (size_t i = 0; i < 2 * P; ++i) {
-    int inf = 0;
-    const int rc = cg1_validate_compressed(cd48 + 48 * i, &inf);
-    if (rc != CG1_OK) { snprintf(ctx->err, sizeof ctx->err, "cg1_ipa_prove_device: prover %zu: %s does not decode (status %d)", i / 2, (i & 1) ? "D" : "C", rc); return rc; }
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  ctx->pend.active = false;
-  size_t lg = 0;
-  while (((size_t)1 << lg) < n) ++lg;
-  const size_t pb = cg1_ipa_proof_bytes(n);
+  if (const int rc = chain_check_shape(ctx, who, t, g_index && g_prime_index && h_index && cd48 && z32 && vec_c32 && vec_d32 && vec_r_c32 && vec_r_d32 &&
+                                       states208 && out_proofs, n, CG1_IPA_MAX_N)) return rc;
+  if (P > CG1_IPA_MAX_PROVERS) { snprintf(ctx->err, sizeof ctx->err, "%s: more than %d provers in one call", who, CG1_IPA_MAX_PROVERS); return CG1_ERR_ARG; }
+  if (const int rc = chain_check_indices(ctx, who, t, {{g_index, P * n}, {g_prime_index, P * n}, {h_index, P}})) return rc;
+  if (const int rc = chain_check_scalars(ctx, who, {{z32, P}, {vec_c32, P * n}, {vec_d32, P * n}, {vec_r_c32, P * n}, {vec_r_d32, P * n}, {g_prime_coeffs32, P * n}})) return rc;
+  if (const int rc = chain_check_points(ctx, who, cd48, P, 2, hashed, nullptr)) return rc;
+  const size_t lg = chain_lg(n), pb = cg1_ipa_proof_bytes(n);
   const IpaLayout L = ipa_layout(n, P, pb);
-  { const int rc = cg1::grow_pinned_pair(ctx, t->h_ipa, nullptr, t->d_ipa, t->cap_ipa, L.total, L.total, hipHostMallocDefault); if (rc) return rc; }
   // ---- stage the inputs: one block, one copy
-  uint8_t* H = t->h_ipa;
-  uint8_t* D = t->d_ipa;
+  uint8_t* H; uint8_t* D;
+  if (const int rc = chain_stage(ctx, t, L, P, states208, H, D)) return rc;
   memcpy(H + L.gi, g_index, P * n * 4); memcpy(H + L.gpi, g_prime_index, P * n * 4); memcpy(H + L.hi, h_index, P * 4);
   if (g_prime_coeffs32) memcpy(H + L.coef, g_prime_coeffs32, P * n * 32);
   memcpy(H + L.vc, vec_c32, P * n * 32); memcpy(H + L.vd, vec_d32, P * n * 32);
@@ -95,8 +58,6 @@ int cg1_ipa_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_provers,
     cg1ipa::step1_offsets((uint32_t)n, (uint32_t)(p * cg1ipa::step1_terms((uint32_t)n)), offs1 + 2 * p);
     cg1ipa::round_offsets((uint32_t)n, (uint32_t)(p * cg1ipa::round_terms((uint32_t)n)), offsr + 4 * p);
   }
-  memset(H + L.status, 0, 16); memset(H + L.clocks, 0, P * 16);
-  memcpy(H + L.states, states208, P * 208);
   HIPCHK(hipMemcpyAsync(D, H, L.up_end, hipMemcpyHostToDevice, ctx->stream));
 
   cg1ipa::IpaArgs a;
@@ -125,13 +86,6 @@ int cg1_ipa_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_provers,
     if (rc) return rc;
     hipLaunchKernelGGL(cg1ipa::k_ipa_step, dim3(Pn), dim3(cg1ipa::IPA_THREADS), 0, ctx->stream, a, cg1ipa::IPA_ROUND, nn >> r, r);
   }
-  HIPCHK(hipMemcpyAsync(H + L.down_begin, D + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));                 // the one wait
-  HIPCHK(hipGetLastError());
-  { const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
-  memcpy(out_proofs, H + L.proof, P * pb);
-  memcpy(states208, H + L.states, P * 208);
-  if (out_clocks) memcpy(out_clocks, H + L.clocks, P * 16);
-  return CG1_OK;
+  return chain_finish(ctx, t, L, P, pb, states208, out_proofs, out_clocks);
 }
 }  // extern "C"

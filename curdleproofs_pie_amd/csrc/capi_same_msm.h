@@ -4,78 +4,51 @@
 #pragma once
 
 namespace {
-struct SmsmLayout {                          // byte offsets into the staging block (pinned host memory and its device twin: the same layout)
-  size_t gi, vx, vr, tu96, offs_a1, offs_a2, offs_l2, offs_l4;        // uploaded
-  size_t status, clocks, states, proof;                               // uploaded (zeros | zeros | the states after the host's two lists | --) and read back
+struct SmsmLayout : ChainLayout {
+  size_t gi, vx, vr, tu96, offs_a1, offs_a2, offs_l2, offs_l4;        // uploaded (the states: as they stand after the host's two lists)
   size_t x, k, row, chal, pts_a, pts_tu, tba, sca, tbl, scl;          // device only
-  size_t up_end, down_begin, down_end, total;
 };
 SmsmLayout smsm_layout(size_t n, size_t P, size_t proof_bytes) {
   SmsmLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 63) & ~(size_t)63; return at; };
-  L.gi = take(P * n * 4); L.vx = take(P * n * 32); L.vr = take(P * n * 32); L.tu96 = take(P * 2 * n * 96);
-  L.offs_a1 = take((P + 1) * 4); L.offs_a2 = take((2 * P + 1) * 4); L.offs_l2 = take((2 * P + 1) * 4); L.offs_l4 = take((4 * P + 1) * 4);
-  L.down_begin = o;
-  L.status = take(16); L.clocks = take(P * 16); L.states = take(P * 208);
-  L.up_end = o;
-  L.proof = take(P * proof_bytes);
-  L.down_end = o;
-  L.x = take(P * n * 32); L.k = take(P * n * 32); L.row = take(P * cg1smsm::SMSM_ROW); L.chal = take(P * 32);
-  L.pts_a = take(P * 2 * 48); L.pts_tu = take(P * 4 * 48);
-  L.tba = take(P * n * 4); L.sca = take(P * n * 32); L.tbl = take(P * 2 * n * 4); L.scl = take(P * 2 * n * 32);
-  L.total = o;
+  L.gi = L.take(P * n * 4); L.vx = L.take(P * n * 32); L.vr = L.take(P * n * 32); L.tu96 = L.take(P * 2 * n * 96);
+  L.offs_a1 = L.take((P + 1) * 4); L.offs_a2 = L.take((2 * P + 1) * 4); L.offs_l2 = L.take((2 * P + 1) * 4); L.offs_l4 = L.take((4 * P + 1) * 4);
+  L.shared(P, proof_bytes);
+  L.x = L.take(P * n * 32); L.k = L.take(P * n * 32); L.row = L.take(P * cg1smsm::SMSM_ROW); L.chal = L.take(P * 32);
+  L.pts_a = L.take(P * 2 * 48); L.pts_tu = L.take(P * 4 * 48);
+  L.tba = L.take(P * n * 4); L.sca = L.take(P * n * 32); L.tbl = L.take(P * 2 * n * 4); L.scl = L.take(P * 2 * n * 32);
   return L;
 }
 }  // namespace
 
 extern "C" {
-size_t cg1_same_msm_proof_bytes(size_t n) {
-  if (n < 2 || (n & (n - 1)) != 0) return 0;
-  size_t lg = 0;
-  while (((size_t)1 << lg) < n) ++lg;
-  return (3 + 6 * lg) * 48 + 32;
-}
+size_t cg1_same_msm_proof_bytes(size_t n) { return chain_pow2(n) ? (3 + 6 * chain_lg(n)) * 48 + 32 : 0; }
 
 int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_provers, const uint32_t* g_index, const uint8_t* azz48,
                               const uint8_t* tu_affine96, const uint8_t* vec_x32, const uint8_t* vec_r32, uint8_t* states208, uint8_t* out_proofs,
                               uint32_t* out_clocks) {
   static const char* const who = "cg1_same_msm_prove_device";
+  static const char* const hashed[] = {"A", "Z_t", "Z_u"};
   if (!ctx) return CG1_ERR_HIP;
   if (n_provers == 0) return CG1_OK;
   // ---- refusals: the whole call, before anything is written
-  if (!t || t->device != ctx->device || !g_index || !azz48 || !tu_affine96 || !vec_x32 || !vec_r32 || !states208 || !out_proofs) {
-    snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
-  if (n < 2 || (n & (n - 1)) != 0 || n > CG1_SAME_MSM_MAX_N) {
-    snprintf(ctx->err, sizeof ctx->err, "%s: n must be a power of two in 2 .. %d", who, CG1_SAME_MSM_MAX_N); return CG1_ERR_ARG; }
-  if (n_provers > CG1_SAME_MSM_MAX_PROVERS || n_provers * 2 * n > CG1_LIGHT_MAX_BASES) {
+  const size_t P = n_provers;
+  if (const int rc = chain_check_shape(ctx, who, t, g_index && azz48 && tu_affine96 && vec_x32 && vec_r32 && states208 && out_proofs, n, CG1_SAME_MSM_MAX_N)) return rc;
+  if (P > CG1_SAME_MSM_MAX_PROVERS || P * 2 * n > CG1_LIGHT_MAX_BASES) {
     snprintf(ctx->err, sizeof ctx->err, "%s: more than %d provers, or more than %d bases T | U, in one call", who, CG1_SAME_MSM_MAX_PROVERS, CG1_LIGHT_MAX_BASES);
     return CG1_ERR_ARG; }
-  const size_t P = n_provers;
-  for (size_t i = 0; i < P * n; ++i)
-    if (g_index[i] >= t->n_bases) { snprintf(ctx->err, sizeof ctx->err, "%s: a base index is outside the table", who); return CG1_ERR_ARG; }
-  if (!ipa_scalars_canonical(vec_x32, P * n) || !ipa_scalars_canonical(vec_r32, P * n)) {
-    snprintf(ctx->err, sizeof ctx->err, "%s: a scalar is >= r: scalar32 must be a canonical Fr element", who); return CG1_ERR_ENCODING; }
+  if (const int rc = chain_check_indices(ctx, who, t, {{g_index, P * n}})) return rc;
+  if (const int rc = chain_check_scalars(ctx, who, {{vec_x32, P * n}, {vec_r32, P * n}})) return rc;
   std::vector<uint8_t> head(P * 144), blobs(P * 2 * n * CG1_POINT_BYTES), tu48(P * 2 * n * 48);
-  for (size_t i = 0; i < 3 * P; ++i) {                      // A, Z_t, Z_u: only hashed, as re-serialised (util.py:27-32)
-    int inf = 0;
-    const int rc = cg1_validate_compressed(azz48 + 48 * i, &inf);
-    if (rc != CG1_OK) { snprintf(ctx->err, sizeof ctx->err, "%s: prover %zu: %s does not decode (status %d)", who, i / 3, i % 3 == 0 ? "A" : i % 3 == 1 ? "Z_t" : "Z_u", rc); return rc; }
-    memcpy(&head[48 * i], azz48 + 48 * i, 48);
-    if (inf) { memset(&head[48 * i], 0, 48); head[48 * i] = 0xC0; }
-  }
+  if (const int rc = chain_check_points(ctx, who, azz48, P, 3, hashed, head.data())) return rc;       // A, Z_t, Z_u: only hashed, as re-serialised
   for (size_t b = 0; b < P * 2 * n; ++b) {                  // canonical coordinates, on the curve (or the all-zero identity record)
     const int rc = cg1_from_affine96(&blobs[b * CG1_POINT_BYTES], tu_affine96 + 96 * b, 1);
     if (rc != CG1_OK) { snprintf(ctx->err, sizeof ctx->err, "%s: prover %zu: entry %zu of vec_T | vec_U is not a curve point (status %d)", who, b / (2 * n), b % (2 * n), rc); return rc; }
   }
   cg1_batch_compress(tu48.data(), blobs.data(), P * 2 * n);
-  HIPCHK(hipSetDevice(ctx->device));
-  ctx->pend.active = false;
-  size_t lg = 0;
-  while (((size_t)1 << lg) < n) ++lg;
-  const size_t pb = cg1_same_msm_proof_bytes(n);
+  const size_t lg = chain_lg(n), pb = cg1_same_msm_proof_bytes(n);
   const SmsmLayout L = smsm_layout(n, P, pb);
-  { const int rc = cg1::grow_pinned_pair(ctx, t->h_smsm, nullptr, t->d_smsm, t->cap_smsm, L.total, L.total, hipHostMallocDefault); if (rc) return rc; }
+  uint8_t* H; uint8_t* D;
+  if (const int rc = chain_stage(ctx, t, L, P, states208, H, D)) return rc;
   if (P * 2 * n > t->cap_smsm_bases) {                      // the light table's records: kept with the handle, regrown only when too small
     if (t->smsm_light) cg1_light_destroy(t->smsm_light);
     t->smsm_light = new cg1_light();
@@ -88,8 +61,6 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
   lt->n_bases = P * 2 * n;
   // ---- stage the inputs: one block, one copy.  The first two same_msm_step1 lists ([A, Z_t, Z_u] and vec_T + vec_U, 2 n encodings:
   // ~74 Keccak permutations at n = 128) depend on nothing the device computes: absorbed here, into the states that go up.
-  uint8_t* H = t->h_smsm;
-  uint8_t* D = t->d_smsm;
   memcpy(H + L.gi, g_index, P * n * 4);
   memcpy(H + L.vx, vec_x32, P * n * 32); memcpy(H + L.vr, vec_r32, P * n * 32);
   memcpy(H + L.tu96, tu_affine96, P * 2 * n * 96);
@@ -101,8 +72,6 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
   for (uint32_t i = 0; i <= Pn; ++i) oa1[i] = i * nn;
   for (uint32_t i = 0; i <= 2 * Pn; ++i) { oa2[i] = i * hh; ol2[i] = i * nn; }
   for (uint32_t i = 0; i <= 4 * Pn; ++i) ol4[i] = i * hh;
-  memset(H + L.status, 0, 16); memset(H + L.clocks, 0, P * 16);
-  memcpy(H + L.states, states208, P * 208);
   static const uint8_t step1[] = "same_msm_step1";
   for (size_t p = 0; p < P; ++p) {
     cg1_merlin_append_list(H + L.states + 208 * p, step1, 14, &head[144 * p], 48, 3);
@@ -157,13 +126,6 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
     { const int rc = msms(2, hh, (const uint32_t*)(D + L.offs_a2), (const uint32_t*)(D + L.offs_l4)); if (rc) return rc; }
     hipLaunchKernelGGL(cg1smsm::k_smsm_step, dim3(Pn), dim3(cg1smsm::SMSM_THREADS), 0, ctx->stream, a, cg1smsm::SMSM_ROUND, nn >> r, r);
   }
-  HIPCHK(hipMemcpyAsync(H + L.down_begin, D + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));                 // the one wait
-  HIPCHK(hipGetLastError());
-  { const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
-  memcpy(out_proofs, H + L.proof, P * pb);
-  memcpy(states208, H + L.states, P * 208);
-  if (out_clocks) memcpy(out_clocks, H + L.clocks, P * 16);
-  return CG1_OK;
+  return chain_finish(ctx, t, L, P, pb, states208, out_proofs, out_clocks);
 }
 }  // extern "C"

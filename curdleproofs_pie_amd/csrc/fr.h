@@ -196,6 +196,55 @@ CG1FR_HD fr fr_inv(const fr& a) {
   return acc;
 }
 
+// 1 / a by Kaliski's almost-inverse (0 -> 0): a binary extended Euclid whose loop only shifts, adds and subtracts -- no reduction mod r
+// inside -- and leaves a^-1 2^k (r bits <= k <= 2 r bits); the power of two goes away with two Montgomery products at the end.
+// The round's challenge is public, so the data-dependent loop leaks nothing, and as ONE dependent chain on one lane its ~400 steps of
+// word arithmetic take 0.12 ms against 0.50 for the 380 Montgomery products of a^(r-2) (fr_inv): DESIGN.md section 10 has
+// both, timed.  Input and output in Montgomery form: with A = a R the loop gives A^-1 2^k = a^-1 R^-1 2^k, and
+// a^-1 R = that * 2^(512 - k) = mont(that, mont(2^(512 - k), R^2)).
+CG1FR_HD fr fr_inv_binary(const fr& a) {
+  if (fr_is_zero(a)) return a;
+  uint64_t u[4] = {cg1::H_FR[0], cg1::H_FR[1], cg1::H_FR[2], cg1::H_FR[3]};
+  uint64_t w[4] = {a.l[0], a.l[1], a.l[2], a.l[3]};
+  uint64_t x[4] = {0, 0, 0, 0}, y[4] = {1, 0, 0, 0};       // x, y < 2 r < 2^256 throughout
+  uint32_t k = 0;
+  while ((w[0] | w[1] | w[2] | w[3]) != 0) {
+    const bool u_even = !(u[0] & 1), w_even = !(w[0] & 1);
+    bool gt = false;                                        // u > w
+    for (int i = 3; i >= 0; --i) if (u[i] != w[i]) { gt = u[i] > w[i]; break; }
+    // which of the four steps: halve u | halve w | u <- (u - w) / 2 | w <- (w - u) / 2; the other side's cofactor doubles.
+    // Two explicit calls, not a pointer chosen at run time: the four numbers stay in registers on the device.
+    const bool on_u = u_even || (!w_even && gt), odd = !u_even && !w_even;
+    auto step = [odd](uint64_t (&big)[4], const uint64_t (&small)[4], uint64_t (&acc)[4], uint64_t (&dbl)[4]) {
+      if (odd) {
+        u128 bw = 0, cy = 0;
+        for (int i = 0; i < 4; ++i) {
+          const u128 dlt = (u128)big[i] - small[i] - bw; big[i] = (uint64_t)dlt; bw = (dlt >> 64) & 1;
+          cy += (u128)acc[i] + dbl[i]; acc[i] = (uint64_t)cy; cy >>= 64;
+        }
+      }
+      for (int i = 0; i < 3; ++i) big[i] = (big[i] >> 1) | (big[i + 1] << 63);
+      big[3] >>= 1;
+      for (int i = 3; i > 0; --i) dbl[i] = (dbl[i] << 1) | (dbl[i - 1] >> 63);
+      dbl[0] <<= 1;
+    };
+    if (on_u) step(u, w, x, y);
+    else step(w, u, y, x);
+    ++k;
+  }
+  if (geq_r(x)) sub_r(x);
+  fr inv{{x[0], x[1], x[2], x[3]}};
+  inv = fr_neg(inv);                                        // r - x = A^-1 2^k mod r, 255 <= k <= 510
+  uint32_t e = 512u - k;                                    // 2 .. 257
+  fr two_e{{0, 0, 0, 0}};
+  const uint32_t eb = e > 254u ? 254u : e;                  // 2^e as a plain integer below r, the rest by doublings
+  two_e.l[eb >> 6] = (uint64_t)1 << (eb & 63u);
+  const fr r2{{cg1::H_FR_R2[0], cg1::H_FR_R2[1], cg1::H_FR_R2[2], cg1::H_FR_R2[3]}};
+  fr out = fr_mul(inv, fr_mul(two_e, r2));
+  for (; e > eb; --e) out = fr_add(out, out);
+  return out;
+}
+
 // in-place inversion of n NON-ZERO elements with one field inversion (host only)
 static inline void fr_batch_inv(fr* v, size_t n) {
   if (n == 0) return;

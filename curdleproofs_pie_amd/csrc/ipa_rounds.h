@@ -15,10 +15,12 @@
 // kGp starts at the caller's G' coefficients (grand_prod.py:64-71 as scalars) or 1; kH is beta: crs_H * beta is never a point.
 // A prover's terms are contiguous: [L_C: h + 1][L_D: h][R_C: h + 1][R_D: h] with h = n0 / 2, every round.
 #pragma once
-#include "fr.h"
+#include "chain_rounds.h"
 
 namespace cg1ipa {
 using cg1fr::fr;
+using cg1chain::load_le;
+using cg1chain::put_term;
 
 struct View {                                // one prover's state (Montgomery form) and its table indices
   fr* c; fr* d;                              // the current vectors: positions [0, len)
@@ -36,20 +38,6 @@ CG1FR_HD void round_offsets(uint32_t n0, uint32_t first, uint32_t* o) {
   o[0] = first; o[1] = o[0] + h + 1u; o[2] = o[1] + h; o[3] = o[2] + h + 1u; o[4] = o[3] + h;
 }
 CG1FR_HD void step1_offsets(uint32_t n0, uint32_t first, uint32_t* o) { o[0] = first; o[1] = first + n0; o[2] = first + 2u * n0; }
-
-// term `slot` of the prover's term arrays (tb: table index, bit 31 = negated base -- never set here; sc: 4 words per canonical scalar)
-CG1FR_HD void put_term(uint32_t* tb, uint64_t* sc, uint32_t slot, uint32_t base, const fr& k) {
-  uint64_t w[4];
-  cg1fr::fr_to_le32(k, reinterpret_cast<uint8_t*>(w));
-  tb[slot] = base;
-  for (int i = 0; i < 4; ++i) sc[4u * slot + i] = w[i];
-}
-CG1FR_HD fr load_le(const uint64_t* src) {    // a canonical scalar (validated by the caller) -> Montgomery form
-  uint64_t w[4] = {src[0], src[1], src[2], src[3]};
-  fr v;
-  (void)cg1fr::fr_from_le32(reinterpret_cast<const uint8_t*>(w), v);
-  return v;
-}
 
 // step 1, lane j < n0:  B_c = MSM(G, r_c),  B_d = MSM(G', r_d)  (ipa.py:97-98)
 CG1FR_HD void step1_term(const View& v, uint32_t j, const fr& rc, const fr& rd, uint32_t* tb, uint64_t* sc) {
@@ -88,55 +76,6 @@ CG1FR_HD void fold_elem(const View& v, uint32_t half, uint32_t t, const fr& gamm
     v.c[i] = cg1fr::fr_add(v.c[i], cg1fr::fr_mul(gamma_inv, v.c[half + i]));
     v.d[i] = cg1fr::fr_add(v.d[i], cg1fr::fr_mul(gamma, v.d[half + i]));
   }
-}
-
-// 1 / a by Kaliski's almost-inverse (0 -> 0): a binary extended Euclid whose loop only shifts, adds and subtracts -- no reduction mod r
-// inside -- and leaves a^-1 2^k (r bits <= k <= 2 r bits); the power of two goes away with two Montgomery products at the end.
-// The round's challenge is public, so the data-dependent loop leaks nothing, and as ONE dependent chain on one lane its ~400 steps of
-// word arithmetic take 0.12 ms against 0.50 for the 380 Montgomery products of a^(r-2) (cg1fr::fr_inv): DESIGN.md section 10 has
-// both, timed.  Input and output in Montgomery form: with A = a R the loop gives A^-1 2^k = a^-1 R^-1 2^k, and
-// a^-1 R = that * 2^(512 - k) = mont(that, mont(2^(512 - k), R^2)).
-CG1FR_HD fr fr_inv_binary(const fr& a) {
-  if (cg1fr::fr_is_zero(a)) return a;
-  uint64_t u[4] = {cg1::H_FR[0], cg1::H_FR[1], cg1::H_FR[2], cg1::H_FR[3]};
-  uint64_t w[4] = {a.l[0], a.l[1], a.l[2], a.l[3]};
-  uint64_t x[4] = {0, 0, 0, 0}, y[4] = {1, 0, 0, 0};       // x, y < 2 r < 2^256 throughout
-  uint32_t k = 0;
-  while ((w[0] | w[1] | w[2] | w[3]) != 0) {
-    const bool u_even = !(u[0] & 1), w_even = !(w[0] & 1);
-    bool gt = false;                                        // u > w
-    for (int i = 3; i >= 0; --i) if (u[i] != w[i]) { gt = u[i] > w[i]; break; }
-    // which of the four steps: halve u | halve w | u <- (u - w) / 2 | w <- (w - u) / 2; the other side's cofactor doubles.
-    // Two explicit calls, not a pointer chosen at run time: the four numbers stay in registers on the device.
-    const bool on_u = u_even || (!w_even && gt), odd = !u_even && !w_even;
-    auto step = [odd](uint64_t (&big)[4], const uint64_t (&small)[4], uint64_t (&acc)[4], uint64_t (&dbl)[4]) {
-      if (odd) {
-        cg1fr::u128 bw = 0, cy = 0;
-        for (int i = 0; i < 4; ++i) {
-          const cg1fr::u128 dlt = (cg1fr::u128)big[i] - small[i] - bw; big[i] = (uint64_t)dlt; bw = (dlt >> 64) & 1;
-          cy += (cg1fr::u128)acc[i] + dbl[i]; acc[i] = (uint64_t)cy; cy >>= 64;
-        }
-      }
-      for (int i = 0; i < 3; ++i) big[i] = (big[i] >> 1) | (big[i + 1] << 63);
-      big[3] >>= 1;
-      for (int i = 3; i > 0; --i) dbl[i] = (dbl[i] << 1) | (dbl[i - 1] >> 63);
-      dbl[0] <<= 1;
-    };
-    if (on_u) step(u, w, x, y);
-    else step(w, u, y, x);
-    ++k;
-  }
-  if (cg1fr::geq_r(x)) cg1fr::sub_r(x);
-  fr inv{{x[0], x[1], x[2], x[3]}};
-  inv = cg1fr::fr_neg(inv);                                 // r - x = A^-1 2^k mod r, 255 <= k <= 510
-  uint32_t e = 512u - k;                                    // 2 .. 257
-  fr two_e{{0, 0, 0, 0}};
-  const uint32_t eb = e > 254u ? 254u : e;                  // 2^e as a plain integer below r, the rest by doublings
-  two_e.l[eb >> 6] = (uint64_t)1 << (eb & 63u);
-  const fr r2{{cg1::H_FR_R2[0], cg1::H_FR_R2[1], cg1::H_FR_R2[2], cg1::H_FR_R2[3]}};
-  fr out = cg1fr::fr_mul(inv, cg1fr::fr_mul(two_e, r2));
-  for (; e > eb; --e) out = cg1fr::fr_add(out, out);
-  return out;
 }
 
 }  // namespace cg1ipa

@@ -217,8 +217,7 @@ __global__ void __launch_bounds__(LANES) k_shuffle_front_end(const uint8_t* __re
   m.labels = lds_labels;
   m.consts = consts;
   for (int i = 0; i < 50; ++i) m.w[i * LANES] = reinterpret_cast<const uint32_t*>(init_state)[i];
-  m.pos = init_state[200]; m.pos_begin = init_state[201]; m.cur_flags = init_state[202];
-  m.k = 0; m.ph = 0; m.i = 0; m.hdr = 0; m.stage = 0; m.k_loaded = 0xffffffffu; m.rec = make_uint4(0, 0, 0, 0);
+  m.reset(init_state);
   __syncthreads();
   const size_t me = live ? t : 0;
   const uint8_t* row = wire + me * (size_t)pr.L * 48u;

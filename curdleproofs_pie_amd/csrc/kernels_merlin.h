@@ -268,6 +268,11 @@ struct Machine {
   uint4 rec;                                 // the operation record of op `k_loaded`
   uint32_t k_loaded;
 
+  // the cursor at the start of a program, over a 208-byte state: its three position bytes follow the 200 sponge bytes
+  __device__ __forceinline__ void reset(const uint8_t* st) {
+    pos = st[200]; pos_begin = st[201]; cur_flags = st[202];
+    k = 0; ph = 0; i = 0; hdr = 0; stage = 0; k_loaded = 0xffffffffu; rec = make_uint4(0, 0, 0, 0);
+  }
   __device__ __forceinline__ void xor_byte(uint32_t p, uint32_t v) { w[(p >> 2) * LANES] ^= v << ((p & 3u) * 8u); }
   __device__ __forceinline__ void xor_u32(uint32_t p, uint32_t v) {          // four bytes at byte position p (p + 4 <= 200)
     const uint32_t sh = (p & 3u) * 8u;
@@ -448,8 +453,7 @@ __global__ void __launch_bounds__(LANES) k_merlin_batch_sync(const uint8_t* __re
   m.labels = lds_labels;
   m.consts = nullptr;
   for (int i = 0; i < 50; ++i) m.w[i * LANES] = reinterpret_cast<const uint32_t*>(init_state)[i];
-  m.pos = init_state[200]; m.pos_begin = init_state[201]; m.cur_flags = init_state[202];
-  m.k = 0; m.ph = 0; m.i = 0; m.hdr = 0; m.stage = 0; m.k_loaded = 0xffffffffu; m.rec = make_uint4(0, 0, 0, 0);
+  m.reset(init_state);
   __syncthreads();
   const uint8_t* row = data + (size_t)(live ? t : 0) * data_stride;
   uint8_t* orow = out + (size_t)(live ? t : 0) * out_stride;

@@ -1,7 +1,7 @@
 // k_smsm_step: everything of the same-MSM argument's prover (same_msm.py:73-143) that is NOT a group operation, as the kernel that sits
 // between two MSM launches -- k_table_msm over the CRS table for the A side (FixedPlan) and over the proof's light table (LightPlan) for T and U, each
 // with its k_fixed_finish -- so that the whole argument is one launch chain with one host wait.
-// Part of the single translation unit csrc/msm_gpu.hip (after kernels_ipa.h, whose label / op helpers it reuses).
+// Part of the single translation unit csrc/msm_gpu.hip (after kernels_merlin.h and kernels_fixed.h).
 //
 // One workgroup per prover, three phases (the host enqueues  begin, table build | MSMs finish stepB | (MSMs finish round) x lg n):
 //   begin    the caller's canonical scalars -> Montgomery state (x, k = 1) and the terms of B_a, B_t, B_u
@@ -10,14 +10,13 @@
 //            same_msm_alpha; x <- r + alpha x; the terms of round 0
 //   round    the six encodings into the proof; the transcript absorbs same_msm_loop [L_A, L_T, L_U, R_A, R_T, R_U] and draws
 //            same_msm_gamma; gamma^-1 (fr_inv_binary); the fold; then the terms of the next round, or x_final after the last one
-// The schedule and the folds are same_msm_rounds.h (shared with the host); the transcript runs on lane 0 as in k_ipa_step.
+// The schedule and the folds are same_msm_rounds.h (shared with the host); the transcript, the status merge and the clocks are the step
+// skeleton of kernels_chain.h.
 #pragma once
 #include "same_msm_rounds.h"
+#include "kernels_chain.h"
 
 namespace cg1smsm {
-using cg1merlin::COp;
-using cg1merlin::LANES;
-using cg1merlin::Machine;
 
 constexpr uint32_t SMSM_THREADS = 256;
 constexpr uint32_t SMSM_ROW = 288;           // a prover's data row: the six (or three) encodings of a step in the transcript's order
@@ -42,12 +41,7 @@ struct SmsmArgs {
 };
 
 __global__ void __launch_bounds__(SMSM_THREADS) k_smsm_step(SmsmArgs a, uint32_t phase, uint32_t len, uint32_t round) {
-  __shared__ uint32_t s_sponge[52 * LANES];
-  __shared__ uint32_t s_drawn[8 * LANES];
-  __shared__ uint32_t s_labels[4 * 8];
-  __shared__ uint32_t s_inf[12];
-  __shared__ COp s_ops[8];
-  __shared__ fr s_ch[2];
+  __shared__ cg1chain::StepLds s;                // (its fifth label slot is unused here)
 
   const uint32_t tid = threadIdx.x, p = blockIdx.x, n0 = a.n0, h = n0 / 2u;
   const unsigned long long t_in = __builtin_amdgcn_s_memtime();
@@ -82,82 +76,43 @@ __global__ void __launch_bounds__(SMSM_THREADS) k_smsm_step(SmsmArgs a, uint32_t
     reinterpret_cast<uint32_t*>(row)[tid] = val;
   }
   // ---- the transcript, on lane 0
-  uint8_t* st = a.states + (size_t)p * 208;
-  if (tid < 50u) s_sponge[tid * LANES] = reinterpret_cast<const uint32_t*>(st)[tid];
   if (tid == 64u) {
-    cg1ipa::ipa_label(s_labels, "same_msm_step1", 14); cg1ipa::ipa_label(s_labels + 8, "same_msm_alpha", 14);
-    cg1ipa::ipa_label(s_labels + 16, "same_msm_loop", 13); cg1ipa::ipa_label(s_labels + 24, "same_msm_gamma", 14);
-    s_inf[0] = 0xC0u;                                                   // the canonical encoding of the identity: C0 00 .. 00
-    for (int j = 1; j < 12; ++j) s_inf[j] = 0u;
+    using cg1chain::label; using cg1chain::op;
+    label(s.labels, "same_msm_step1", 14); label(s.labels + 8, "same_msm_alpha", 14);
+    label(s.labels + 16, "same_msm_loop", 13); label(s.labels + 24, "same_msm_gamma", 14);
     if (phase == SMSM_STEPB) {
-      for (uint32_t q = 0; q < 3u; ++q) s_ops[q] = cg1ipa::ipa_op(cg1merlin::OP_APPEND_POINT, 0, 14, 48, 48u * q, 0);
-      s_ops[3] = cg1ipa::ipa_op(cg1merlin::OP_CHALLENGE_SCALAR, 1, 14, 32, 0, 0);
+      for (uint32_t q = 0; q < 3u; ++q) s.ops[q] = op(cg1merlin::OP_APPEND_POINT, 0, 14, 48, 48u * q, 0);
+      s.ops[3] = op(cg1merlin::OP_CHALLENGE_SCALAR, 1, 14, 32, 0, 0);   // alpha
     } else {
-      for (uint32_t q = 0; q < 6u; ++q) s_ops[q] = cg1ipa::ipa_op(cg1merlin::OP_APPEND_POINT, 2, 13, 48, 48u * q, 0);
-      s_ops[6] = cg1ipa::ipa_op(cg1merlin::OP_CHALLENGE_SCALAR, 3, 14, 32, 0, 0);
+      for (uint32_t q = 0; q < 6u; ++q) s.ops[q] = op(cg1merlin::OP_APPEND_POINT, 2, 13, 48, 48u * q, 0);
+      s.ops[6] = op(cg1merlin::OP_CHALLENGE_SCALAR, 3, 14, 32, 0, 0);   // gamma
     }
   }
-  __threadfence_block();
-  __syncthreads();
-  if (tid == 0u) {
-    const uint32_t bad = a.status_a[0] | a.status_tu[0];
-    if (bad != 0u) atomicOr(a.chain_status, bad);
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    Machine m;
-    m.w = s_sponge; m.drawn = s_drawn; m.labels = s_labels; m.consts = reinterpret_cast<const uint8_t*>(s_inf);
-    m.pos = st[200]; m.pos_begin = st[201]; m.cur_flags = st[202];
-    m.k = 0; m.ph = 0; m.i = 0; m.hdr = 0; m.stage = 0; m.k_loaded = 0xffffffffu; m.rec = make_uint4(0, 0, 0, 0);
-    uint8_t* orow = a.chal + (size_t)p * 32;
-    const uint32_t nops = phase == SMSM_STEPB ? 4u : 7u;
-    bool done = false;
-    for (;;) {
-      bool blocked = false;
-      if (!m.advance(s_ops, nops, row, orow, done, blocked)) break;
-      cg1merlin::keccak_words(m.w);
-      m.pos = 0; m.pos_begin = 0;
-    }
-    st[200] = (uint8_t)m.pos; st[201] = (uint8_t)m.pos_begin; st[202] = (uint8_t)m.cur_flags;
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    const fr ch = load_le(reinterpret_cast<const uint64_t*>(orow));     // alpha, or gamma
-    s_ch[0] = ch;
-    if (phase == SMSM_ROUND) s_ch[1] = cg1ipa::ipa_inv_binary(ch);
-    const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-    if (a.clocks) {
-      uint32_t* ck = a.clocks + 4u * p;
-      ck[0] += (uint32_t)(t1 - t0);
-      if (phase == SMSM_ROUND) ck[1] += (uint32_t)(t2 - t1);
-      ck[3] += 1u;
-    }
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (tid < 50u) reinterpret_cast<uint32_t*>(st)[tid] = s_sponge[tid * LANES];
+  const bool first = phase == SMSM_STEPB;
+  uint32_t* ck = a.clocks ? a.clocks + 4u * p : nullptr;
+  cg1chain::transcript_step(s, a.states + (size_t)p * 208, first ? 4u : 7u, row, a.chal + (size_t)p * 32, a.status_a, a.status_tu, a.chain_status,
+                            first ? cg1chain::INV_NONE : cg1chain::INV_BINARY, nullptr, ck);
 
   // ---- the Fr step
   uint32_t cur = len;                                                   // the vector's length once this step is done
   if (phase == SMSM_STEPB) {
-    const fr alpha = s_ch[0];
+    const fr alpha = s.ch[0];
     for (uint32_t j = tid; j < n0; j += SMSM_THREADS) blind_elem(v, j, alpha, load_le(vr + 4u * j));
   } else {
-    const fr gamma = s_ch[0], gamma_inv = s_ch[1];
+    const fr gamma = s.ch[0], gamma_inv = s.ch[1];
     cur = len / 2u;
     for (uint32_t t = tid; t < h; t += SMSM_THREADS) fold_elem(v, cur, t, gamma, gamma_inv);
   }
   __threadfence_block();
   __syncthreads();
   if (cur == 1u) {                                                      // after the last fold: x_final
-    if (tid == 0u) {
-      uint64_t w[4];
-      cg1fr::fr_to_le32(v.x[0], reinterpret_cast<uint8_t*>(w));
-      uint32_t* dst = proof + (3u + 6u * a.lg) * 12u;
-      for (int k = 0; k < 4; ++k) { dst[2 * k] = (uint32_t)w[k]; dst[2 * k + 1] = (uint32_t)(w[k] >> 32); }
-    }
+    if (tid == 0u) cg1chain::put_scalar(proof + (3u + 6u * a.lg) * 12u, v.x[0]);
     return;
   }
   // ---- the terms of the next round
   const uint32_t half = cur / 2u;
   for (uint32_t t = tid; t < h; t += SMSM_THREADS) round_term(v, half, t, tba, sca, tbl, scl);
-  if (tid == 0u && a.clocks) a.clocks[4u * p + 2u] += (uint32_t)(__builtin_amdgcn_s_memtime() - t_in);
+  if (tid == 0u) cg1chain::step_clock(ck, t_in);
 }
 
 }  // namespace cg1smsm

@@ -506,7 +506,7 @@ int cg1_ipa_round_emulate(int op, size_t n0, size_t len, uint8_t* c32, uint8_t* 
     cg1ipa::round_offsets((uint32_t)n0, 0, out_offsets);
     if (challenge32) {
       if (cg1fr::fr_is_zero(ch[0])) return CG1_ERR_ARG;
-      const fr ginv = cg1ipa::fr_inv_binary(ch[0]);
+      const fr ginv = cg1fr::fr_inv_binary(ch[0]);
       if (!cg1fr::fr_eq(ginv, cg1fr::fr_inv(ch[0]))) return CG1_ERR_ARG;          // the two inversions agree, or the test hears of it
       for (uint32_t t = 0; t < h; ++t) cg1ipa::fold_elem(v, half, t, ch[0], ginv);
       len = half;
@@ -566,7 +566,7 @@ int cg1_same_msm_round_emulate(int op, size_t n0, size_t len, uint8_t* x32, uint
     merge(6, h);
     if (challenge32) {
       if (cg1fr::fr_is_zero(ch[0])) return CG1_ERR_ARG;
-      const fr ginv = cg1ipa::fr_inv_binary(ch[0]);
+      const fr ginv = cg1fr::fr_inv_binary(ch[0]);
       if (!cg1fr::fr_eq(ginv, cg1fr::fr_inv(ch[0]))) return CG1_ERR_ARG;          // the two inversions agree, or the test hears of it
       for (uint32_t t = 0; t < h; ++t) cg1smsm::fold_elem(v, half, t, ch[0], ginv);
       len = half;

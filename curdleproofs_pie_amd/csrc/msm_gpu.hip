@@ -72,8 +72,9 @@ int pick_window(size_t n);
 #include "kernels_merlin.h"
 #include "kernels_frontend.h"
 #include "kernels_opening.h"
-#include "kernels_ipa.h"           // k_ipa_step: the Fr and transcript half of the inner-product argument's prover
-#include "kernels_same_msm.h"      // k_smsm_step: the Fr and transcript half of the same-MSM argument's prover
+#include "kernels_chain.h"         // the step skeleton of the device provers: lane-0 transcript, status merge, inversion, clocks
+#include "kernels_ipa.h"           // k_ipa_step: the inner-product argument's phases, op tables and Fr steps over that skeleton
+#include "kernels_same_msm.h"      // k_smsm_step: the same-MSM argument's
 #include "host_context.h"          // Ctx: streams, helper threads, scratch buffers
 #include "host_chains.h"           // planner + launch chains: regime A, k_msm_small, regime B
 #include "capi_core_msm.h"         // cg1_* : host operators, context, memory, parameters, MSM entry points
@@ -84,6 +85,7 @@ int pick_window(size_t n);
 #include "capi_frontend.h"         // the shuffle verifier front-end on the device
 #include "capi_rows_probes.h"      // scalar rows, compression, synthetic scalars, probes
 #include "capi_fixed.h"            // resident fixed-base tables: cg1_fixed_*
+#include "capi_chain.h"            // the host layer of a device prover's launch chain: layout, shared refusals, staging, tail
 #include "capi_ipa.h"              // the inner-product argument proved on the device: cg1_ipa_prove_device
 #include "capi_light.h"            // light tables of variable bases: cg1_light_*
 #include "capi_same_msm.h"         // the same-MSM argument proved on the device: cg1_same_msm_prove_device

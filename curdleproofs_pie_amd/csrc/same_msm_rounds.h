@@ -16,12 +16,12 @@
 //     the TU array [L_T: h][L_U: h][R_T: h][R_U: h]  indices into the light table: T[j] at tu + j, U[j] at tu + n0 + j
 // and for the step before the rounds, B_a = MSM(G, r) | B_t = MSM(T, r), B_u = MSM(U, r):  [B_a: n0]  and  [B_t: n0][B_u: n0].
 #pragma once
-#include "ipa_rounds.h"
+#include "chain_rounds.h"
 
 namespace cg1smsm {
 using cg1fr::fr;
-using cg1ipa::load_le;
-using cg1ipa::put_term;
+using cg1chain::load_le;
+using cg1chain::put_term;
 
 struct View {                                // one prover's state (Montgomery form) and its table indices
   fr* x;                                     // the current vector: positions [0, len)

@@ -18,10 +18,11 @@ replays inputs recorded from the reference prover and compares every L / R point
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Callable, List, Sequence, Tuple
 
 from .msm_accumulator import batch_mul, batch_mul_same_scalar, compute_MSM, compute_MSM_batch
-from .py_arkworks_bls12381 import CURVE_ORDER, G1Point, Scalar
+from .py_arkworks_bls12381 import CURVE_ORDER, G1Point, Scalar, pack_scalars
 from .util import random_scalar
 
 N_BLINDERS = 4                                                          # curdleproofs.py:24
@@ -112,6 +113,49 @@ def ipa_rounds(crs_G_vec: Sequence[G1Point], crs_G_prime_vec: Sequence[G1Point],
     return ipa_rounds_many([(crs_G_vec, crs_G_prime_vec, H, vec_c, vec_d, G_prime_coeffs, H_coeff)], [next_gamma], table=table)[0]
 
 
+def _chain_provers(provers: Sequence[tuple], transcripts: Sequence, vec_at: int, what: str, max_n: int):
+    """The head of a *_prove_device_many call: -> (the provers as tuples, their vector length n = len(provers[0][vec_at]); 0 for none)."""
+    provers = [tuple(pr) for pr in provers]
+    if len(provers) != len(transcripts):
+        raise ValueError("one transcript per prover")
+    n = len(provers[0][vec_at]) if provers else 0
+    if provers and (n < 2 or n & (n - 1) or n > max_n):
+        raise ValueError(f"the vectors of {what} argument have a power-of-two length in 2 .. {max_n}, not {n}")
+    return provers, n
+
+
+def _pack32(vals: Sequence[Scalar]):
+    b = ctypes.create_string_buffer(32 * max(1, len(vals)))
+    pack_scalars(vals, ctypes.addressof(b), len(vals))
+    return b
+
+
+def _chain_prove(table, provers: Sequence[tuple], transcripts: Sequence, n: int, step: int, wrong_table: str, prove, n_points: int, n_vecs: int,
+                 n_scalars: int) -> List[tuple]:
+    """The frame of a *_prove_device_many call: under the table's context lock, `step` provers per chain (more provers than one chain
+    carries: several calls), prove(lo, part, states) -> (proofs, new states) with the transcripts' states packed and moved back, and each
+    proof's bytes cut into n_points points, n_vecs vectors of lg n points and n_scalars trailing scalars."""
+    from . import _native as N
+
+    S, lg = N.MERLIN_STATE_BYTES, n.bit_length() - 1
+    out: List[tuple] = []
+    with table._ctx_lock():
+        if table._KIND != "fixed-base":                                  # a LightTable: its records are not what the chain's MSM kernel reads
+            raise TypeError(wrong_table)
+        for lo in range(0, len(provers), step):
+            part, ts = provers[lo: lo + step], transcripts[lo: lo + step]
+            proofs, new_states = prove(lo, part, b"".join(bytes(t.strobe._st.raw[:S]) for t in ts))
+            pb = len(proofs) // len(part)
+            for i, t in enumerate(ts):
+                ctypes.memmove(t.strobe._st, new_states[S * i: S * i + S], S)
+                raw = proofs[pb * i: pb * i + pb]
+                P48 = [G1Point.from_compressed_bytes_unchecked(raw[48 * j: 48 * j + 48]) for j in range(n_points + n_vecs * lg)]
+                vecs = [P48[n_points + q * lg: n_points + (q + 1) * lg] for q in range(n_vecs)]
+                tail = raw[pb - 32 * n_scalars:]
+                out.append((*P48[:n_points], *vecs, *(Scalar.from_le_bytes(tail[32 * k: 32 * k + 32]) for k in range(n_scalars))))
+    return out
+
+
 def ipa_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence) -> List[tuple]:
     """IPA.new (ipa.py:75-153) after its blinder draw, for SEVERAL independent provers of one vector length in step, proved ON THE DEVICE:
     one launch chain (csrc/kernels_ipa.h), one wait -- the MSMs over the resident `table` (a fixed_base.FixedBaseTable), the
@@ -123,59 +167,38 @@ def ipa_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence
     transcripts[p]: that prover's CurdleproofsTranscript, advanced to the state after the last ipa_gamma -- the caller goes on exactly
     where the reference would.  -> per prover (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final), the fields of IPA.
     A refused call (ValueError: n not a power of two >= 2; NativeError: a scalar >= r, an undecodable C or D) changes nothing."""
-    import ctypes
-
     from . import _native as N
-    from .py_arkworks_bls12381 import pack_scalars, points_to_compressed
+    from .py_arkworks_bls12381 import points_to_compressed
 
-    provers = [tuple(pr) for pr in provers]
-    if len(provers) != len(transcripts):
-        raise ValueError("one transcript per prover")
+    provers, n = _chain_provers(provers, transcripts, 6, "an inner-product", N.IPA_MAX_N)
     if not provers:
         return []
-    n = len(provers[0][6])
-    if n < 2 or n & (n - 1) or n > N.IPA_MAX_N:
-        raise ValueError(f"the vectors of an inner-product argument have a power-of-two length in 2 .. {N.IPA_MAX_N}, not {n}")
     if any(not (len(pr[0]) == len(pr[1]) == len(pr[6]) == len(pr[7]) == len(pr[8]) == len(pr[9]) == n) for pr in provers):
         raise ValueError("provers in step share one vector length")
     coeffs = [pr[10] if len(pr) > 10 else None for pr in provers]
     if any(k is not None and len(k) != n for k in coeffs):
         raise ValueError("G_prime_coeffs has one entry per base")
-    pts = [x for pr in provers for x in pr[3:5] if type(x) is G1Point]
-    enc = iter(points_to_compressed(pts))
-    out: List[tuple] = []
-    with table._ctx_lock():
-        if table._KIND != "fixed-base":                                  # a LightTable: its records are not what the chain's MSM kernel reads
-            raise TypeError("the device chain of the inner-product argument runs over a FixedBaseTable")
-        for lo in range(0, len(provers), N.IPA_MAX_PROVERS):             # (more provers than one chain carries: several calls)
-            part, P = provers[lo: lo + N.IPA_MAX_PROVERS], len(provers[lo: lo + N.IPA_MAX_PROVERS])
-            gi, gpi, hi, cd, flat = [], [], [], [], [[] for _ in range(6)]
-            for pr, k in zip(part, coeffs[lo: lo + P]):
-                gi.extend(table._indices(pr[0], n)); gpi.extend(table._indices(pr[1], n)); hi.extend(table._indices([pr[2]], 1))
-                cd.extend(bytes(x) if type(x) is not G1Point else next(enc) for x in pr[3:5])
-                if any(len(e) != 48 for e in cd[-2:]):
-                    raise ValueError("C and D are G1Points or 48-byte encodings")
-                flat[0].append(pr[5])
-                for dst, src in zip(flat[1:5], pr[6:10]):
-                    dst.extend(src)
-                if any(c is not None for c in coeffs[lo: lo + P]):
-                    flat[5].extend(k if k is not None else [1] * n)
-            bufs = []
-            for vals in flat:
-                b = ctypes.create_string_buffer(32 * max(1, len(vals)))
-                pack_scalars(vals, ctypes.addressof(b), len(vals))
-                bufs.append(b)
-            states = b"".join(bytes(t.strobe._st.raw[:N.MERLIN_STATE_BYTES]) for t in transcripts[lo: lo + P])
-            proofs, new_states = table._ctx.ipa_prove_device(table._tab, n, P, gi, gpi, hi, bufs[5] if flat[5] else None, b"".join(cd), bufs[0], bufs[1],
-                                                             bufs[2], bufs[3], bufs[4], states)
-            lg, pb, S = n.bit_length() - 1, len(proofs) // P, N.MERLIN_STATE_BYTES
-            for i, t in enumerate(transcripts[lo: lo + P]):
-                ctypes.memmove(t.strobe._st, new_states[S * i: S * i + S], S)
-                raw = proofs[pb * i: pb * i + pb]
-                P48 = [G1Point.from_compressed_bytes_unchecked(raw[48 * j: 48 * j + 48]) for j in range(2 + 4 * lg)]
-                vecs = [P48[2 + q * lg: 2 + (q + 1) * lg] for q in range(4)]
-                out.append((P48[0], P48[1], *vecs, Scalar.from_le_bytes(raw[pb - 64: pb - 32]), Scalar.from_le_bytes(raw[pb - 32:])))
-    return out
+    enc = iter(points_to_compressed([x for pr in provers for x in pr[3:5] if type(x) is G1Point]))
+
+    def prove(lo, part, states):
+        P = len(part)
+        gi, gpi, hi, cd, flat = [], [], [], [], [[] for _ in range(6)]
+        for pr, k in zip(part, coeffs[lo: lo + P]):
+            gi.extend(table._indices(pr[0], n)); gpi.extend(table._indices(pr[1], n)); hi.extend(table._indices([pr[2]], 1))
+            cd.extend(bytes(x) if type(x) is not G1Point else next(enc) for x in pr[3:5])
+            if any(len(e) != 48 for e in cd[-2:]):
+                raise ValueError("C and D are G1Points or 48-byte encodings")
+            flat[0].append(pr[5])
+            for dst, src in zip(flat[1:5], pr[6:10]):
+                dst.extend(src)
+            if any(c is not None for c in coeffs[lo: lo + P]):
+                flat[5].extend(k if k is not None else [1] * n)
+        bufs = [_pack32(vals) for vals in flat]
+        return table._ctx.ipa_prove_device(table._tab, n, P, gi, gpi, hi, bufs[5] if flat[5] else None, b"".join(cd), bufs[0], bufs[1], bufs[2], bufs[3],
+                                           bufs[4], states)
+
+    return _chain_prove(table, provers, transcripts, n, N.IPA_MAX_PROVERS, "the device chain of the inner-product argument runs over a FixedBaseTable",
+                        prove, 2, 4, 2)
 
 
 def ipa_prove_device(table, crs_G_vec, crs_G_prime_vec, crs_H, C, D, z: Scalar, vec_c: Sequence[Scalar], vec_d: Sequence[Scalar],
@@ -242,55 +265,31 @@ def same_msm_prove_device_many(table, provers: Sequence[tuple], transcripts: Seq
     transcripts[p]: that prover's CurdleproofsTranscript, advanced to the state after the last same_msm_gamma.
     -> per prover (B_a, B_t, B_u, vec_L_A, vec_L_T, vec_L_U, vec_R_A, vec_R_T, vec_R_U, x_final), the fields of SameMSMProof.
     A refused call (ValueError: n not a power of two >= 2; NativeError: a scalar >= r, an undecodable A, Z_t or Z_u) changes nothing."""
-    import ctypes
-
     from . import _native as N
-    from .py_arkworks_bls12381 import pack_scalars, points_to_affine96, points_to_compressed
+    from .py_arkworks_bls12381 import points_to_affine96, points_to_compressed
 
-    provers = [tuple(pr) for pr in provers]
-    if len(provers) != len(transcripts):
-        raise ValueError("one transcript per prover")
+    provers, n = _chain_provers(provers, transcripts, 6, "a same-MSM", N.SAME_MSM_MAX_N)
     if not provers:
         return []
-    n = len(provers[0][6])
-    if n < 2 or n & (n - 1) or n > N.SAME_MSM_MAX_N:
-        raise ValueError(f"the vectors of a same-MSM argument have a power-of-two length in 2 .. {N.SAME_MSM_MAX_N}, not {n}")
     if any(not (len(pr[0]) == len(pr[4]) == len(pr[5]) == len(pr[6]) == len(pr[7]) == n) for pr in provers):
         raise ValueError("provers in step share one vector length")
     if any(type(x) is not G1Point for pr in provers for x in list(pr[4]) + list(pr[5])):
         raise TypeError("vec_T and vec_U are G1Points")
     enc = iter(points_to_compressed([x for pr in provers for x in pr[1:4] if type(x) is G1Point]))
-    step = min(N.SAME_MSM_MAX_PROVERS, N.LIGHT_MAX_BASES // (2 * n))     # (more provers than one chain carries: several calls)
-    out: List[tuple] = []
-    with table._ctx_lock():
-        if table._KIND != "fixed-base":
-            raise TypeError("the device chain of the same-MSM argument takes crs_G_vec from a FixedBaseTable")
-        for lo in range(0, len(provers), step):
-            part = provers[lo: lo + step]
-            P = len(part)
-            gi, azz, tu, xs, rs = [], [], [], [], []
-            for pr in part:
-                gi.extend(table._indices(pr[0], n))
-                azz.extend(bytes(x) if type(x) is not G1Point else next(enc) for x in pr[1:4])
-                if any(len(e) != 48 for e in azz[-3:]):
-                    raise ValueError("A, Z_t and Z_u are G1Points or 48-byte encodings")
-                tu.extend(pr[4]); tu.extend(pr[5])
-                xs.extend(pr[6]); rs.extend(pr[7])
-            bufs = []
-            for vals in (xs, rs):
-                b = ctypes.create_string_buffer(32 * len(vals))
-                pack_scalars(vals, ctypes.addressof(b), len(vals))
-                bufs.append(b)
-            states = b"".join(bytes(t.strobe._st.raw[:N.MERLIN_STATE_BYTES]) for t in transcripts[lo: lo + P])
-            proofs, new_states = table._ctx.same_msm_prove_device(table._tab, n, P, gi, b"".join(azz), bytes(points_to_affine96(tu)), bufs[0], bufs[1], states)
-            lg, pb, S = n.bit_length() - 1, len(proofs) // P, N.MERLIN_STATE_BYTES
-            for i, t in enumerate(transcripts[lo: lo + P]):
-                ctypes.memmove(t.strobe._st, new_states[S * i: S * i + S], S)
-                raw = proofs[pb * i: pb * i + pb]
-                P48 = [G1Point.from_compressed_bytes_unchecked(raw[48 * j: 48 * j + 48]) for j in range(3 + 6 * lg)]
-                vecs = [P48[3 + q * lg: 3 + (q + 1) * lg] for q in range(6)]
-                out.append((P48[0], P48[1], P48[2], *vecs, Scalar.from_le_bytes(raw[pb - 32:])))
-    return out
+
+    def prove(lo, part, states):
+        gi, azz, tu, xs, rs = [], [], [], [], []
+        for pr in part:
+            gi.extend(table._indices(pr[0], n))
+            azz.extend(bytes(x) if type(x) is not G1Point else next(enc) for x in pr[1:4])
+            if any(len(e) != 48 for e in azz[-3:]):
+                raise ValueError("A, Z_t and Z_u are G1Points or 48-byte encodings")
+            tu.extend(pr[4]); tu.extend(pr[5])
+            xs.extend(pr[6]); rs.extend(pr[7])
+        return table._ctx.same_msm_prove_device(table._tab, n, len(part), gi, b"".join(azz), bytes(points_to_affine96(tu)), _pack32(xs), _pack32(rs), states)
+
+    return _chain_prove(table, provers, transcripts, n, min(N.SAME_MSM_MAX_PROVERS, N.LIGHT_MAX_BASES // (2 * n)),
+                        "the device chain of the same-MSM argument takes crs_G_vec from a FixedBaseTable", prove, 3, 6, 1)
 
 
 def same_msm_prove_device(table, crs_G_vec, A, Z_t, Z_u, vec_T: Sequence[G1Point], vec_U: Sequence[G1Point], vec_x: Sequence[Scalar],
