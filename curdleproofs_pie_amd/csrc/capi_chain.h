@@ -74,13 +74,16 @@ int chain_stage(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L, size_t P, cons
   memcpy(H + L.states, states208, P * 208);
   return CG1_OK;
 }
-// ---- after the last launch: one copy down, the one wait, the chain's status, and only then the caller's buffers
-int chain_finish(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L, size_t P, size_t proof_bytes, uint8_t* states208, uint8_t* out_proofs, uint32_t* out_clocks) {
+// ---- after the last launch: one copy down, the one wait, the chain's status, and only then the caller's buffers.  own_status (optional):
+// the refusals of an argument whose step kernel sets status bits of its own, above k_table_msm's
+int chain_finish(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L, size_t P, size_t proof_bytes, uint8_t* states208, uint8_t* out_proofs, uint32_t* out_clocks,
+                 int (*own_status)(cg1_ctx*, uint32_t) = nullptr) {
   uint8_t* H = t->h_chain;
   HIPCHK(hipMemcpyAsync(H + L.down_begin, t->d_chain + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));                 // the one wait
   HIPCHK(hipGetLastError());
   { const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
+  if (own_status) { const int rc = own_status(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
   memcpy(out_proofs, H + L.proof, P * proof_bytes);
   memcpy(states208, H + L.states, P * 208);
   if (out_clocks) memcpy(out_clocks, H + L.clocks, P * 16);

@@ -24,13 +24,14 @@ constexpr uint32_t IPA_BEGIN = 0, IPA_STEP1 = 1, IPA_ROUND = 2;
 
 struct IpaArgs {
   uint32_t n0, lg, has_coeffs, inv_fermat;
+  uint32_t d_first = 0;                      // 1: the launch before step 1 left THREE encodings, D | B_c | B_d, and D goes into the data row (kernels_gprod.h)
   const uint32_t* gi; const uint32_t* gpi; const uint32_t* hi;         // [P][n0], [P][n0], [P]
   const uint64_t* coef; const uint64_t* vc; const uint64_t* vd; const uint64_t* rc; const uint64_t* rd;   // [P][n0] canonical scalars
   fr* c; fr* d; fr* kG; fr* kGp; fr* kH;     // the state: [P][n0] each, [P]
   uint8_t* states;                           // [P][208]
   uint8_t* trow;                             // [P][IPA_TROW]
   uint8_t* chal;                             // [P][64]: where the transcript writes its draws
-  const uint32_t* pts48;                     // k_fixed_finish's encodings of the launch before: [P][2 or 4][12 words]
+  const uint32_t* pts48;                     // k_fixed_finish's encodings of the launch before: [P][2 (3 with d_first) or 4][12 words]
   uint32_t* proof; uint32_t proof_words;     // [P][proof_words]: IPA.to_bytes order
   uint32_t* tb; uint64_t* sc;                // the term arrays k_table_msm reads: indices, scalars
   const uint32_t* msm_status;                // the status word of the MSM launch before
@@ -66,15 +67,19 @@ __global__ void __launch_bounds__(IPA_THREADS) k_ipa_step(IpaArgs a, uint32_t ph
 
   // ---- the encodings of the launch before: into the proof (and, step 1, into the transcript's data row)
   uint32_t* proof = a.proof + (size_t)p * a.proof_words;
-  const uint32_t npts = phase == IPA_STEP1 ? 2u : 4u;
+  const uint32_t pre = phase == IPA_STEP1 ? a.d_first : 0u;
+  const uint32_t npts = phase == IPA_STEP1 ? 2u + pre : 4u;
   const uint32_t* pts = a.pts48 + (size_t)p * npts * 12u;
   uint8_t* trow = a.trow + (size_t)p * IPA_TROW;
   if (tid < npts * 12u) {
     const uint32_t q = tid / 12u, w = tid - q * 12u, val = pts[tid];
-    // IPA.to_bytes: B_c | B_d | vec_L_C | vec_R_C | vec_L_D | vec_R_D | c_final | d_final; a round's four are L_C, L_D, R_C, R_D
-    const uint32_t slot = phase == IPA_STEP1 ? q : 2u + (q == 0u ? 0u : q == 1u ? 2u : q == 2u ? 1u : 3u) * a.lg + round;
-    proof[slot * 12u + w] = val;
-    if (phase == IPA_STEP1) reinterpret_cast<uint32_t*>(trow + 128)[tid] = val;
+    if (q < pre) reinterpret_cast<uint32_t*>(trow + 48)[w] = val;      // D
+    else {
+      // IPA.to_bytes: B_c | B_d | vec_L_C | vec_R_C | vec_L_D | vec_R_D | c_final | d_final; a round's four are L_C, L_D, R_C, R_D
+      const uint32_t slot = phase == IPA_STEP1 ? q - pre : 2u + (q == 0u ? 0u : q == 1u ? 2u : q == 2u ? 1u : 3u) * a.lg + round;
+      proof[slot * 12u + w] = val;
+      if (phase == IPA_STEP1) reinterpret_cast<uint32_t*>(trow + 128)[tid - pre * 12u] = val;
+    }
   }
   // ---- the transcript, on lane 0
   if (tid == 64u) {

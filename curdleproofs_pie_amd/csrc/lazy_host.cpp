@@ -4,6 +4,7 @@
 #include "pool.h"
 #include "ipa_rounds.h"
 #include "same_msm_rounds.h"
+#include "gprod_rounds.h"
 #include "../../include/curdle_g1.h"
 
 #include <algorithm>
@@ -574,6 +575,84 @@ int cg1_same_msm_round_emulate(int op, size_t n0, size_t len, uint8_t* x32, uint
   }
   for (size_t i = 0; i < len; ++i) cg1fr::fr_to_le32(x[i], x32 + 32 * i);
   for (size_t i = 0; i < n0; ++i) cg1fr::fr_to_le32(k[i], k32 + 32 * i);
+  return CG1_OK;
+}
+
+// The formulas, the blinder completion and the term schedule of the device prover of the grand-product argument (csrc/gprod_rounds.h: the
+// functions k_gprod_step runs -- a workgroup scan and an LDS tree there, loops here), with the two challenges given: for the CPU tests.
+int cg1_gprod_emulate(size_t ell, size_t n_blinders, const uint8_t* gprod_result32, const uint8_t* vec_b32, const uint8_t* vec_c_blinders32,
+                      const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* alpha32, const uint8_t* beta32, const uint32_t* g_index,
+                      uint8_t* out_state32, uint8_t* out_scalars32, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets,
+                      uint32_t* out_status) {
+  using cg1fr::fr;
+  const size_t nb = n_blinders, n0 = ell + nb;
+  if (ell < 1 || nb < 2 || n0 < ell || (n0 & (n0 - 1)) != 0 || n0 > CG1_IPA_MAX_N) return CG1_ERR_ARG;
+  if (!gprod_result32 || !vec_b32 || !vec_c_blinders32 || !ipa_r32 || !ipa_z_head32 || !alpha32 || !beta32 || !g_index || !out_state32 || !out_scalars32 ||
+      !out_term_base || !out_term_scalars32 || !out_offsets || !out_status) return CG1_ERR_ARG;
+  bool ok = true;
+  auto load = [&](const uint8_t* src, size_t count) {
+    std::vector<fr> v(count);
+    for (size_t i = 0; i < count; ++i) ok = cg1fr::fr_from_le32(src + 32 * i, v[i]) && ok;
+    return v;
+  };
+  const std::vector<fr> gres = load(gprod_result32, 1), b = load(vec_b32, n0), cbl = load(vec_c_blinders32, nb), r = load(ipa_r32, n0),
+                        ch = load(alpha32, 1), bt = load(beta32, 1);
+  std::vector<fr> z = load(ipa_z_head32, n0 - 2);
+  if (!ok) return CG1_ERR_ENCODING;
+  const uint32_t n = (uint32_t)n0, L = (uint32_t)ell;
+  const fr alpha = ch[0], beta = bt[0];
+  *out_status = 0;
+  std::vector<fr> c(n), d(n), kg(n, cg1fr::fr_one()), kgp(n);
+  std::vector<uint64_t> sc(4 * (size_t)5 * n);
+  // ---- begin: the prefix products, the product, the terms of B' and C
+  fr pre = cg1fr::fr_one();
+  for (uint32_t i = 0; i < L; ++i) { c[i] = pre; pre = cg1fr::fr_mul(pre, b[i]); }
+  for (uint32_t k = 0; k < nb; ++k) c[L + k] = cbl[k];
+  if (!cg1fr::fr_eq(pre, gres[0])) *out_status |= cg1gprod::ST_BAD_PRODUCT;
+  for (uint32_t j = 0; j < n; ++j) cg1gprod::begin_term(g_index, n, j, b[j], c[j], out_term_base, sc.data());
+  // ---- step: r_p, the powers, vec_d, the coefficients, inner_prod
+  fr r_p = cg1fr::fr_zero();
+  for (uint32_t k = 0; k < nb; ++k) r_p = cg1fr::fr_add(r_p, cg1fr::fr_mul(cg1fr::fr_add(b[L + k], alpha), c[L + k]));
+  fr beta_inv = cg1fr::fr_zero();
+  if (cg1fr::fr_is_zero(beta)) *out_status |= cg1gprod::ST_ZERO_BETA;
+  else {
+    beta_inv = cg1fr::fr_inv_binary(beta);
+    if (!cg1fr::fr_eq(beta_inv, cg1fr::fr_inv(beta))) return CG1_ERR_ARG;             // the two inversions agree, or the test hears of it
+  }
+  fr pw = cg1fr::fr_one(), pwi = beta_inv;
+  for (uint32_t i = 0; i < L; ++i) {
+    d[i] = cg1gprod::d_elem(b[i], beta, pw);
+    kgp[i] = pwi;
+    pw = cg1fr::fr_mul(pw, beta); pwi = cg1fr::fr_mul(pwi, beta_inv);
+  }
+  const fr beta_ell = pw, beta_ell1 = cg1fr::fr_mul(pw, beta);
+  for (uint32_t k = 0; k < nb; ++k) { d[L + k] = cg1gprod::d_blinder(cg1fr::fr_add(b[L + k], alpha), beta_ell1); kgp[L + k] = pwi; }
+  const fr ip = cg1gprod::inner_prod(r_p, gres[0], beta_ell, beta_ell1);
+  // ---- the blinders' completion
+  fr omega = cg1fr::fr_zero(), delta = cg1fr::fr_zero();
+  for (uint32_t j = 0; j < n; ++j) {
+    omega = cg1fr::fr_add(omega, cg1fr::fr_mul(r[j], d[j]));
+    if (j + 2 < n) { omega = cg1fr::fr_add(omega, cg1fr::fr_mul(z[j], c[j])); delta = cg1fr::fr_add(delta, cg1fr::fr_mul(r[j], z[j])); }
+  }
+  const fr e = cg1gprod::blinder_denominator(r[n - 2], r[n - 1], c[n - 2], c[n - 1]);
+  if (cg1fr::fr_is_zero(c[n - 2])) *out_status |= cg1gprod::ST_ZERO_C;
+  if (cg1fr::fr_is_zero(e)) *out_status |= cg1gprod::ST_ZERO_DENOMINATOR;
+  fr pen = cg1fr::fr_zero(), last = cg1fr::fr_zero();
+  if (!(*out_status & (cg1gprod::ST_ZERO_C | cg1gprod::ST_ZERO_DENOMINATOR)))
+    cg1gprod::blinder_finish(omega, delta, r[n - 2], c[n - 2], c[n - 1], e, cg1fr::fr_inv_binary(cg1fr::fr_mul(e, c[n - 2])), pen, last);
+  z.push_back(pen); z.push_back(last);
+  // ---- the terms of D, B_c, B_d
+  cg1ipa::View v{c.data(), d.data(), kg.data(), kgp.data(), g_index, g_index, 0u, n};
+  for (uint32_t j = 0; j < n; ++j)
+    cg1gprod::step_term(v, j, j < L ? cg1fr::fr_sub(b[j], beta_inv) : cg1fr::fr_add(b[j], alpha), r[j], z[j], out_term_base + 2 * n, sc.data() + 4 * (size_t)2 * n);
+  if (*out_status) return CG1_ERR_ARG;
+  memcpy(out_term_scalars32, sc.data(), sc.size() * 8);
+  for (uint32_t q = 0; q <= 5; ++q) out_offsets[q] = q * n;
+  for (uint32_t j = 0; j < n; ++j) {
+    cg1fr::fr_to_le32(c[j], out_state32 + 32 * (size_t)j); cg1fr::fr_to_le32(d[j], out_state32 + 32 * (size_t)(n + j));
+    cg1fr::fr_to_le32(kgp[j], out_state32 + 32 * (size_t)(2 * n + j)); cg1fr::fr_to_le32(z[j], out_state32 + 32 * (size_t)(3 * n + j));
+  }
+  cg1fr::fr_to_le32(r_p, out_scalars32); cg1fr::fr_to_le32(ip, out_scalars32 + 32);
   return CG1_OK;
 }
 

@@ -338,3 +338,62 @@ def grand_product_bases(crs_G_vec: Sequence[G1Point], crs_H_vec: Sequence[G1Poin
         p = p * beta_inv
     res = batch_mul(list(crs_G_vec) + list(crs_H_vec), pows + [p] * len(crs_H_vec))
     return res[:ell], res[ell:]
+
+
+def grand_product_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence) -> List[tuple]:
+    """GrandProductProof.new (grand_prod.py:29-119) after its random draws, for SEVERAL independent provers of one shape in step, proved ON
+    THE DEVICE: one launch chain (csrc/kernels_gprod.h, then the inner-product argument's phases of csrc/kernels_ipa.h), one wait -- the
+    prefix products, both gprod transcript steps, the powers of beta, the completion of the IPA's blinders, the MSMs over the resident
+    `table` (a fixed_base.FixedBaseTable) and the whole inner-product argument never come back to the host.
+    provers[p] = (crs_G_vec, crs_H_vec, crs_U, B, gprod_result, vec_b, vec_b_blinders, vec_c_blinders, ipa_r, ipa_z_head): bases are
+    objects of the table or indices into it (KeyError / IndexError, FixedBaseTable._indices); B is a G1Point or its 48-byte encoding;
+    the draws are the caller's, in the reference's order: vec_c_blinders (n_blinders), then ipa_r (n = ell + n_blinders) and ipa_z_head
+    (n - 2), the two draws of generate_ipa_blinders (ipa.py:30-31) -- the device completes z.  No input is mutated.
+    transcripts[p]: that prover's CurdleproofsTranscript, advanced to the state after the last ipa_gamma.
+    -> per prover (C, r_p, (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final)), the fields of GrandProductProof.
+    A refused call changes nothing.  ValueError: a shape (ell >= 1, n_blinders >= 2, n a power of two).  NativeError: a scalar >= r, an
+    undecodable B, and what the reference answers with an AssertionError or a division by zero -- B is not the commitment to vec_b |
+    vec_b_blinders, gprod_result is not the product of vec_b, vec_c_blinders[-2] = 0, or the second denominator of generate_ipa_blinders
+    is zero (draw ipa_r again)."""
+    from . import _native as N
+    from .py_arkworks_bls12381 import points_to_compressed
+
+    provers, n = _chain_provers(provers, transcripts, 8, "a grand-product", N.IPA_MAX_N)
+    if not provers:
+        return []
+    ell, nb = len(provers[0][0]), len(provers[0][1])
+    if ell < 1 or nb < 2 or ell + nb != n:
+        raise ValueError("a grand-product argument has ell >= 1 bases crs_G_vec, n_blinders >= 2 bases crs_H_vec and ipa_r of length ell + n_blinders")
+    if any(not (len(pr[0]) == len(pr[5]) == ell and len(pr[1]) == len(pr[6]) == len(pr[7]) == nb and len(pr[8]) == n and len(pr[9]) == n - 2) for pr in provers):
+        raise ValueError("provers in step share one shape (ell, n_blinders); ipa_r has n entries and ipa_z_head n - 2")
+    enc = iter(points_to_compressed([pr[3] for pr in provers if type(pr[3]) is G1Point]))
+
+    def prove(lo, part, states):
+        gi, ui, b48, flat = [], [], [], [[] for _ in range(5)]
+        for pr in part:
+            gi.extend(table._indices(pr[0], ell)); gi.extend(table._indices(pr[1], nb)); ui.extend(table._indices([pr[2]], 1))
+            b48.append(bytes(pr[3]) if type(pr[3]) is not G1Point else next(enc))
+            if len(b48[-1]) != 48:
+                raise ValueError("B is a G1Point or a 48-byte encoding")
+            flat[0].append(pr[4])
+            flat[1].extend(pr[5]); flat[1].extend(pr[6])
+            for dst, src in zip(flat[2:], pr[7:10]):
+                dst.extend(src)
+        bufs = [_pack32(vals) for vals in flat]
+        proofs, new_states = table._ctx.gprod_prove_device(table._tab, ell, nb, len(part), gi, ui, b"".join(b48), *bufs, states)
+        pb = len(proofs) // len(part)
+        # C | r_p | the IPA's proof  ->  points first, scalars last: what _chain_prove cuts
+        cut = [proofs[pb * i: pb * i + pb] for i in range(len(part))]
+        return b"".join(raw[:48] + raw[80: pb - 64] + raw[48:80] + raw[pb - 64:] for raw in cut), new_states
+
+    res = _chain_prove(table, provers, transcripts, n, N.IPA_MAX_PROVERS, "the device chain of the grand-product argument runs over a FixedBaseTable",
+                       prove, 3, 4, 3)
+    return [(C, r_p, (*ipa_points, c_final, d_final)) for C, *ipa_points, r_p, c_final, d_final in res]
+
+
+def grand_product_prove_device(table, crs_G_vec, crs_H_vec, crs_U, B, gprod_result: Scalar, vec_b: Sequence[Scalar], vec_b_blinders: Sequence[Scalar],
+                               vec_c_blinders: Sequence[Scalar], ipa_r: Sequence[Scalar], ipa_z_head: Sequence[Scalar], transcript):
+    """GrandProductProof.new (grand_prod.py:29-119) after its draws, on the device: see grand_product_prove_device_many.  `transcript` is
+    advanced as the reference advances it.  -> (C, r_p, (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final))."""
+    return grand_product_prove_device_many(table, [(crs_G_vec, crs_H_vec, crs_U, B, gprod_result, vec_b, vec_b_blinders, vec_c_blinders, ipa_r, ipa_z_head)],
+                                           [transcript])[0]

@@ -672,6 +672,53 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t n, size_t n_p
 int cg1_same_msm_round_emulate(int op, size_t n0, size_t len, uint8_t* x32, uint8_t* k32, const uint8_t* challenge32 /* nullable for op 2 */,
                                const uint8_t* r32, const uint32_t* g_index, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets);
 
+/* ---- The grand-product argument PROVED on the device: GrandProductProof.new (grand_prod.py:29-119) after its random draws, for n_provers
+ * independent provers of one shape (ell, n_blinders; n = ell + n_blinders) in step, as ONE launch chain with one host wait
+ * (csrc/kernels_gprod.h, csrc/gprod_rounds.h, then the phases of csrc/kernels_ipa.h).  vec_G = crs_G_vec | crs_H_vec are n entries of a
+ * cg1_fixed table and never move: C = MSM(vec_G, c | c_blinders) over the prefix products c; the base change G'_i = G_i beta^-(i+1) is a
+ * coefficient vector (the g_prime_coeffs32 of cg1_ipa_prove_device, made on the device), and D, which the reference builds from B, is the
+ * MSM its own assertion says it is (grand_prod.py:105): D = MSM(vec_G, b_j - beta^-1 | r_b_j + alpha).  k_gprod_step begin | MSM finish |
+ * k_gprod_step step (both transcript steps, the prefix products and powers by one workgroup scan, the completion of the IPA's blinders) |
+ * MSM finish | the IPA's step 1 and lg n rounds: 1 + 3 (lg n + 2) launches.
+ *   per prover p, host buffers:
+ *     g_index[p n ..]     table indices of crs_G_vec | crs_H_vec;  u_index[p]  that of crs_U
+ *     b48                 B as a 48-byte encoding: validated like cd48 above and hashed re-serialised.  The reference's assertions
+ *                         (grand_prod.py:103-105) hold exactly when B = MSM(vec_G, vec_b | vec_b_blinders) and gprod_result is the product
+ *                         of vec_b: the chain computes that MSM next to C, compares the encodings, compares the product, and REFUSES the
+ *                         call where the reference raises AssertionError
+ *     gprod_result32, vec_b32 (n scalars: vec_b | vec_b_blinders), vec_c_blinders32 (n_blinders)   canonical scalars
+ *     ipa_r32 (n), ipa_z_head32 (n - 2)   the draws of generate_ipa_blinders (ipa.py:30-31) in its order; the device completes z with
+ *                         penultimate_z, last_z (ipa.py:33-41; one inversion for both denominators)
+ *     states208           in: the transcript where GrandProductProof.new would find it; out: after the last ipa_gamma
+ *     out_proofs          cg1_gprod_proof_bytes(ell, n_blinders) = 48 + 32 + cg1_ipa_proof_bytes(n) bytes each, GrandProductProof.to_bytes
+ *                         order: C | r_p | the IPA's proof
+ *     out_clocks          NULL, or 4 words per prover, as cg1_ipa_prove_device (the inversions: beta, the blinders' and the gammas)
+ *   The returned status covers the whole call, and a refused call leaves out_proofs and states208 untouched.  Refused before anything is
+ *   written, in cg1_ipa_prove_device's order: n not a power of two in 2 .. CG1_IPA_MAX_N, ell < 1 or n_blinders < 2 (so n >= 4), more than
+ *   CG1_IPA_MAX_PROVERS provers, an index outside the table, a table of another device: CG1_ERR_ARG; a scalar >= r: CG1_ERR_ENCODING (never
+ *   reduced); an undecodable B: cg1_validate_compressed's status; vec_c_blinders[n_blinders - 2] = 0 (generate_ipa_blinders divides by it):
+ *   CG1_ERR_ARG.  Refused at the chain's end, from its status word (CG1_GPROD_*; never a trap: a zero is tested BEFORE every inversion and
+ *   the chain runs on with zeros): B not the commitment, gprod_result not the product, gprod_beta = 0, the second denominator of
+ *   generate_ipa_blinders = 0 (r[n-1] c[n-2] = r[n-2] c[n-1]: draw ipa_r again): CG1_ERR_ARG, each with its own text.
+ *   cg1_gprod_emulate     host only, test support: the formulas, the blinder completion and the term schedule compiled from the header the
+ *                         kernel runs (csrc/gprod_rounds.h), with the two challenges given.  out_state32: 4 n scalars c | d | kGp | the
+ *                         completed z;  out_scalars32: r_p | inner_prod;  the terms of the five MSMs B', C, D, B_c, B_d (5 n terms, 6
+ *                         offsets 0, n, .., 5 n).  The same refusals by shape and encoding; for the others CG1_ERR_ARG with *out_status =
+ *                         the CG1_GPROD_* bits (B is not looked at: evaluate the first term list). */
+#define CG1_GPROD_BAD_COMMITMENT   0x100
+#define CG1_GPROD_BAD_PRODUCT      0x200
+#define CG1_GPROD_ZERO_BETA        0x400
+#define CG1_GPROD_ZERO_C           0x800
+#define CG1_GPROD_ZERO_DENOMINATOR 0x1000
+size_t cg1_gprod_proof_bytes(size_t ell, size_t n_blinders);        /* 0 when ell < 1, n_blinders < 2 or ell + n_blinders is not a power of two */
+int cg1_gprod_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_blinders, size_t n_provers, const uint32_t* g_index, const uint32_t* u_index,
+                           const uint8_t* b48, const uint8_t* gprod_result32, const uint8_t* vec_b32, const uint8_t* vec_c_blinders32,
+                           const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, uint8_t* states208, uint8_t* out_proofs, uint32_t* out_clocks /* nullable */);
+int cg1_gprod_emulate(size_t ell, size_t n_blinders, const uint8_t* gprod_result32, const uint8_t* vec_b32, const uint8_t* vec_c_blinders32,
+                      const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* alpha32, const uint8_t* beta32, const uint32_t* g_index,
+                      uint8_t* out_state32, uint8_t* out_scalars32, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets,
+                      uint32_t* out_status);
+
 #ifdef __cplusplus
 }
 #endif
