@@ -288,6 +288,13 @@ cg1_gprod_prove_device = _proto("cg1_gprod_prove_device", c_int, c_void_p, c_voi
 cg1_gprod_emulate = _proto("cg1_gprod_emulate", c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 GPROD_BAD_COMMITMENT, GPROD_BAD_PRODUCT, GPROD_ZERO_BETA, GPROD_ZERO_C, GPROD_ZERO_DENOMINATOR = 0x100, 0x200, 0x400, 0x800, 0x1000      # CG1_GPROD_* of include/curdle_g1.h
+# the same-permutation argument proved on the device (csrc/kernels_same_perm.h, csrc/same_perm_rounds.h, then the grand-product chain)
+cg1_same_perm_proof_bytes = _proto("cg1_same_perm_proof_bytes", c_size_t, c_size_t, c_size_t)
+cg1_same_perm_prove_device = _proto("cg1_same_perm_prove_device", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+cg1_same_perm_emulate = _proto("cg1_same_perm_emulate", c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+SAME_PERM_BAD_A, SAME_PERM_BAD_M = 0x2000, 0x4000                        # CG1_SAME_PERM_* of include/curdle_g1.h
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -313,6 +320,7 @@ EXPORTED_SYMBOLS = [
     "cg1_light_create", "cg1_light_destroy", "cg1_light_len", "cg1_light_bytes", "cg1_light_msm", "cg1_light_msm_device", "cg1_light_digits",
     "cg1_same_msm_proof_bytes", "cg1_same_msm_prove_device", "cg1_same_msm_round_emulate",
     "cg1_gprod_proof_bytes", "cg1_gprod_prove_device", "cg1_gprod_emulate",
+    "cg1_same_perm_proof_bytes", "cg1_same_perm_prove_device", "cg1_same_perm_emulate",
 ]
 
 
@@ -571,6 +579,19 @@ class Context:
         return self._chain_prove_device(lambda ctx, t, _n, P, *rest: cg1_gprod_prove_device(ctx, t, ell, n_blinders, P, *rest),
                                         lambda _n: cg1_gprod_proof_bytes(ell, n_blinders), tab, n, n_provers, (g_index, u_index),
                                         (b48, gprod_result32, vec_b32, vec_c_blinders32, ipa_r32, ipa_z_head32), states208, want_clocks)
+
+    def same_perm_prove_device(self, tab: "FixedTable", ell: int, n_blinders: int, n_provers: int, g_index, u_index, am48: bytes, vec_a32: bytes, perm,
+                               vec_a_blinders32: bytes, vec_m_blinders32: bytes, vec_c_blinders32: bytes, ipa_r32: bytes, ipa_z_head32: bytes, states208: bytes,
+                               want_clocks: bool = False):
+        """cg1_same_perm_prove_device: n_provers same-permutation arguments of shape (ell, n_blinders) over the table, one launch chain, one
+        wait; perm: n_provers * ell ints in 0 .. 2^32 - 1.
+        -> (proofs, states) as bytes [, clocks]; raises (check) on a refusal, and then nothing the caller holds has changed."""
+        n = ell + n_blinders
+        assert len(g_index) == n * n_provers and len(u_index) == n_provers and len(am48) == 96 * n_provers and len(perm) == ell * n_provers
+        perm32 = (ctypes.c_uint32 * max(1, len(perm)))(*perm)
+        return self._chain_prove_device(lambda ctx, t, _n, P, *rest: cg1_same_perm_prove_device(ctx, t, ell, n_blinders, P, *rest),
+                                        lambda _n: cg1_same_perm_proof_bytes(ell, n_blinders), tab, n, n_provers, (g_index, u_index),
+                                        (am48, vec_a32, perm32, vec_a_blinders32, vec_m_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32), states208, want_clocks)
 
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""

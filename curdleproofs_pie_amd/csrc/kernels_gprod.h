@@ -12,11 +12,13 @@
 //           omega and delta by an LDS tree and the last two blinders (one inversion); the terms of D, B_c, B_d
 // and it leaves k_ipa_step's state -- c, d, kG = 1, kGp, the data row C | . | z, r and the completed z where its step 1 reads the
 // blinders -- so the IPA's step 1 and rounds run unchanged (IpaArgs::d_first: the launch before them also computed D).
+// The same-permutation argument (kernels_same_perm.h) runs this chain with another first kernel: GprodArgs::same_perm selects the step
+// phase's other head (four encodings; A', M' checked, B' emitted as B) and moves the proof 12 words on; the default is this header's own.
 // The formulas and the term schedule are gprod_rounds.h (shared with the host).  A zero where an inverse is wanted (beta, c[n-2], the
 // second denominator of generate_ipa_blinders) is tested BEFORE the inversion and sets a status bit; the chain then runs to its end on
 // zeros and the host refuses the call.
 #pragma once
-#include "gprod_rounds.h"
+#include "same_perm_rounds.h"
 #include "kernels_ipa.h"
 
 namespace cg1gprod {
@@ -33,6 +35,10 @@ struct GprodArgs {
   uint64_t* z;                               // [P][n0] canonical: the n0 - 2 drawn entries of z; the step phase completes them (= ipa.rd)
   uint8_t* row;                              // [P][GP_ROW]
   uint32_t* proof; uint32_t proof_words;     // [P][proof_words]: GrandProductProof.to_bytes order, C | r_p | the IPA's proof (= ipa.proof)
+  // The same-permutation argument's head (kernels_same_perm.h: its begin kernel ran instead of the begin phase and left vb, gprod_result
+  // and FOUR encodings A' | M' | B' | C).  The defaults are the grand-product argument's own launch.
+  uint32_t same_perm = 0u;                   // 1: A', M' against am48, B' EMITTED as B (row, proof words 0..11), the proof 12 words further on
+  const uint32_t* am48 = nullptr;            // [P][2][12] canonical encodings: the caller's A | M
 };
 
 // The exclusive prefix products of `count` elements by the whole workgroup: out(i, in(0) .. in(i-1)).  A lane owns a block of
@@ -109,16 +115,21 @@ __global__ void __launch_bounds__(GP_THREADS) k_gprod_step(GprodArgs a, uint32_t
     return;
   }
 
-  // ---- the encodings of launch 1: B' against B, C into the proof and the two data rows
+  // ---- the encodings of launch 1: B' against B, C into the proof and the two data rows; or (same_perm) A' against A, M' against M,
+  // B' into the data row and the proof as B, then C, 12 words further on
+  const uint32_t po = a.same_perm ? 12u : 0u;
   uint32_t* proof = a.proof + (size_t)p * a.proof_words;
-  const uint32_t* pts = a.ipa.pts48 + (size_t)p * 2u * 12u;
+  const uint32_t* pts = a.ipa.pts48 + (size_t)p * (a.same_perm ? 4u : 2u) * 12u;
   uint8_t* trow = a.ipa.trow + (size_t)p * cg1ipa::IPA_TROW;
-  if (tid < 24u) {
-    const uint32_t w = tid < 12u ? tid : tid - 12u, val = pts[tid];
-    if (tid < 12u) {
-      if (val != reinterpret_cast<const uint32_t*>(row)[w]) atomicOr(a.ipa.chain_status, ST_BAD_COMMITMENT);
+  if (tid < 24u + 2u * po) {
+    const uint32_t q = tid / 12u + (a.same_perm ? 0u : 2u), w = tid % 12u, val = pts[tid];      // q: A' | M' | B' | C
+    if (q < 2u) {
+      if (val != a.am48[(size_t)p * 24u + tid]) atomicOr(a.ipa.chain_status, q == 0u ? cg1sperm::ST_BAD_A : cg1sperm::ST_BAD_M);
+    } else if (q == 2u) {
+      if (a.same_perm) { reinterpret_cast<uint32_t*>(row)[w] = val; proof[w] = val; }
+      else if (val != reinterpret_cast<const uint32_t*>(row)[w]) atomicOr(a.ipa.chain_status, ST_BAD_COMMITMENT);
     } else {
-      proof[w] = val;
+      proof[po + w] = val;
       reinterpret_cast<uint32_t*>(row + 80)[w] = val;
       reinterpret_cast<uint32_t*>(trow)[w] = val;
     }
@@ -143,7 +154,7 @@ __global__ void __launch_bounds__(GP_THREADS) k_gprod_step(GprodArgs a, uint32_t
     tree_sum2(s_red, acc, acc);
     if (tid == 0u) {
       s_x[1] = s_red[0][0];
-      cg1chain::put_scalar(proof + 12, s_red[0][0]);
+      cg1chain::put_scalar(proof + po + 12u, s_red[0][0]);
       cg1chain::put_scalar(reinterpret_cast<uint32_t*>(row + 128), s_red[0][0]);
     }
   }

@@ -5,6 +5,7 @@
 #include "ipa_rounds.h"
 #include "same_msm_rounds.h"
 #include "gprod_rounds.h"
+#include "same_perm_rounds.h"
 #include "../../include/curdle_g1.h"
 
 #include <algorithm>
@@ -653,6 +654,63 @@ int cg1_gprod_emulate(size_t ell, size_t n_blinders, const uint8_t* gprod_result
     cg1fr::fr_to_le32(kgp[j], out_state32 + 32 * (size_t)(2 * n + j)); cg1fr::fr_to_le32(z[j], out_state32 + 32 * (size_t)(3 * n + j));
   }
   cg1fr::fr_to_le32(r_p, out_scalars32); cg1fr::fr_to_le32(ip, out_scalars32 + 32);
+  return CG1_OK;
+}
+
+// The head of the device prover of the same-permutation argument: the host transcript head the entry runs (on a copy of the state: a
+// refused call leaves it alone) and the formulas and term schedule of k_same_perm_begin (csrc/same_perm_rounds.h -- a workgroup scan
+// there, a loop here): for the CPU tests.
+int cg1_same_perm_emulate(size_t ell, size_t n_blinders, uint8_t* state208, const uint8_t* a48, const uint8_t* m48, const uint8_t* vec_a32, const uint32_t* perm,
+                          const uint8_t* vec_a_blinders32, const uint8_t* vec_m_blinders32, const uint8_t* vec_c_blinders32, const uint32_t* g_index,
+                          uint8_t* out_challenges32, uint8_t* out_b32, uint8_t* out_gprod_result32, uint32_t* out_term_base, uint8_t* out_term_scalars32,
+                          uint32_t* out_offsets, uint32_t* out_status) {
+  using cg1fr::fr;
+  const size_t nb = n_blinders, n0 = ell + nb;
+  if (ell < 1 || nb < 2 || n0 < ell || (n0 & (n0 - 1)) != 0 || n0 > CG1_IPA_MAX_N) return CG1_ERR_ARG;
+  if (!state208 || !a48 || !m48 || !vec_a32 || !perm || !vec_a_blinders32 || !vec_m_blinders32 || !vec_c_blinders32 || !g_index || !out_challenges32 || !out_b32 ||
+      !out_gprod_result32 || !out_term_base || !out_term_scalars32 || !out_offsets || !out_status) return CG1_ERR_ARG;
+  for (size_t i = 0; i < ell; ++i)
+    if (perm[i] >= ell) return CG1_ERR_ARG;
+  bool ok = true;
+  auto load = [&](const uint8_t* src, size_t count) {
+    std::vector<fr> v(count);
+    for (size_t i = 0; i < count; ++i) ok = cg1fr::fr_from_le32(src + 32 * i, v[i]) && ok;
+    return v;
+  };
+  const std::vector<fr> va = load(vec_a32, ell), abl = load(vec_a_blinders32, nb), mbl = load(vec_m_blinders32, nb), cbl = load(vec_c_blinders32, nb);
+  if (!ok) return CG1_ERR_ENCODING;
+  uint8_t am[96];
+  for (int q = 0; q < 2; ++q) {                             // as the transcript absorbs them: the identity re-serialised
+    int inf = 0;
+    const uint8_t* src = q == 0 ? a48 : m48;
+    const int rc = cg1_validate_compressed(src, &inf);
+    if (rc != CG1_OK) return rc;
+    memcpy(am + 48 * q, src, 48);
+    if (inf) { memset(am + 48 * q, 0, 48); am[48 * q] = 0xC0; }
+  }
+  // ---- same_perm_step1 [A, M], same_perm_step1 vec_a -> same_perm_alpha, same_perm_beta
+  static const uint8_t step1[] = "same_perm_step1", l_alpha[] = "same_perm_alpha", l_beta[] = "same_perm_beta";
+  cg1_merlin_append_list(state208, step1, 15, am, 48, 2);
+  cg1_merlin_append_list(state208, step1, 15, vec_a32, 32, ell);
+  cg1_merlin_challenge_scalar(state208, l_alpha, 15, out_challenges32);
+  cg1_merlin_challenge_scalar(state208, l_beta, 14, out_challenges32 + 32);
+  const std::vector<fr> ch = load(out_challenges32, 2);
+  const uint32_t n = (uint32_t)n0, L = (uint32_t)ell;
+  *out_status = 0;
+  // ---- b | b_blinders, the prefix products, gprod_result, the terms of A', M', B', C
+  std::vector<fr> b(n), c(n);
+  for (uint32_t j = 0; j < L; ++j) b[j] = cg1sperm::factor(va[perm[j]], perm[j], ch[0], ch[1]);
+  for (uint32_t k = 0; k < nb; ++k) b[L + k] = cg1sperm::blinder(abl[k], mbl[k], ch[0]);
+  fr pre = cg1fr::fr_one();
+  for (uint32_t i = 0; i < L; ++i) { c[i] = pre; pre = cg1fr::fr_mul(pre, b[i]); }
+  for (uint32_t k = 0; k < nb; ++k) c[L + k] = cbl[k];
+  std::vector<uint64_t> sc(4 * (size_t)cg1sperm::begin_terms(n));
+  for (uint32_t j = 0; j < n; ++j)
+    cg1sperm::begin_term(g_index, n, j, j < L ? va[perm[j]] : abl[j - L], j < L ? cg1fr::fr_from_u64(perm[j]) : mbl[j - L], b[j], c[j], out_term_base, sc.data());
+  memcpy(out_term_scalars32, sc.data(), sc.size() * 8);
+  cg1sperm::begin_offsets(n, 0, out_offsets);
+  for (uint32_t j = 0; j < n; ++j) cg1fr::fr_to_le32(b[j], out_b32 + 32 * (size_t)j);
+  cg1fr::fr_to_le32(pre, out_gprod_result32);
   return CG1_OK;
 }
 

@@ -397,3 +397,67 @@ def grand_product_prove_device(table, crs_G_vec, crs_H_vec, crs_U, B, gprod_resu
     advanced as the reference advances it.  -> (C, r_p, (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final))."""
     return grand_product_prove_device_many(table, [(crs_G_vec, crs_H_vec, crs_U, B, gprod_result, vec_b, vec_b_blinders, vec_c_blinders, ipa_r, ipa_z_head)],
                                            [transcript])[0]
+
+
+def same_permutation_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence) -> List[tuple]:
+    """SamePermutationProof.new (same_perm.py:27-72) after its callee's random draws, for SEVERAL independent provers of one shape in step,
+    proved ON THE DEVICE: the grand-product launch chain with another head (csrc/kernels_same_perm.h, then csrc/kernels_gprod.h and the
+    inner-product argument's phases of csrc/kernels_ipa.h), one wait.  same_perm_step1 and the challenges same_perm_alpha / same_perm_beta
+    run on the host inside the native call (they depend on nothing the device computes); the polynomial factors, their product, B and
+    everything GrandProductProof.new does never come back to the host.
+    provers[p] = (crs_G_vec, crs_H_vec, crs_U, A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders, vec_c_blinders, ipa_r, ipa_z_head):
+    bases are objects of the table or indices into it (KeyError / IndexError, FixedBaseTable._indices); A and M are G1Points or their
+    48-byte encodings; permutation holds ell ints (not required to be a bijection: the reference does not require it either); the draws
+    are the caller's, in the reference's order, as in grand_product_prove_device_many.  No input is mutated.
+    transcripts[p]: that prover's CurdleproofsTranscript, advanced to the state after the last ipa_gamma.
+    -> per prover (B, (C, r_p, (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final))), the fields of SamePermutationProof.
+    A refused call changes nothing.  ValueError: a shape (ell >= 1, n_blinders >= 2, n a power of two; a permutation entry that is not an
+    int in 0 .. 2^32 - 1).  NativeError: a scalar >= r, an undecodable A or M, a permutation entry >= ell, and what the reference answers
+    with an AssertionError or a division by zero -- A is not the commitment to vec_a o permutation | vec_a_blinders, M is not the
+    commitment to permutation | vec_m_blinders, vec_c_blinders[-2] = 0, or the second denominator of generate_ipa_blinders is zero."""
+    from . import _native as N
+    from .py_arkworks_bls12381 import points_to_compressed
+
+    provers, n = _chain_provers(provers, transcripts, 10, "a same-permutation", N.IPA_MAX_N)
+    if not provers:
+        return []
+    ell, nb = len(provers[0][0]), len(provers[0][1])
+    if ell < 1 or nb < 2 or ell + nb != n:
+        raise ValueError("a same-permutation argument has ell >= 1 bases crs_G_vec, n_blinders >= 2 bases crs_H_vec and ipa_r of length ell + n_blinders")
+    if any(not (len(pr[0]) == len(pr[5]) == len(pr[6]) == ell and len(pr[1]) == len(pr[7]) == len(pr[8]) == len(pr[9]) == nb and len(pr[10]) == n
+                and len(pr[11]) == n - 2) for pr in provers):
+        raise ValueError("provers in step share one shape (ell, n_blinders); vec_a and the permutation have ell entries, ipa_r n and ipa_z_head n - 2")
+    if any(not isinstance(m, int) or not 0 <= m < 1 << 32 for pr in provers for m in pr[6]):
+        raise ValueError("a permutation holds ints in 0 .. 2^32 - 1")
+    enc = iter(points_to_compressed([x for pr in provers for x in pr[3:5] if type(x) is G1Point]))
+
+    def prove(lo, part, states):
+        gi, ui, am, perm, flat = [], [], [], [], [[] for _ in range(6)]
+        for pr in part:
+            gi.extend(table._indices(pr[0], ell)); gi.extend(table._indices(pr[1], nb)); ui.extend(table._indices([pr[2]], 1))
+            am.extend(bytes(x) if type(x) is not G1Point else next(enc) for x in pr[3:5])
+            if any(len(e) != 48 for e in am[-2:]):
+                raise ValueError("A and M are G1Points or 48-byte encodings")
+            perm.extend(pr[6])
+            for dst, src in zip(flat, (pr[5],) + pr[7:12]):
+                dst.extend(src)
+        bufs = [_pack32(vals) for vals in flat]
+        proofs, new_states = table._ctx.same_perm_prove_device(table._tab, ell, nb, len(part), gi, ui, b"".join(am), bufs[0], perm, *bufs[1:], states)
+        pb = len(proofs) // len(part)
+        # B | C | r_p | the IPA's proof  ->  points first, scalars last: what _chain_prove cuts
+        cut = [proofs[pb * i: pb * i + pb] for i in range(len(part))]
+        return b"".join(raw[:96] + raw[128: pb - 64] + raw[96:128] + raw[pb - 64:] for raw in cut), new_states
+
+    res = _chain_prove(table, provers, transcripts, n, N.IPA_MAX_PROVERS, "the device chain of the same-permutation argument runs over a FixedBaseTable",
+                       prove, 4, 4, 3)
+    return [(B, (C, r_p, (*ipa_points, c_final, d_final))) for B, C, *ipa_points, r_p, c_final, d_final in res]
+
+
+def same_permutation_prove_device(table, crs_G_vec, crs_H_vec, crs_U, A, M, vec_a: Sequence[Scalar], permutation: Sequence[int],
+                                  vec_a_blinders: Sequence[Scalar], vec_m_blinders: Sequence[Scalar], vec_c_blinders: Sequence[Scalar], ipa_r: Sequence[Scalar],
+                                  ipa_z_head: Sequence[Scalar], transcript):
+    """SamePermutationProof.new (same_perm.py:27-72) after its callee's draws, on the device: see same_permutation_prove_device_many.
+    `transcript` is advanced as the reference advances it.
+    -> (B, (C, r_p, (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final)))."""
+    return same_permutation_prove_device_many(table, [(crs_G_vec, crs_H_vec, crs_U, A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders, vec_c_blinders,
+                                                       ipa_r, ipa_z_head)], [transcript])[0]

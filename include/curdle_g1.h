@@ -719,6 +719,46 @@ int cg1_gprod_emulate(size_t ell, size_t n_blinders, const uint8_t* gprod_result
                       uint8_t* out_state32, uint8_t* out_scalars32, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets,
                       uint32_t* out_status);
 
+/* ---- The same-permutation argument PROVED on the device: SamePermutationProof.new (same_perm.py:27-72) after its callee's random draws,
+ * for n_provers independent provers of one shape in step: the grand-product launch chain above with another head, still 1 + 3 (lg n + 2)
+ * launches and one host wait (csrc/kernels_same_perm.h, csrc/same_perm_rounds.h, then k_gprod_step's step phase and the IPA's phases).
+ * The bases never move.  With b_i = vec_a[perm[i]] + perm[i] alpha + beta and b_blinder_k = vec_a_blinders[k] + alpha vec_m_blinders[k], the
+ * reference's B = A + alpha M + beta sum G_i equals B' = MSM(vec_G, b | b_blinders) exactly when A - A' + alpha (M - M') = O for
+ * A' = MSM(vec_G, vec_a o perm | vec_a_blinders), M' = MSM(vec_G, perm | vec_m_blinders) -- which is also exactly when the reference's
+ * assertion grand_prod.py:105 holds.  The first MSM launch computes A', M', B' and C (4 MSMs of n terms per prover); the chain compares the
+ * encodings of A' and M' with the caller's A and M, REFUSES the call on a mismatch where the reference raises AssertionError, and EMITS B'
+ * as B.  A = A' and M = M' is stricter than the reference's condition only on the event A - A' = -alpha (M - M') != O; alpha is drawn after
+ * A and M are absorbed, so that event has negligible probability.  No point outside the table enters an MSM.
+ * same_perm_step1 [A, M], same_perm_step1 vec_a and the challenges same_perm_alpha, same_perm_beta depend on nothing the device computes:
+ * the entry runs them on the host, on the copy of the states it uploads, and uploads alpha and beta.
+ *   per prover p, host buffers (g_index, u_index, vec_c_blinders32, ipa_r32, ipa_z_head32, states208, out_clocks: as cg1_gprod_prove_device):
+ *     am48                A | M as 48-byte encodings: validated like b48 above and hashed re-serialised
+ *     vec_a32 (ell), vec_a_blinders32, vec_m_blinders32 (n_blinders each)   canonical scalars
+ *     perm                ell uint32 entries < ell; NOT required to be a bijection (the reference does not require it either)
+ *     out_proofs          cg1_same_perm_proof_bytes(ell, n_blinders) = 48 + cg1_gprod_proof_bytes(ell, n_blinders) bytes each,
+ *                         SamePermutationProof.to_bytes order: B | C | r_p | the IPA's proof
+ *   Refusals as cg1_gprod_prove_device's, in its order, and: a perm entry >= ell (the reference's get_permutation raises IndexError):
+ *   CG1_ERR_ARG; an undecodable A or M: cg1_validate_compressed's status; every scalar array is checked < r.  At the chain's end, from its
+ *   status word: A or M not the commitment (CG1_SAME_PERM_*), then the grand-product chain's own (CG1_GPROD_*), each with its own text.  A
+ *   refused call leaves out_proofs and states208 untouched.
+ *   cg1_same_perm_emulate   host only, test support: the host transcript head and the formulas and term schedule compiled from the header
+ *                         the kernel runs (csrc/same_perm_rounds.h).  state208: in/out, advanced past same_perm_beta (untouched by a refused
+ *                         call);  out_challenges32: alpha | beta;  out_b32: n scalars b | b_blinders;  out_gprod_result32;  the terms of
+ *                         the four MSMs A', M', B', C (4 n terms, 5 offsets 0, n, .., 4 n; vec_c_blinders32 is what C's list ends in).  The
+ *                         entry's refusals by shape, permutation and encoding; *out_status = 0 (A and M are only decoded: evaluate the
+ *                         first two term lists). */
+#define CG1_SAME_PERM_BAD_A        0x2000
+#define CG1_SAME_PERM_BAD_M        0x4000
+size_t cg1_same_perm_proof_bytes(size_t ell, size_t n_blinders);    /* 0 when cg1_gprod_proof_bytes is */
+int cg1_same_perm_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_blinders, size_t n_provers, const uint32_t* g_index, const uint32_t* u_index,
+                               const uint8_t* am48, const uint8_t* vec_a32, const uint32_t* perm, const uint8_t* vec_a_blinders32, const uint8_t* vec_m_blinders32,
+                               const uint8_t* vec_c_blinders32, const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, uint8_t* states208, uint8_t* out_proofs,
+                               uint32_t* out_clocks /* nullable */);
+int cg1_same_perm_emulate(size_t ell, size_t n_blinders, uint8_t* state208, const uint8_t* a48, const uint8_t* m48, const uint8_t* vec_a32, const uint32_t* perm,
+                          const uint8_t* vec_a_blinders32, const uint8_t* vec_m_blinders32, const uint8_t* vec_c_blinders32, const uint32_t* g_index,
+                          uint8_t* out_challenges32, uint8_t* out_b32, uint8_t* out_gprod_result32, uint32_t* out_term_base, uint8_t* out_term_scalars32,
+                          uint32_t* out_offsets, uint32_t* out_status);
+
 #ifdef __cplusplus
 }
 #endif
