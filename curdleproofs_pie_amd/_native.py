@@ -295,6 +295,13 @@ cg1_same_perm_prove_device = _proto("cg1_same_perm_prove_device", c_int, c_void_
 cg1_same_perm_emulate = _proto("cg1_same_perm_emulate", c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 SAME_PERM_BAD_A, SAME_PERM_BAD_M = 0x2000, 0x4000                        # CG1_SAME_PERM_* of include/curdle_g1.h
+# the shuffle prover's same-scalar block proved on the device (csrc/kernels_same_scalar.h, csrc/same_scalar_rounds.h)
+cg1_same_scalar_proof_bytes = _proto("cg1_same_scalar_proof_bytes", c_size_t)
+cg1_same_scalar_prove_device = _proto("cg1_same_scalar_prove_device", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_void_p, c_void_p, c_void_p)
+cg1_same_scalar_emulate = _proto("cg1_same_scalar_emulate", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p)
+SAME_SCALAR_NOT_G1, SAME_SCALAR_MAX_ELL, SAME_SCALAR_MAX_PROVERS = 0x8000, 1024, 64      # CG1_SAME_SCALAR_* of include/curdle_g1.h
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -321,6 +328,7 @@ EXPORTED_SYMBOLS = [
     "cg1_same_msm_proof_bytes", "cg1_same_msm_prove_device", "cg1_same_msm_round_emulate",
     "cg1_gprod_proof_bytes", "cg1_gprod_prove_device", "cg1_gprod_emulate",
     "cg1_same_perm_proof_bytes", "cg1_same_perm_prove_device", "cg1_same_perm_emulate",
+    "cg1_same_scalar_proof_bytes", "cg1_same_scalar_prove_device", "cg1_same_scalar_emulate",
 ]
 
 
@@ -592,6 +600,17 @@ class Context:
         return self._chain_prove_device(lambda ctx, t, _n, P, *rest: cg1_same_perm_prove_device(ctx, t, ell, n_blinders, P, *rest),
                                         lambda _n: cg1_same_perm_proof_bytes(ell, n_blinders), tab, n, n_provers, (g_index, u_index),
                                         (am48, vec_a32, perm32, vec_a_blinders32, vec_m_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32), states208, want_clocks)
+
+    def same_scalar_prove_device(self, tab: "FixedTable", ell: int, n_provers: int, gth_affine96: bytes, rs_affine96: bytes, vec_a32: bytes, k32: bytes,
+                                 blinders32: bytes, bases_certified: bool, states208: bytes, want_clocks: bool = False):
+        """cg1_same_scalar_prove_device: the same-scalar block (R, S, cm_T, cm_U, SameScalarProof.new) of n_provers provers of one ell over
+        ONE light table of G_t | G_u | H | every prover's vec_R | vec_S, built inside the call: one launch chain, one wait.  blinders32:
+        r_t r_u r_a r_b r_k per prover.  bases_certified: every vec_R | vec_S record is known to lie in G1 (otherwise the chain tests them).
+        -> (proofs, states) as bytes [, clocks]; raises (check) on a refusal, and then nothing the caller holds has changed."""
+        assert len(gth_affine96) == 288 and len(rs_affine96) == 192 * ell * n_provers
+        return self._chain_prove_device(lambda ctx, t, _n, P, *rest: cg1_same_scalar_prove_device(ctx, t, ell, P, *rest[:5], 1 if bases_certified else 0, *rest[5:]),
+                                        lambda _n: cg1_same_scalar_proof_bytes(), tab, ell, n_provers, (),
+                                        (gth_affine96, rs_affine96, vec_a32, k32, blinders32), states208, want_clocks)
 
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""

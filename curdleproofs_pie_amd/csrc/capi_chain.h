@@ -1,4 +1,4 @@
-// The host layer every argument proved as one device launch chain shares (capi_ipa.h, capi_same_msm.h, capi_gprod.h with capi_same_perm.h): the layout of the staging block,
+// The host layer every argument proved as one device launch chain shares (capi_ipa.h, capi_same_msm.h, capi_gprod.h with capi_same_perm.h, capi_same_scalar.h): the layout of the staging block,
 // the refusals, the staging of status, clocks and states, and the tail from the download to the caller's buffers.  An entry point keeps
 // its argument list, its layout's fields, its own refusals and its launch sequence.
 // Part of the single translation unit csrc/msm_gpu.hip (included there; not a stand-alone header).

@@ -30,6 +30,22 @@ int light_alloc(cg1_ctx* ctx, cg1_light* t, size_t m) {
   return t->alloc(ctx);
 }
 
+// The light table a device prover builds inside its call over per-proof bases (capi_same_msm.h, capi_same_scalar.h): ONE scratch of
+// records kept with the cg1_fixed handle the chain runs on, regrown only when a call needs more than it holds.  Nothing is built.
+int chain_light_scratch(cg1_ctx* ctx, cg1_fixed* t, size_t m, cg1_light*& lt) {
+  if (m > t->cap_smsm_bases) {
+    if (t->smsm_light) cg1_light_destroy(t->smsm_light);
+    t->smsm_light = new cg1_light();
+    t->smsm_light->device = ctx->device;
+    t->cap_smsm_bases = 0;
+    { const int rc = light_alloc(ctx, t->smsm_light, m); if (rc) { cg1_light_destroy(t->smsm_light); t->smsm_light = nullptr; return rc; } }
+    t->cap_smsm_bases = m;
+  }
+  lt = t->smsm_light;
+  lt->n_bases = m;
+  return CG1_OK;
+}
+
 int light_create_impl(cg1_ctx* ctx, cg1_light* t, const uint8_t* bases96, size_t m) {
   for (size_t b = 0; b < m; ++b) {                          // canonical coordinates, on the curve (or the all-zero identity record)
     uint8_t blob[CG1_POINT_BYTES];

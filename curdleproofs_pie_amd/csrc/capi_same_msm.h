@@ -49,16 +49,8 @@ int cg1_same_msm_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t n, size_t n_pro
   const SmsmLayout L = smsm_layout(n, P, pb);
   uint8_t* H; uint8_t* D;
   if (const int rc = chain_stage(ctx, t, L, P, states208, H, D)) return rc;
-  if (P * 2 * n > t->cap_smsm_bases) {                      // the light table's records: kept with the handle, regrown only when too small
-    if (t->smsm_light) cg1_light_destroy(t->smsm_light);
-    t->smsm_light = new cg1_light();
-    t->smsm_light->device = ctx->device;
-    t->cap_smsm_bases = 0;
-    { const int rc = light_alloc(ctx, t->smsm_light, P * 2 * n); if (rc) { cg1_light_destroy(t->smsm_light); t->smsm_light = nullptr; return rc; } }
-    t->cap_smsm_bases = P * 2 * n;
-  }
-  cg1_light* lt = t->smsm_light;
-  lt->n_bases = P * 2 * n;
+  cg1_light* lt;
+  if (const int rc = chain_light_scratch(ctx, t, P * 2 * n, lt)) return rc;
   // ---- stage the inputs: one block, one copy.  The first two same_msm_step1 lists ([A, Z_t, Z_u] and vec_T + vec_U, 2 n encodings:
   // ~74 Keccak permutations at n = 128) depend on nothing the device computes: absorbed here, into the states that go up.
   memcpy(H + L.gi, g_index, P * n * 4);

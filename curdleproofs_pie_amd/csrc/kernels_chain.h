@@ -1,4 +1,4 @@
-// The skeleton of a step kernel of an argument proved as ONE launch chain (kernels_ipa.h, kernels_same_msm.h): one workgroup per prover,
+// The skeleton of a step kernel of an argument proved as ONE launch chain (kernels_ipa.h, kernels_same_msm.h, kernels_gprod.h, kernels_same_scalar.h): one workgroup per prover,
 // between two k_table_msm / k_fixed_finish launches.  Shared by every argument: the transcript on lane 0 -- cg1merlin::Machine over the
 // prover's OWN 208-byte state in device memory, absorbing the encodings k_fixed_finish left and drawing the step's challenge (that lane
 // is the serial part of a step: Keccak permutations, a rejection-sampled draw, the inversion) -- the status of the launch before, the

@@ -6,6 +6,7 @@
 #include "same_msm_rounds.h"
 #include "gprod_rounds.h"
 #include "same_perm_rounds.h"
+#include "same_scalar_rounds.h"
 #include "../../include/curdle_g1.h"
 
 #include <algorithm>
@@ -711,6 +712,48 @@ int cg1_same_perm_emulate(size_t ell, size_t n_blinders, uint8_t* state208, cons
   cg1sperm::begin_offsets(n, 0, out_offsets);
   for (uint32_t j = 0; j < n; ++j) cg1fr::fr_to_le32(b[j], out_b32 + 32 * (size_t)j);
   cg1fr::fr_to_le32(pre, out_gprod_result32);
+  return CG1_OK;
+}
+
+// The term schedule and the formulas of the device prover of the same-scalar block (csrc/same_scalar_rounds.h: the functions
+// k_sscalar_step runs, one lane per element there, a loop here) and, given the ten encodings, its transcript step on the host: for the
+// CPU tests.
+int cg1_same_scalar_emulate(size_t ell, const uint8_t* vec_a32, const uint8_t* k32, const uint8_t* blinders32, const uint8_t* enc480, uint8_t* state208,
+                            uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets, uint8_t* out_alpha32, uint8_t* out_z96) {
+  using cg1fr::fr;
+  if (ell < 1 || ell > CG1_SAME_SCALAR_MAX_ELL) return CG1_ERR_ARG;
+  if (!vec_a32 || !k32 || !blinders32 || !out_term_base || !out_term_scalars32 || !out_offsets || (enc480 && (!state208 || !out_alpha32 || !out_z96))) return CG1_ERR_ARG;
+  bool ok = true;
+  auto load = [&](const uint8_t* src, size_t count) {
+    std::vector<fr> v(count);
+    for (size_t i = 0; i < count; ++i) ok = cg1fr::fr_from_le32(src + 32 * i, v[i]) && ok;
+    return v;
+  };
+  const std::vector<fr> va = load(vec_a32, ell), k = load(k32, 1), bl = load(blinders32, 5);          // bl: r_t r_u r_a r_b r_k
+  if (!ok) return CG1_ERR_ENCODING;
+  uint8_t enc[cg1sscalar::MSMS * 48];
+  for (uint32_t q = 0; enc480 && q < cg1sscalar::MSMS; ++q) {          // as the transcript absorbs them: the identity re-serialised
+    int inf = 0;
+    const int rc = cg1_validate_compressed(enc480 + 48 * q, &inf);
+    if (rc != CG1_OK) return rc;
+    memcpy(enc + 48 * q, enc480 + 48 * q, 48);
+    if (inf) { memset(enc + 48 * q, 0, 48); enc[48 * q] = 0xC0; }
+  }
+  const uint32_t L = (uint32_t)ell;
+  std::vector<uint64_t> sc(4 * (size_t)cg1sscalar::terms(L));
+  for (uint32_t j = 0; j < L; ++j) cg1sscalar::elem_terms(L, cg1sscalar::SHARED_BASES, j, va[j], k[0], bl[4], out_term_base, sc.data());
+  for (uint32_t w = 0; w < 4; ++w) cg1sscalar::blinder_terms(L, w, bl[w], out_term_base, sc.data());
+  memcpy(out_term_scalars32, sc.data(), sc.size() * 8);
+  cg1sscalar::offsets(L, 0, out_offsets);
+  if (!enc480) return CG1_OK;
+  // ---- sameexp_points [R, S, T.T_1, T.T_2, U.T_1, U.T_2, A.T_1, A.T_2, B.T_1, B.T_2] -> same_scalar_alpha, then the responses
+  static const uint8_t l_points[] = "sameexp_points", l_alpha[] = "same_scalar_alpha";
+  cg1_merlin_append_list(state208, l_points, 14, enc, 48, cg1sscalar::MSMS);
+  cg1_merlin_challenge_scalar(state208, l_alpha, 17, out_alpha32);
+  const std::vector<fr> alpha = load(out_alpha32, 1);
+  cg1fr::fr_to_le32(cg1sscalar::response(bl[4], k[0], alpha[0]), out_z96);
+  cg1fr::fr_to_le32(cg1sscalar::response(bl[2], bl[0], alpha[0]), out_z96 + 32);
+  cg1fr::fr_to_le32(cg1sscalar::response(bl[3], bl[1], alpha[0]), out_z96 + 64);
   return CG1_OK;
 }
 

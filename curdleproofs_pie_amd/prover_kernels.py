@@ -461,3 +461,69 @@ def same_permutation_prove_device(table, crs_G_vec, crs_H_vec, crs_U, A, M, vec_
     -> (B, (C, r_p, (B_c, B_d, vec_L_C, vec_R_C, vec_L_D, vec_R_D, c_final, d_final)))."""
     return same_permutation_prove_device_many(table, [(crs_G_vec, crs_H_vec, crs_U, A, M, vec_a, permutation, vec_a_blinders, vec_m_blinders, vec_c_blinders,
                                                        ipa_r, ipa_z_head)], [transcript])[0]
+
+
+def same_scalar_prove_device_many(table, provers: Sequence[tuple], transcripts: Sequence) -> List[tuple]:
+    """What CurdleProofsProof.new runs between SamePermutationProof.new and SameMSMProof.new (curdleproofs.py:92-116), for SEVERAL
+    independent provers of one ell in step, proved ON THE DEVICE: R = MSM(vec_R, vec_a), S = MSM(vec_S, vec_a), cm_T, cm_U and all of
+    SameScalarProof.new (same_scalar.py:39-69) as one launch chain (csrc/kernels_same_scalar.h), one wait.  R k, S k, R r_k and S r_k are
+    never formed: the factors fold into the scalars, and every point the block emits is one MSM over a light table of crs_G_t | crs_G_u |
+    crs_H | vec_R | vec_S the call builds on the device.  `table` (a fixed_base.FixedBaseTable) is the chain's home -- its staging block,
+    its light-table scratch, its context's lock; the three CRS points need not be among its bases.
+    provers[p] = (crs_G_t, crs_G_u, crs_H, vec_R, vec_S, vec_a, k, r_t, r_u, r_a, r_b, r_k): G1Points (deferred ones are materialised in
+    one batch; the identity included), Scalars; the draws are the caller's, in the reference's order (r_t, r_u before the block, then r_a,
+    r_b, r_k).  Provers that follow one another with the same three CRS points share a call.  No input is mutated.
+    The folding is exact only for vec_R / vec_S in the prime-order subgroup: where every one of a call's entries already carries a
+    membership certificate the call says so, otherwise the chain tests them on the device -- no host test is run here.
+    transcripts[p]: that prover's CurdleproofsTranscript, advanced to the state after same_scalar_alpha.
+    -> per prover (R, S, cm_T, cm_U, cm_A, cm_B, z_k, z_t, z_u), a commitment as the pair (T_1, T_2).
+    A refused call changes nothing.  ValueError: a shape (ell in 1 .. 1024, one ell for all).  NativeError: a scalar >= r, or a vec_R /
+    vec_S entry outside G1 -- that caller stays on the operators, which multiply R itself."""
+    from . import _native as N
+    from .py_arkworks_bls12381 import points_to_affine96
+
+    provers = [tuple(pr) for pr in provers]
+    if len(provers) != len(transcripts):
+        raise ValueError("one transcript per prover")
+    if not provers:
+        return []
+    ell = len(provers[0][3])
+    if not 1 <= ell <= N.SAME_SCALAR_MAX_ELL:
+        raise ValueError(f"the vectors of a same-scalar block have a length in 1 .. {N.SAME_SCALAR_MAX_ELL}, not {ell}")
+    if any(len(pr) != 12 or not (len(pr[3]) == len(pr[4]) == len(pr[5]) == ell) for pr in provers):
+        raise ValueError("provers in step share one vector length")
+    if any(type(x) is not G1Point for pr in provers for x in list(pr[:3]) + list(pr[3]) + list(pr[4])):
+        raise TypeError("crs_G_t, crs_G_u, crs_H and the entries of vec_R and vec_S are G1Points")
+    S, pb = N.MERLIN_STATE_BYTES, int(N.cg1_same_scalar_proof_bytes())
+    step = min(N.SAME_SCALAR_MAX_PROVERS, (N.LIGHT_MAX_BASES - 3) // (2 * ell))
+    out: List[tuple] = []
+    with table._ctx_lock():
+        if table._KIND != "fixed-base":
+            raise TypeError("the device chain of the same-scalar block runs on a FixedBaseTable's staging block and light-table scratch")
+        crs = bytes(points_to_affine96([x for pr in provers for x in pr[:3]]))
+        lo = 0
+        while lo < len(provers):
+            hi = lo + 1
+            while hi < len(provers) and hi - lo < step and crs[288 * hi: 288 * hi + 288] == crs[288 * lo: 288 * lo + 288]:
+                hi += 1
+            part, ts = provers[lo:hi], transcripts[lo:hi]
+            rs = [x for pr in part for x in list(pr[3]) + list(pr[4])]
+            certified = all(x._sg is True for x in rs)
+            proofs, new_states = table._ctx.same_scalar_prove_device(
+                table._tab, ell, len(part), crs[288 * lo: 288 * lo + 288], bytes(points_to_affine96(rs)), _pack32([a for pr in part for a in pr[5]]),
+                _pack32([pr[6] for pr in part]), _pack32([r for pr in part for r in pr[7:12]]), certified, b"".join(bytes(t.strobe._st.raw[:S]) for t in ts))
+            for i, t in enumerate(ts):
+                ctypes.memmove(t.strobe._st, new_states[S * i: S * i + S], S)
+                raw = proofs[pb * i: pb * i + pb]
+                T1, T2, U1, U2, R, S_, A1, A2, B1, B2 = (G1Point.from_compressed_bytes_unchecked(raw[48 * j: 48 * j + 48]) for j in range(10))
+                z_k, z_t, z_u = (Scalar.from_le_bytes(raw[480 + 32 * j: 512 + 32 * j]) for j in range(3))
+                out.append((R, S_, (T1, T2), (U1, U2), (A1, A2), (B1, B2), z_k, z_t, z_u))
+            lo = hi
+    return out
+
+
+def same_scalar_prove_device(table, crs_G_t: G1Point, crs_G_u: G1Point, crs_H: G1Point, vec_R: Sequence[G1Point], vec_S: Sequence[G1Point],
+                             vec_a: Sequence[Scalar], k: Scalar, r_t: Scalar, r_u: Scalar, r_a: Scalar, r_b: Scalar, r_k: Scalar, transcript):
+    """curdleproofs.py:92-116 after the draws r_t, r_u and r_a, r_b, r_k, on the device: see same_scalar_prove_device_many.  `transcript`
+    is advanced as the reference advances it.  -> (R, S, cm_T, cm_U, cm_A, cm_B, z_k, z_t, z_u), a commitment as the pair (T_1, T_2)."""
+    return same_scalar_prove_device_many(table, [(crs_G_t, crs_G_u, crs_H, vec_R, vec_S, vec_a, k, r_t, r_u, r_a, r_b, r_k)], [transcript])[0]

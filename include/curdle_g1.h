@@ -759,6 +759,54 @@ int cg1_same_perm_emulate(size_t ell, size_t n_blinders, uint8_t* state208, cons
                           uint8_t* out_challenges32, uint8_t* out_b32, uint8_t* out_gprod_result32, uint32_t* out_term_base, uint8_t* out_term_scalars32,
                           uint32_t* out_offsets, uint32_t* out_status);
 
+/* ---- The shuffle prover's same-scalar block PROVED on the device: what CurdleProofsProof.new runs between SamePermutationProof.new and
+ * SameMSMProof.new (curdleproofs.py:92-116) -- R = MSM(vec_R, vec_a), S = MSM(vec_S, vec_a), cm_T = GroupCommitment.new(G_t, H, R k, r_t),
+ * cm_U = GroupCommitment.new(G_u, H, S k, r_u) and all of SameScalarProof.new (same_scalar.py:39-69) after its three draws -- for n_provers
+ * independent provers of one ell in step, as ONE launch chain with one host wait (csrc/kernels_same_scalar.h, csrc/same_scalar_rounds.h).
+ * No base is ever multiplied on its own: R k = sum (k a_i) R_i and R r_k = sum (r_k a_i) R_i, so each of the ten points the block emits is an
+ * MSM over G_t | G_u | H | vec_R | vec_S.  The call builds ONE light table of 3 + n_provers 2 ell bases (the scratch kept with the cg1_fixed
+ * handle, shared with cg1_same_msm_prove_device and regrown only when too small; `tab` is the chain's home -- staging block, scratch, lock
+ * -- and G_t, G_u, H need not be among its bases) and runs ONE k_table_msm launch of 10 MSMs per prover, ONE k_fixed_finish and
+ * k_sscalar_step on both sides: upload | begin | the table's two build launches | [k_subgroup_row] | MSMs | finish | step: 6 launches, 7
+ * with the subgroup test.
+ *   sum (k a_i mod r) R_i = k (sum a_i R_i) holds only for bases of order r, and nothing here decodes or tests a point on the host:
+ *     bases_certified     0: the chain tests every vec_R | vec_S record on the device (k_subgroup_row; the all-zero identity record is in
+ *                         G1) and a record outside G1 REFUSES the call at its end: CG1_ERR_NOT_IN_SUBGROUP with its own text, status bit
+ *                         CG1_SAME_SCALAR_NOT_G1 of the chain's word -- never a trap, never wrong bytes.  1: the caller vouches that every
+ *                         record lies in G1 and the launch is skipped.
+ *   host buffers:
+ *     gth_affine96        G_t | G_u | H: three affine96 records, shared by all provers (any curve points)
+ *     rs_affine96         per prover vec_R | vec_S: 2 ell affine96 records (all-zero = the identity)
+ *     vec_a32 (ell per prover), k32 (1), blinders32 (5: r_t r_u r_a r_b r_k)   canonical scalars; the draws are the caller's, in the
+ *                         reference's order (r_t, r_u at curdleproofs.py:92-93, then r_a, r_b, r_k at same_scalar.py:39-41)
+ *     states208           in: the transcript where the block would find it; out: after same_scalar_alpha
+ *     out_proofs          cg1_same_scalar_proof_bytes() = 576 bytes each: cm_T | cm_U | R | S | cm_A | cm_B | z_k | z_t | z_u, a commitment
+ *                         as T_1 | T_2 -- CurdleProofsProof.to_bytes order without A, M and the other two arguments' proofs
+ *     out_clocks          NULL, or 4 words per prover: clock ticks of its lane 0 in the transcript | 0 | 0 | transcript programs run (2)
+ *   The returned status covers the whole call, and a refused call leaves out_proofs and states208 untouched.  Refused before anything is
+ *   written: a null pointer or a table of another device, ell outside 1 .. CG1_SAME_SCALAR_MAX_ELL (ell need not be a power of two), more
+ *   than CG1_SAME_SCALAR_MAX_PROVERS provers or 3 + n_provers 2 ell > CG1_LIGHT_MAX_BASES (REFUSED, not chunked -- the caller splits):
+ *   CG1_ERR_ARG; a scalar >= r: CG1_ERR_ENCODING (never reduced); a coordinate >= p or a point off the curve: cg1_from_affine96's status,
+ *   the text naming the prover and the entry.
+ * Limits: CG1_SAME_SCALAR_MAX_ELL = 1024: an MSM has ell + 1 terms <= CG1_LIGHT_MAX_TERMS and one prover's 2 ell light records are 256 MiB.
+ * CG1_SAME_SCALAR_MAX_PROVERS = 64: 10 MSMs per prover within CG1_LIGHT_MAX_MSMS, and 3 + 64 x 2 ell bases at ell = 124 fit the table.
+ *   cg1_same_scalar_emulate   host only, test support: the term schedule and the formulas compiled from the header the kernel runs
+ *                         (csrc/same_scalar_rounds.h), one prover whose vec_R starts at light-table index 3.  The terms of the ten MSMs in
+ *                         the transcript's order R, S, T.T_1, T.T_2, U.T_1, U.T_2, A.T_1, A.T_2, B.T_1, B.T_2 (6 ell + 8 terms, 11 offsets).
+ *                         With enc480 (the ten 48-byte encodings, validated like cd48 above) also the transcript step on state208 (in /
+ *                         out; untouched by a refused call): out_alpha32 and out_z96 = z_k | z_t | z_u.  enc480 NULL: state208, out_alpha32
+ *                         and out_z96 are not looked at.  The entry's refusals by shape and encoding. */
+#define CG1_SAME_SCALAR_NOT_G1     0x8000
+#define CG1_SAME_SCALAR_MAX_ELL     1024
+#define CG1_SAME_SCALAR_MAX_PROVERS 64
+size_t cg1_same_scalar_proof_bytes(void);                           /* 576 */
+int cg1_same_scalar_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_provers, const uint8_t* gth_affine96, const uint8_t* rs_affine96,
+                                 const uint8_t* vec_a32, const uint8_t* k32, const uint8_t* blinders32 /* r_t r_u r_a r_b r_k per prover */,
+                                 int bases_certified, uint8_t* states208, uint8_t* out_proofs, uint32_t* out_clocks /* nullable */);
+int cg1_same_scalar_emulate(size_t ell, const uint8_t* vec_a32, const uint8_t* k32, const uint8_t* blinders32, const uint8_t* enc480 /* nullable */,
+                            uint8_t* state208 /* nullable with enc480 */, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets,
+                            uint8_t* out_alpha32, uint8_t* out_z96);
+
 #ifdef __cplusplus
 }
 #endif
