@@ -172,6 +172,10 @@ cg1_batch_decompress_gpu = _proto("cg1_batch_decompress_gpu", c_int, c_void_p, _
 cg1_gen_scalars_device = _proto("cg1_gen_scalars_device", c_int, c_void_p, c_void_p, c_size_t, c_uint64)
 cg1_probe_madd = _proto("cg1_probe_madd", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int, POINTER(c_float))
 cg1_probe_add_chain = _proto("cg1_probe_add_chain", c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p, POINTER(c_float))
+cg1_probe_fp_ops = _proto("cg1_probe_fp_ops", c_int, c_void_p, c_int, c_int, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p)
+cg1_probe_g1_ops = _proto("cg1_probe_g1_ops", c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p)
+cg1_probe_fr_ops = _proto("cg1_probe_fr_ops", c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p)
+cg1_fr_ops_host = _proto("cg1_fr_ops_host", c_int, c_int, c_void_p, c_size_t, c_void_p)
 cg1_probe_mad_rate = _proto("cg1_probe_mad_rate", c_int, c_void_p, c_int, c_int, POINTER(ctypes.c_double))
 cg1_batch_sum_device = _proto("cg1_batch_sum_device", c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint32), c_size_t, c_void_p)
 cg1_batch_sum = _proto("cg1_batch_sum", c_int, c_void_p, _u8p, POINTER(ctypes.c_uint32), c_size_t, _buf)
@@ -321,7 +325,7 @@ EXPORTED_SYMBOLS = [
     "cg1_comm_create", "cg1_comm_port", "cg1_comm_rank", "cg1_comm_connect", "cg1_comm_set_timeout", "cg1_comm_attach_rccl", "cg1_comm_transport",
     "cg1_comm_world_seen", "cg1_comm_error", "cg1_comm_allgather", "cg1_comm_allgather_host", "cg1_comm_barrier", "cg1_comm_allreduce_g1", "cg1_comm_destroy",
     "cg1_validate_compressed", "cg1_fp_jacobi", "cg1_batch_decompress_pool", "cg1_batch_subgroup_pool", "cg1_batch_subgroup", "cg1_lincomb_batch", "cg1_lincomb_batch_pool", "cg1_glv_split", "cg1_batch_decompress_rows",
-    "cg1_probe_add_chain", "cg1_msm_blobs", "cg1_stage_reserve", "cg1_msm_blobs_device", "cg1_vec_create", "cg1_vec_destroy", "cg1_vec_len", "cg1_msm_vec", "cg1_batch_normalize", "cg1_batch_from_affine96", "cg1_get_last_launches", "cg1_plan_describe",
+    "cg1_probe_add_chain", "cg1_probe_fp_ops", "cg1_probe_g1_ops", "cg1_probe_fr_ops", "cg1_fr_ops_host", "cg1_msm_blobs", "cg1_stage_reserve", "cg1_msm_blobs_device", "cg1_vec_create", "cg1_vec_destroy", "cg1_vec_len", "cg1_msm_vec", "cg1_batch_normalize", "cg1_batch_from_affine96", "cg1_get_last_launches", "cg1_plan_describe",
     "cg1_fixed_create", "cg1_fixed_destroy", "cg1_fixed_len", "cg1_fixed_bytes", "cg1_fixed_msm", "cg1_fixed_msm_device", "cg1_fixed_digits",
     "cg1_ipa_proof_bytes", "cg1_ipa_prove_device", "cg1_ipa_round_emulate",
     "cg1_light_create", "cg1_light_destroy", "cg1_light_len", "cg1_light_bytes", "cg1_light_msm", "cg1_light_msm_device", "cg1_light_digits",

@@ -188,4 +188,73 @@ int cg1_probe_add_chain(cg1_ctx* ctx, int mode, const uint8_t* two_points_affine
   return CG1_OK;
 }
 
+// ---- the arithmetic probes: the device's field, group and scalar-field operations over operands taken AS GIVEN (host buffers; at most
+// 4 096 items per call).  The caller guarantees each operation's preconditions: nothing is normalised, reduced or exported on the way.
+//
+// in_limbs: n tuples of four raw 14-limb vectors a, b, c, d (unused ones ignored); out_limbs: n raw 14-limb results (to_words /
+// to_host_words: 12 words, then two zeros); out_flags: n words, is_zero_mod_p's answer.  form 0: one lane per tuple, fp28.h; form 1: one
+// DPP row per tuple, fp_row.h (four tuples per wave).  op: 0 mul (a b), 1 sqr (a a), 2 mul2 (a b + c d), 3 norm (fp_norm | two
+// row_norm_pass), 4 is_zero_mod_p(a, kmax), 5 inv (fp_inv | row_inv), 6 to_words, 7 to_host_words (form 0 only).  kmax: one of the
+// literals the product code itself passes -- 6, 8, 10 or 14 on one lane, 6 on rows (k_probe_fp_lane says why) -- and ignored by the other operations.
+int cg1_probe_fp_ops(cg1_ctx* ctx, int form, int op, uint32_t kmax, const uint32_t* in_limbs, size_t n, uint32_t* out_limbs, uint32_t* out_flags) {
+  if (!ctx) return CG1_ERR_HIP;
+  if (n == 0) return CG1_OK;
+  if (form < 0 || form > 1 || op < 0 || op > cg1::FPOP_TO_HOST_WORDS || (form == 1 && op >= cg1::FPOP_TO_WORDS) || n > 4096 || !in_limbs || !out_limbs || !out_flags)
+    return CG1_ERR_ARG;
+  if (op == cg1::FPOP_IS_ZERO && kmax != 6u && !(form == 0 && (kmax == 8u || kmax == 10u || kmax == 14u))) return CG1_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t in_bytes = n * cg1::FP_PROBE_TUPLE * 4, out_bytes = n * cg1::NL * 4;
+  DevBuf din, dout, dfl;
+  HIPCHK(din.alloc(in_bytes)); HIPCHK(dout.alloc(out_bytes)); HIPCHK(dfl.alloc(n * 4));
+  HIPCHK(hipMemcpy(din.p, in_limbs, in_bytes, hipMemcpyHostToDevice));
+  if (form == 0) hipLaunchKernelGGL(cg1::k_probe_fp_lane, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, (const uint32_t*)din.p, (uint32_t)n, op, kmax, (uint32_t*)dout.p, (uint32_t*)dfl.p);
+  else hipLaunchKernelGGL(cg1::k_probe_fp_row, dim3((unsigned)((n + 3) / 4)), dim3(64), 0, ctx->stream, (const uint32_t*)din.p, (uint32_t)n, op, (uint32_t*)dout.p, (uint32_t*)dfl.p);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out_limbs, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out_flags, dfl.p, n * 4, hipMemcpyDeviceToHost));
+  return CG1_OK;
+}
+
+// in_xyzz: n pairs of raw XYZZ records (CG1_PROBE_XYZZ_WORDS words each: X, Y, ZZ, ZZZ as 14 limbs, then `inf`, then padding), the second
+// of a pair unused by a doubling; out_xyzz: n such records, raw.  op 0: a + b, 1: 2 a.  form 0: xyzz_add / xyzz_dbl on one lane, 1: quad_add /
+// quad_dbl on a DPP quad, 2: row_add / row_dbl on a wave.
+int cg1_probe_g1_ops(cg1_ctx* ctx, int form, int op, const uint32_t* in_xyzz, size_t n, uint32_t* out_xyzz) {
+  static_assert(sizeof(cg1::PointSum) == 4 * CG1_PROBE_XYZZ_WORDS, "the probe's record is the device's XYZZ partial sum");
+  if (!ctx) return CG1_ERR_HIP;
+  if (n == 0) return CG1_OK;
+  if (form < 0 || form > 2 || op < 0 || op > 1 || n > 4096 || !in_xyzz || !out_xyzz) return CG1_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  DevBuf din, dout;
+  HIPCHK(din.alloc(2 * n * sizeof(cg1::PointSum))); HIPCHK(dout.alloc(n * sizeof(cg1::PointSum)));
+  HIPCHK(hipMemcpy(din.p, in_xyzz, 2 * n * sizeof(cg1::PointSum), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(dout.p, 0, n * sizeof(cg1::PointSum), ctx->stream));
+  const cg1::PointSum* pin = (const cg1::PointSum*)din.p;
+  cg1::PointSum* pout = (cg1::PointSum*)dout.p;
+  if (form == 0) hipLaunchKernelGGL((cg1::k_probe_g1<0>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, pin, (uint32_t)n, op, pout);
+  else if (form == 1) hipLaunchKernelGGL((cg1::k_probe_g1<1>), dim3((unsigned)((n + 15) / 16)), dim3(64), 0, ctx->stream, pin, (uint32_t)n, op, pout);
+  else hipLaunchKernelGGL((cg1::k_probe_g1<2>), dim3((unsigned)n), dim3(64), 0, ctx->stream, pin, (uint32_t)n, op, pout);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out_xyzz, dout.p, n * sizeof(cg1::PointSum), hipMemcpyDeviceToHost));
+  return CG1_OK;
+}
+
+// in: n items of 64 bytes, out: n items of 64 bytes (k_probe_fr, kernels_chain.h, has the layout and the operations; CG1_FR_OP_* of
+// include/curdle_g1.h).  The same operations over the host compilation of fr.h: cg1_fr_ops_host.
+int cg1_probe_fr_ops(cg1_ctx* ctx, int op, const uint8_t* in, size_t n, uint8_t* out) {
+  if (!ctx) return CG1_ERR_HIP;
+  if (n == 0) return CG1_OK;
+  if (op < 0 || op >= cg1chain::FROP_COUNT || n > 4096 || !in || !out) return CG1_ERR_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  DevBuf din, dout;
+  HIPCHK(din.alloc(64 * n)); HIPCHK(dout.alloc(64 * n));
+  HIPCHK(hipMemcpy(din.p, in, 64 * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(cg1chain::k_probe_fr, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, (const uint8_t*)din.p, (uint32_t)n, op, (uint8_t*)dout.p);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dout.p, 64 * n, hipMemcpyDeviceToHost));
+  return CG1_OK;
+}
+
 }  // extern "C"

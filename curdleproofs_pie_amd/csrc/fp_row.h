@@ -106,14 +106,33 @@ __device__ __forceinline__ uint32_t row_norm_pass(uint32_t t, uint32_t lane16) {
     t = row_down1((uint32_t)acc & LMASK) + (uint32_t)(acc >> 28);                    \
   }
 
-// a * b * 2^-392 mod-ish p: the value fp_mul(a, b) returns, nearly normal.  Requires max_limb(a) * max_limb(b) < 2^59.
+// The limb contract of a row product.  A lane accumulates ONE partial product per step, not a column of fourteen.  With
+// L = max_limb(a) max_limb(b) (+ max_limb(c) max_limb(d)) <= 13 * 2^56 and a carry-save limb t < 2^32 coming in, a step's acc is
+// L + t + m p_j < 13 * 2^56 + 2^32 + 2^56 (m and every limb of p are below 2^28), so acc >> 28 < 14 * 2^28 + 16, and the t it leaves --
+// that plus a 28-bit limb -- is below 15 * 2^28 + 16 < 2^32 again: by induction no acc, no acc >> 28 and no t wraps, whatever the limbs of
+// p.  The call sites below reach L = 9 * 2^56 (P P, R R, M M: limbs just under 3 * 2^28 on both sides) and 11 * 2^56 (row_mul2 of stage
+// 4 / stage 3: the same plus a nearly-normal limb against a limb of kp3 / kp6): the static_asserts.  tests/rowlane_model.py is this code in
+// plain ints with an assertion at every place that could wrap; tests/test_field_edges.py runs it at these maxima and at the bound itself,
+// tests/test_field_edges_gpu.py holds the device's limbs against the model's.  The value contract is fp_mul's: a b (+ c d) < p 2^392, so
+// the result is below 2p.
+constexpr uint64_t ROW_MUL_LIMB_BOUND = 13ull << 56;
+constexpr uint64_t row_kp_max(const uint32_t* t) { uint64_t m = 0; for (int i = 0; i < NL - 1; ++i) m = t[i] > m ? t[i] : m; return m; }
+constexpr uint64_t ROW_NN = (1ull << 28) + 3;                                                  // a nearly-normal limb
+constexpr uint64_t ROW_LAZY3 = ROW_NN + row_kp_max(D_KP3), ROW_LAZY12 = ROW_NN + row_kp_max(D_KP12);      // P, R | qx, sx
+static_assert(ROW_LAZY3 * ROW_LAZY3 <= ROW_MUL_LIMB_BOUND && 9 * ROW_NN * ROW_NN <= ROW_MUL_LIMB_BOUND, "row_add stage 2 (P P, R R), row_dbl stage 2 (M M)");
+static_assert(ROW_LAZY3 * ROW_LAZY12 + ROW_NN * row_kp_max(D_KP3) <= ROW_MUL_LIMB_BOUND, "row_add stage 4: R qx + PPP ns1");
+static_assert(3 * ROW_NN * ROW_LAZY12 + ROW_NN * row_kp_max(D_KP6) <= ROW_MUL_LIMB_BOUND, "row_dbl stage 3: M sx + W ny");
+
+// a * b * 2^-392 mod-ish p: the value fp_mul(a, b) returns, nearly normal.  Requires max_limb(a) * max_limb(b) <= 13 * 2^56 (above).
 __device__ __forceinline__ uint32_t row_mul(uint32_t a, uint32_t b, const RowK& k) {
   uint32_t t = 0;
   CG1_ROW_STEP(0) CG1_ROW_STEP(1) CG1_ROW_STEP(2) CG1_ROW_STEP(3) CG1_ROW_STEP(4) CG1_ROW_STEP(5) CG1_ROW_STEP(6)
   CG1_ROW_STEP(7) CG1_ROW_STEP(8) CG1_ROW_STEP(9) CG1_ROW_STEP(10) CG1_ROW_STEP(11) CG1_ROW_STEP(12) CG1_ROW_STEP(13)
+  // two passes: the first leaves limb <= 2^28 - 1 + 15, and a limb of exactly 2^28 wherever a zero digit sits under a carry (a sparse
+  // value: tests/test_field_edges_gpu.py has the class); the second brings every limb to <= 2^28
   return row_norm_pass(row_norm_pass(t, k.lane16), k.lane16);
 }
-// (a * b + c * d) * 2^-392: one reduction for both products (fp_mul2).  Requires max(a) max(b) + max(c) max(d) < 2^59.
+// (a * b + c * d) * 2^-392: one reduction for both products (fp_mul2).  Requires max(a) max(b) + max(c) max(d) <= 13 * 2^56 (above).
 __device__ __forceinline__ uint32_t row_mul2(uint32_t a, uint32_t b, uint32_t c, uint32_t d, const RowK& k) {
   uint32_t t = 0;
   CG1_ROW_STEP2(0) CG1_ROW_STEP2(1) CG1_ROW_STEP2(2) CG1_ROW_STEP2(3) CG1_ROW_STEP2(4) CG1_ROW_STEP2(5) CG1_ROW_STEP2(6)
@@ -459,5 +478,90 @@ __global__ void __launch_bounds__(64) k_probe_add_chain(const PreparedPoint* __r
     PointWords* dst = out + blockIdx.x;
     for (int c = 0; c < 4; ++c) for (int j = 0; j < 12; ++j) dst->w[c][j] = o.w[c][j];
     dst->inf = o.inf;
+  }
+}
+
+// ---- the arithmetic probes (cg1_probe_fp_ops / cg1_probe_g1_ops, capi_rows_probes.h): the field and group operations above and those of
+// fp28.h / g1_xyzz.h / g1_quad.h AS THE DEVICE RUNS THEM, over raw limb vectors taken as given (any lazy form the operation admits), raw
+// limbs out -- so that a test can put a chosen carry pattern or a chosen multiple of p in front of each of them.  Separate kernels:
+// nothing here is on a product path.
+__device__ __noinline__ uint32_t row_inv(uint32_t a, const RowK k);          // kernels_fixed.h
+
+enum : int { FPOP_MUL = CG1_FP_OP_MUL, FPOP_SQR = CG1_FP_OP_SQR, FPOP_MUL2 = CG1_FP_OP_MUL2, FPOP_NORM = CG1_FP_OP_NORM, FPOP_IS_ZERO = CG1_FP_OP_IS_ZERO,
+             FPOP_INV = CG1_FP_OP_INV, FPOP_TO_WORDS = CG1_FP_OP_TO_WORDS, FPOP_TO_HOST_WORDS = CG1_FP_OP_TO_HOST_WORDS };      // include/curdle_g1.h
+constexpr uint32_t FP_PROBE_TUPLE = 4u * NL;                                 // a tuple: four limb vectors a, b, c, d
+
+// fp_is_zero_mod_p's kmax is a literal at every call site of the product code (6, 8, 10, 14; row_is_zero_mod_p's: 6), and the optimiser
+// folds what it knows of an argument into the shared body before it inlines it: the probes pass literals from that set only -- all four on
+// one lane, row_add's 6 on rows -- so that no product kernel is compiled from anything else than before.
+__device__ __forceinline__ bool probe_is_zero(const fp& a, uint32_t kmax) {
+  return kmax == 6u ? fp_is_zero_mod_p(a, 6) : kmax == 8u ? fp_is_zero_mod_p(a, 8) : kmax == 10u ? fp_is_zero_mod_p(a, 10) : fp_is_zero_mod_p(a, 14);
+}
+__device__ __forceinline__ fp probe_load_fp(const uint32_t* src) { fp r; for (int i = 0; i < NL; ++i) r.l[i] = src[i]; return r; }
+
+// one lane per tuple: fp28.h
+__global__ void __launch_bounds__(64) k_probe_fp_lane(const uint32_t* __restrict__ in, uint32_t n, int op, uint32_t kmax, uint32_t* __restrict__ out,
+                                                      uint32_t* __restrict__ flags) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* src = in + (size_t)i * FP_PROBE_TUPLE;
+  const fp a = probe_load_fp(src), b = probe_load_fp(src + NL);
+  fp r = fp_zero();
+  uint32_t fl = 0;
+  if (op == FPOP_MUL) r = fp_mul(a, b);
+  else if (op == FPOP_SQR) r = fp_sqr(a);
+  else if (op == FPOP_MUL2) r = fp_mul2(a, b, probe_load_fp(src + 2 * NL), probe_load_fp(src + 3 * NL));
+  else if (op == FPOP_NORM) r = fp_norm(a);
+  else if (op == FPOP_IS_ZERO) fl = probe_is_zero(a, kmax) ? 1u : 0u;
+  else if (op == FPOP_INV) r = fp_inv(a);
+  else if (op == FPOP_TO_WORDS) fp_to_words(a, r.l);                          // 12 words; limbs 12, 13 stay zero
+  else fp_to_host_words(a, r.l);
+  for (int j = 0; j < NL; ++j) out[(size_t)i * NL + j] = r.l[j];
+  flags[i] = fl;
+}
+
+// one row per tuple, four tuples per wave.  Every lane of the wave runs every row product: a row past the end computes on the last
+// tuple, and only the store is guarded.
+__global__ void __launch_bounds__(64) k_probe_fp_row(const uint32_t* __restrict__ in, uint32_t n, int op, uint32_t* __restrict__ out,
+                                                     uint32_t* __restrict__ flags) {
+  const RowK k = row_constants();
+  const uint32_t i = blockIdx.x * 4u + k.row, l = k.lane16;
+  const uint32_t* src = in + (size_t)(i < n ? i : n - 1u) * FP_PROBE_TUPLE;
+  const uint32_t a = row_load14(src, l), b = row_load14(src + NL, l);
+  uint32_t r = 0, fl = 0;
+  if (op == FPOP_MUL) r = row_mul(a, b, k);
+  else if (op == FPOP_SQR) r = row_mul(a, a, k);
+  else if (op == FPOP_MUL2) r = row_mul2(a, b, row_load14(src + 2 * NL, l), row_load14(src + 3 * NL, l), k);
+  else if (op == FPOP_NORM) r = row_norm_pass(row_norm_pass(a, l), l);
+  else if (op == FPOP_IS_ZERO) fl = row_is_zero_mod_p(a, 6) ? 1u : 0u;
+  else r = row_inv(a, k);
+  if (i >= n) return;
+  if (l < (uint32_t)NL) out[(size_t)i * NL + l] = r;
+  if (l == 0u) flags[i] = fl;
+}
+
+// a + b (OP 0) or 2 a (OP 1) over raw XYZZ records: tuple i is the PointSum pair in[2 i], in[2 i + 1].  FORM 0: one lane per tuple
+// (xyzz_add / xyzz_dbl); 1: one DPP quad per tuple (quad_add / quad_dbl; a quad past the end computes on the last tuple); 2: one wave per
+// tuple, one limb per lane (row_add / row_dbl; the record comes back nearly normal, as row code stores it).
+template <int FORM>
+__global__ void __launch_bounds__(64) k_probe_g1(const PointSum* __restrict__ in, uint32_t n, int op, PointSum* __restrict__ out) {
+  if (FORM == 2) {
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;                                                      // (the whole wave)
+    const RowK k = row_constants();
+    const xyzz_row a = row_load_sum(in + 2 * (size_t)i, k.lane16), b = row_load_sum(in + 2 * (size_t)i + 1, k.lane16);
+    const xyzz_row r = op == 0 ? row_add(a, b, k) : row_dbl(a, k);
+    row_store_sum(out + i, r, k.lane16);
+  } else if (FORM == 1) {
+    const uint32_t i = blockIdx.x * 16u + (threadIdx.x >> 2), q = threadIdx.x & 3u;
+    const size_t t = i < n ? i : n - 1u;
+    const xyzz a = load_sum(in + 2 * t), b = load_sum(in + 2 * t + 1);
+    const xyzz r = op == 0 ? quad_add(a, b, q) : quad_dbl(a, q);
+    if (i < n && q == 0u) store_sum(out + i, r);
+  } else {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const xyzz a = load_sum(in + 2 * (size_t)i), b = load_sum(in + 2 * (size_t)i + 1);
+    store_sum(out + i, op == 0 ? xyzz_add(a, b) : xyzz_dbl(a));
   }
 }

@@ -1,7 +1,11 @@
 // BLS12-381 scalar field Fr (r = 0x73eda753...00000001, 255 bits): 4 x 64-bit limbs, Montgomery radix 2^256,
 // header-only, ONE source for the host (csrc/shuffle_verify.cpp) and the device (csrc/kernels_rows.h: the same functions
-// compiled __host__ __device__, so both sides produce the same bytes by construction; on the device only the product is tuned:
-// 32-bit limbs, round 3 -- a verification needs a few thousand Fr products against ~10^5 Fp products).
+// compiled __host__ __device__).  Everything but the product is the same code on both sides; the product, fr_mul, is a SEPARATE
+// implementation on the device (eight 32-bit limbs, round 3 -- a verification needs a few thousand Fr products against ~10^5 Fp
+// products), so "the same bytes" is a tested fact, not a construction: tests/test_field_edges_gpu.py runs every function here on the
+// device (cg1_probe_fr_ops) against Python ints and against the host compilation (cg1_fr_ops_host) byte for byte over an edge list --
+// non-canonical first operands of fr_mul that reach its ninth word, inputs that take fr_inv_binary through each of its tails -- and
+// tests/test_field_edges.py does the same for the host side alone.
 // Backs the verifier-side scalar work of the shuffle argument:
 // the reference does this with one Python `Scalar` object per operation over the Rust wheel
 // (py_arkworks_bls12381-stubs/__init__.pyi:32-54; ipa.py:164-186,216,227-229; same_msm.py:155-182,213;
@@ -73,7 +77,8 @@ CG1FR_HD fr fr_mul(const fr& a, const fr& b) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // device: the same CIOS over eight 32-bit limbs -- a step is one v_mad_u64_u32 and one 64-bit add (a 64 x 64 -> 128 product costs
   // four of them plus the carries of the 128-bit accumulations: 857 instructions per product against ~420 here).  The result is the
-  // canonical representative either way: the same bytes as the 64-bit code below.
+  // canonical representative either way: the same bytes as the 64-bit code below (tested: see the head of this file).  t9 is the
+  // carry out of word 8: zero for canonical operands, reached by the non-canonical first operands fr_from_le64_wide passes.
   uint32_t A[8], B[8], M[8], t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < 4; ++i) {

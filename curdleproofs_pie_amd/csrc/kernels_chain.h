@@ -26,6 +26,35 @@ struct StepLds {                             // a step kernel's transcript block
 __device__ __noinline__ fr inv_fermat(const fr& a) { return cg1fr::fr_inv(a); }
 __device__ __noinline__ fr inv_binary(const fr& a) { return cg1fr::fr_inv_binary(a); }
 
+// The Fr probe (cg1_probe_fr_ops, capi_rows_probes.h): one lane per item runs ONE operation of fr.h as compiled for the device -- the
+// 32-bit-limb product, the two inversions through the very wrappers the steps call -- over a 64-byte item, 64 bytes out: the result in
+// bytes 0..31, fr_from_le32's boolean as a word at byte 32.  mul, add, sub, neg, inv, inv_binary take and return raw Montgomery words
+// (mul: any 256-bit first operand); pow_u64: the exponent at byte 32.  The host twin is cg1_fr_ops_host (lazy_host.cpp).
+enum : int { FROP_MUL = CG1_FR_OP_MUL, FROP_ADD = CG1_FR_OP_ADD, FROP_SUB = CG1_FR_OP_SUB, FROP_NEG = CG1_FR_OP_NEG, FROP_FROM_LE32 = CG1_FR_OP_FROM_LE32,
+             FROP_FROM_LE64_WIDE = CG1_FR_OP_FROM_LE64_WIDE, FROP_TO_LE32 = CG1_FR_OP_TO_LE32, FROP_INV = CG1_FR_OP_INV, FROP_INV_BINARY = CG1_FR_OP_INV_BINARY,
+             FROP_POW_U64 = CG1_FR_OP_POW_U64, FROP_COUNT = CG1_FR_OP_COUNT };      // include/curdle_g1.h
+__global__ void __launch_bounds__(64) k_probe_fr(const uint8_t* __restrict__ in, uint32_t n, int op, uint8_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* src = in + 64 * (size_t)i;                       // (items are 64-byte aligned: the entry point allocates the buffers)
+  const uint64_t* w = reinterpret_cast<const uint64_t*>(src);
+  const fr a{{w[0], w[1], w[2], w[3]}}, b{{w[4], w[5], w[6], w[7]}};
+  fr r = cg1fr::fr_zero();
+  uint32_t ok = 1;
+  if (op == FROP_MUL) r = cg1fr::fr_mul(a, b);
+  else if (op == FROP_ADD) r = cg1fr::fr_add(a, b);
+  else if (op == FROP_SUB) r = cg1fr::fr_sub(a, b);
+  else if (op == FROP_NEG) r = cg1fr::fr_neg(a);
+  else if (op == FROP_FROM_LE32) ok = cg1fr::fr_from_le32(src, r) ? 1u : 0u;
+  else if (op == FROP_FROM_LE64_WIDE) r = cg1fr::fr_from_le64_wide(src);
+  else if (op == FROP_TO_LE32) cg1fr::fr_to_le32(a, reinterpret_cast<uint8_t*>(r.l));
+  else if (op == FROP_INV) r = inv_fermat(a);
+  else if (op == FROP_INV_BINARY) r = inv_binary(a);
+  else r = cg1fr::fr_pow_u64(a, b.l[0]);
+  uint64_t* o = reinterpret_cast<uint64_t*>(out + 64 * (size_t)i);
+  o[0] = r.l[0]; o[1] = r.l[1]; o[2] = r.l[2]; o[3] = r.l[3]; o[4] = ok; o[5] = 0; o[6] = 0; o[7] = 0;
+}
+
 __device__ inline void label(uint32_t* dst, const char* s, uint32_t n) {          // label words, little-endian, zero-padded to 32 bytes
   for (uint32_t j = 0; j < 8u; ++j) dst[j] = 0u;
   for (uint32_t j = 0; j < n; ++j) dst[j >> 2] |= (uint32_t)(uint8_t)s[j] << ((j & 3u) * 8u);

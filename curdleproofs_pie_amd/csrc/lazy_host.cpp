@@ -757,4 +757,33 @@ int cg1_same_scalar_emulate(size_t ell, const uint8_t* vec_a32, const uint8_t* k
   return CG1_OK;
 }
 
+// The operations of fr.h as compiled for the HOST over items taken as given: the twin of cg1_probe_fr_ops (k_probe_fr, kernels_chain.h,
+// has the layout), so that a test can hold the device's 32-bit-limb product and both inversions against these bytes.
+int cg1_fr_ops_host(int op, const uint8_t* in, size_t n, uint8_t* out) {
+  using cg1fr::fr;
+  if (n == 0) return CG1_OK;
+  if (op < 0 || op >= CG1_FR_OP_COUNT || !in || !out) return CG1_ERR_ARG;
+  for (size_t i = 0; i < n; ++i) {
+    const uint8_t* src = in + 64 * i;
+    fr a, b, r = cg1fr::fr_zero();
+    memcpy(a.l, src, 32); memcpy(b.l, src + 32, 32);
+    uint64_t ok = 1;
+    switch (op) {
+      case CG1_FR_OP_MUL: r = cg1fr::fr_mul(a, b); break;
+      case CG1_FR_OP_ADD: r = cg1fr::fr_add(a, b); break;
+      case CG1_FR_OP_SUB: r = cg1fr::fr_sub(a, b); break;
+      case CG1_FR_OP_NEG: r = cg1fr::fr_neg(a); break;
+      case CG1_FR_OP_FROM_LE32: ok = cg1fr::fr_from_le32(src, r) ? 1 : 0; break;
+      case CG1_FR_OP_FROM_LE64_WIDE: r = cg1fr::fr_from_le64_wide(src); break;
+      case CG1_FR_OP_TO_LE32: cg1fr::fr_to_le32(a, reinterpret_cast<uint8_t*>(r.l)); break;
+      case CG1_FR_OP_INV: r = cg1fr::fr_inv(a); break;
+      case CG1_FR_OP_INV_BINARY: r = cg1fr::fr_inv_binary(a); break;
+      default: r = cg1fr::fr_pow_u64(a, b.l[0]); break;                       // CG1_FR_OP_POW_U64
+    }
+    const uint64_t o[8] = {r.l[0], r.l[1], r.l[2], r.l[3], ok, 0, 0, 0};
+    memcpy(out + 64 * i, o, 64);
+  }
+  return CG1_OK;
+}
+
 }  // extern "C"

@@ -323,6 +323,46 @@ void cg1_glv_split(const uint8_t scalar32[32], uint8_t k1_16[16], uint8_t k2_16[
 int cg1_probe_add_chain(cg1_ctx* ctx, int mode, const uint8_t* two_points_affine96, size_t waves, int iters, int reps,
                         uint8_t* out_blob144, float* ms);
 
+/* The arithmetic probes: the device's base-field, group and scalar-field operations over operands taken AS GIVEN -- raw limbs / raw
+ * Montgomery words in, raw results out, nothing normalised or exported on the way -- so that a test can feed each of them the carry
+ * patterns, lazy forms and multiples of p its callers can reach (tests/test_field_edges_gpu.py).  Host buffers, n <= 4 096 per call; the
+ * caller guarantees the operation's preconditions.
+ * cg1_probe_fp_ops: in_limbs = n tuples of four 14-limb vectors a, b, c, d; out_limbs = n 14-limb results; out_flags = n words.  form 0 =
+ * one lane per tuple (csrc/fp28.h), 1 = one limb per lane, one DPP row per tuple (csrc/fp_row.h).  to_words / to_host_words: form 0 only,
+ * 12 words out (then two zero words).  is_zero_mod_p takes kmax = 6, 8, 10 or 14 on one lane and 6 on rows, the values the product code passes
+ * (CG1_ERR_ARG otherwise); the other operations ignore kmax.
+ * cg1_probe_g1_ops: in_xyzz = n pairs of XYZZ records of CG1_PROBE_XYZZ_WORDS words (X, Y, ZZ, ZZZ as 14 limbs each, then inf, then
+ * padding), out_xyzz = n records.  op 0 = a + b, 1 = 2 a.  form 0 = one lane (csrc/g1_xyzz.h), 1 = a DPP quad (csrc/g1_quad.h), 2 = a wave
+ * with one limb per lane (csrc/fp_row.h; limbs come back nearly normal, <= 2^28 + 3).
+ * cg1_probe_fr_ops / cg1_fr_ops_host: csrc/fr.h as compiled for the device / for the host, one operation over n items of 64 bytes, 64
+ * bytes out each: the result in bytes 0..31, from_le32's boolean as a 64-bit word at byte 32.  mul, add, sub, neg, inv, inv_binary take
+ * and return raw Montgomery words (operands at bytes 0 and 32; mul accepts any 256-bit first operand); from_le32 / to_le32 read bytes
+ * 0..31, from_le64_wide all 64; pow_u64 has its exponent at byte 32. */
+#define CG1_FP_OP_MUL 0
+#define CG1_FP_OP_SQR 1
+#define CG1_FP_OP_MUL2 2
+#define CG1_FP_OP_NORM 3
+#define CG1_FP_OP_IS_ZERO 4
+#define CG1_FP_OP_INV 5
+#define CG1_FP_OP_TO_WORDS 6
+#define CG1_FP_OP_TO_HOST_WORDS 7
+#define CG1_PROBE_XYZZ_WORDS 64
+#define CG1_FR_OP_MUL 0
+#define CG1_FR_OP_ADD 1
+#define CG1_FR_OP_SUB 2
+#define CG1_FR_OP_NEG 3
+#define CG1_FR_OP_FROM_LE32 4
+#define CG1_FR_OP_FROM_LE64_WIDE 5
+#define CG1_FR_OP_TO_LE32 6
+#define CG1_FR_OP_INV 7
+#define CG1_FR_OP_INV_BINARY 8
+#define CG1_FR_OP_POW_U64 9
+#define CG1_FR_OP_COUNT 10
+int cg1_probe_fp_ops(cg1_ctx* ctx, int form, int op, uint32_t kmax, const uint32_t* in_limbs, size_t n, uint32_t* out_limbs, uint32_t* out_flags);
+int cg1_probe_g1_ops(cg1_ctx* ctx, int form, int op, const uint32_t* in_xyzz, size_t n, uint32_t* out_xyzz);
+int cg1_probe_fr_ops(cg1_ctx* ctx, int op, const uint8_t* in, size_t n, uint8_t* out);
+int cg1_fr_ops_host(int op, const uint8_t* in, size_t n, uint8_t* out);
+
 /* ---------------- native Merlin transcript (host C++) ------------------------
  * Stands behind merlin_transcripts/merlin_transcripts/{merlin_transcript.py:6-24, strobe.py:16-107,
  * keccak.py:16-66} and curdleproofs/curdleproofs/curdleproofs_transcript.py:7-28.
