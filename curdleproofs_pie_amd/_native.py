@@ -306,6 +306,13 @@ cg1_same_scalar_prove_device = _proto("cg1_same_scalar_prove_device", c_int, c_v
 cg1_same_scalar_emulate = _proto("cg1_same_scalar_emulate", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p)
 SAME_SCALAR_NOT_G1, SAME_SCALAR_MAX_ELL, SAME_SCALAR_MAX_PROVERS = 0x8000, 1024, 64      # CG1_SAME_SCALAR_* of include/curdle_g1.h
+# a whole shuffle proof proved on the device (csrc/capi_shuffle.h, csrc/kernels_shuffle.h, csrc/shuffle_rounds.h)
+cg1_shuffle_prover_proof_bytes = _proto("cg1_shuffle_prover_proof_bytes", c_size_t, c_size_t)
+cg1_shuffle_prove_device = _proto("cg1_shuffle_prove_device", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                  c_void_p)
+cg1_shuffle_begin_emulate = _proto("cg1_shuffle_begin_emulate", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -333,6 +340,7 @@ EXPORTED_SYMBOLS = [
     "cg1_gprod_proof_bytes", "cg1_gprod_prove_device", "cg1_gprod_emulate",
     "cg1_same_perm_proof_bytes", "cg1_same_perm_prove_device", "cg1_same_perm_emulate",
     "cg1_same_scalar_proof_bytes", "cg1_same_scalar_prove_device", "cg1_same_scalar_emulate",
+    "cg1_shuffle_prover_proof_bytes", "cg1_shuffle_prove_device", "cg1_shuffle_begin_emulate",
 ]
 
 
@@ -615,6 +623,27 @@ class Context:
         return self._chain_prove_device(lambda ctx, t, _n, P, *rest: cg1_same_scalar_prove_device(ctx, t, ell, P, *rest[:5], 1 if bases_certified else 0, *rest[5:]),
                                         lambda _n: cg1_same_scalar_proof_bytes(), tab, ell, n_provers, (),
                                         (gth_affine96, rs_affine96, vec_a32, k32, blinders32), states208, want_clocks)
+
+    def shuffle_prove_device(self, tab: "FixedTable", ell: int, n_provers: int, g_index, h_index, u_index, gt_index, gu_index, gth_affine96: bytes,
+                             rs_affine96: bytes, tu_affine96: bytes, m48: bytes, perm, k32: bytes, vec_m_blinders32: bytes, vec_a_blinders32: bytes,
+                             vec_c_blinders32: bytes, ipa_r32: bytes, ipa_z_head32: bytes, blinders32: bytes, vec_r32: bytes, bases_certified: bool,
+                             want_clocks: bool = False):
+        """cg1_shuffle_prove_device: n_provers whole shuffle proofs of one ell (CurdleProofsProof.new, N_BLINDERS = 4) in one native call; the
+        index lists are table indices of crs.vec_G (ell per prover), crs.vec_H (4), crs.H, crs.G_t, crs.G_u (1 each); perm: n_provers * ell
+        ints in 0 .. 2^32 - 1; blinders32: r_t r_u r_a r_b r_k per prover.
+        -> the proofs as bytes [, clocks]; raises (check) on a refusal, and then nothing the caller holds has changed."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        P = n_provers
+        assert len(g_index) == ell * P and len(h_index) == 4 * P and len(u_index) == len(gt_index) == len(gu_index) == P and len(perm) == ell * P
+        assert len(gth_affine96) == 288 and len(rs_affine96) == len(tu_affine96) == 192 * ell * P and len(m48) == 48 * P
+        u32 = lambda v: (ctypes.c_uint32 * max(1, len(v)))(*v)
+        out = ctypes.create_string_buffer(max(1, int(cg1_shuffle_prover_proof_bytes(ell)) * P))
+        ck = (ctypes.c_uint32 * (4 * max(1, P)))() if want_clocks else None
+        self.check(cg1_shuffle_prove_device(self.handle, tab.handle, ell, P, u32(g_index), u32(h_index), u32(u_index), u32(gt_index), u32(gu_index), gth_affine96,
+                                            rs_affine96, tu_affine96, m48, u32(perm), k32, vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32,
+                                            blinders32, vec_r32, 1 if bases_certified else 0, out, ck))
+        return (out.raw, list(ck)) if want_clocks else out.raw
 
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""

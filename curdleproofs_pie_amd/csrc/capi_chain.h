@@ -8,13 +8,17 @@ namespace {
 // Byte offsets into a table handle's ONE staging block (t->h_chain, pinned, and its device twin t->d_chain: the same layout).  The calls
 // on a handle run under the context's lock and complete before they return, and each lays the block out afresh: nothing in it survives
 // from one call to the next.  Sections, in order: uploaded | uploaded and read back | read back (both: shared()) | device only.
+// A call that runs several arguments (capi_shuffle.h) lays their layouts end to end -- begin(base) -- with ONE states field in front of them
+// (shared(.., states_at)): every argument then uploads [up_begin, up_end) and downloads [down_begin, down_end) of its own.
 struct ChainLayout {
+  static constexpr size_t OWN_STATES = ~(size_t)0;
   size_t status = 0, clocks = 0, states = 0, proof = 0;     // zeros | zeros | the callers' states, up and down | the proofs, down
-  size_t up_end = 0, down_begin = 0, down_end = 0, total = 0;
+  size_t up_begin = 0, up_end = 0, down_begin = 0, down_end = 0, total = 0;
+  void begin(size_t base) { up_begin = total = base; }
   size_t take(size_t bytes) { const size_t at = total; total = (total + bytes + 63) & ~(size_t)63; return at; }
-  void shared(size_t P, size_t proof_bytes) {               // between the uploaded and the device-only fields
+  void shared(size_t P, size_t proof_bytes, size_t states_at = OWN_STATES) {      // between the uploaded and the device-only fields
     down_begin = total;
-    status = take(16); clocks = take(P * 16); states = take(P * 208);
+    status = take(16); clocks = take(P * 16); states = states_at == OWN_STATES ? take(P * 208) : states_at;
     up_end = total;
     proof = take(P * proof_bytes);
     down_end = total;
@@ -65,25 +69,45 @@ int chain_check_points(cg1_ctx* ctx, const char* who, const uint8_t* pts48, size
 }
 
 // ---- after the refusals: the block, laid out by L, with its shared upload fields filled (status and clocks zero, the states as given)
-int chain_stage(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L, size_t P, const uint8_t* states208, uint8_t*& H, uint8_t*& D) {
+int chain_reserve(cg1_ctx* ctx, cg1_fixed* t, size_t total, uint8_t*& H, uint8_t*& D) {
   HIPCHK(hipSetDevice(ctx->device));
   ctx->pend.active = false;
-  { const int rc = cg1::grow_pinned_pair(ctx, t->h_chain, nullptr, t->d_chain, t->cap_chain, L.total, L.total, hipHostMallocDefault); if (rc) return rc; }
+  { const int rc = cg1::grow_pinned_pair(ctx, t->h_chain, nullptr, t->d_chain, t->cap_chain, total, total, hipHostMallocDefault); if (rc) return rc; }
   H = t->h_chain; D = t->d_chain;
-  memset(H + L.status, 0, 16); memset(H + L.clocks, 0, P * 16);
+  return CG1_OK;
+}
+void chain_clear(uint8_t* H, const ChainLayout& L, size_t P) { memset(H + L.status, 0, 16); memset(H + L.clocks, 0, P * 16); }
+int chain_stage(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L, size_t P, const uint8_t* states208, uint8_t*& H, uint8_t*& D) {
+  if (const int rc = chain_reserve(ctx, t, L.total, H, D)) return rc;
+  chain_clear(H, L, P);
   memcpy(H + L.states, states208, P * 208);
   return CG1_OK;
 }
-// ---- after the last launch: one copy down, the one wait, the chain's status, and only then the caller's buffers.  own_status (optional):
-// the refusals of an argument whose step kernel sets status bits of its own, above k_table_msm's
+// the two copies of a layout, enqueued on the context's stream; nothing waits here
+int chain_upload(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L) {
+  HIPCHK(hipMemcpyAsync(t->d_chain + L.up_begin, t->h_chain + L.up_begin, L.up_end - L.up_begin, hipMemcpyHostToDevice, ctx->stream));
+  return CG1_OK;
+}
+int chain_download(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L) {
+  HIPCHK(hipMemcpyAsync(t->h_chain + L.down_begin, t->d_chain + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
+  return CG1_OK;
+}
+// the refusals of a chain whose status word has come down.  own_status (optional): those of an argument whose step kernel sets status
+// bits of its own, above k_table_msm's; `who` is the entry's name in their texts
+using ChainOwnStatus = int (*)(cg1_ctx*, const char* who, uint32_t);
+int chain_status_error(cg1_ctx* ctx, const uint8_t* H, const ChainLayout& L, const char* who, ChainOwnStatus own_status) {
+  const uint32_t st = reinterpret_cast<const uint32_t*>(H + L.status)[0];
+  { const int rc = table_status_error<FixedKind>(ctx, st); if (rc) return rc; }
+  return own_status ? own_status(ctx, who, st) : CG1_OK;
+}
+// ---- after the last launch: one copy down, the one wait, the chain's status, and only then the caller's buffers
 int chain_finish(cg1_ctx* ctx, cg1_fixed* t, const ChainLayout& L, size_t P, size_t proof_bytes, uint8_t* states208, uint8_t* out_proofs, uint32_t* out_clocks,
-                 int (*own_status)(cg1_ctx*, uint32_t) = nullptr) {
+                 const char* who = nullptr, ChainOwnStatus own_status = nullptr) {
   uint8_t* H = t->h_chain;
-  HIPCHK(hipMemcpyAsync(H + L.down_begin, t->d_chain + L.down_begin, L.down_end - L.down_begin, hipMemcpyDeviceToHost, ctx->stream));
+  if (const int rc = chain_download(ctx, t, L)) return rc;
   HIPCHK(hipStreamSynchronize(ctx->stream));                 // the one wait
   HIPCHK(hipGetLastError());
-  { const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
-  if (own_status) { const int rc = own_status(ctx, reinterpret_cast<const uint32_t*>(H + L.status)[0]); if (rc) return rc; }
+  if (const int rc = chain_status_error(ctx, H, L, who, own_status)) return rc;
   memcpy(out_proofs, H + L.proof, P * proof_bytes);
   memcpy(states208, H + L.states, P * 208);
   if (out_clocks) memcpy(out_clocks, H + L.clocks, P * 16);

@@ -8,13 +8,13 @@ static_assert(cg1sperm::ST_BAD_A == CG1_SAME_PERM_BAD_A && cg1sperm::ST_BAD_M ==
 
 namespace {
 // the refusals the step kernel can only report: the two of this argument, then the grand-product chain's own
-int same_perm_status_error(cg1_ctx* ctx, uint32_t st) {
+int same_perm_status_error(cg1_ctx* ctx, const char* who, uint32_t st) {
   const char* what = nullptr;
   if (st & cg1sperm::ST_BAD_A) what = "A is not the commitment MSM(crs_G_vec | crs_H_vec, vec_a∘permutation | vec_a_blinders)";
   else if (st & cg1sperm::ST_BAD_M) what = "M is not the commitment MSM(crs_G_vec | crs_H_vec, permutation | vec_m_blinders)";
   else what = gprod_status_text(st);
   if (!what) return CG1_OK;
-  snprintf(ctx->err, sizeof ctx->err, "cg1_same_perm_prove_device: %s", what);
+  snprintf(ctx->err, sizeof ctx->err, "%s: %s", who, what);
   return CG1_ERR_ARG;
 }
 }  // namespace

@@ -1,0 +1,228 @@
+// C ABI, part 15: a whole shuffle proof proved on the device -- CurdleProofsProof.new (curdleproofs.py:63-160) for n_provers shuffles of
+// one ell in step, as ONE native call: k_shuffle_begin (kernels_shuffle.h) and the head MSMs A | A', then the parts of the same-scalar
+// block (capi_same_scalar.h), the same-permutation chain (capi_gprod.h, capi_same_perm.h) and the same-MSM chain (capi_same_msm.h) on one
+// stream, with the two transcript heads that need a device result run on the host behind an event each, under device work already queued.
+// Part of the single translation unit csrc/msm_gpu.hip (included there; not a stand-alone header).
+#pragma once
+
+namespace {
+// the entry's own fields; the three arguments' layouts follow it in the block, behind the one states field
+struct ShuffleLayout : ChainLayout {
+  size_t perm, abl, gi_a, offs;                             // uploaded
+  size_t pts, st_head;                                      // read back: A | A' per prover, the head launch's status
+  size_t tb, sc;                                            // device only
+};
+ShuffleLayout shuffle_layout(size_t ell, size_t P, size_t base) {
+  ShuffleLayout L{};
+  L.begin(base);
+  const size_t n = ell + cg1shuffle::N_BLINDERS;
+  L.perm = L.take(P * ell * 4); L.abl = L.take(P * 2 * 32); L.gi_a = L.take(P * n * 4); L.offs = L.take((cg1shuffle::HEAD_MSMS * P + 1) * 4);
+  L.up_end = L.total;
+  L.down_begin = L.total;
+  L.pts = L.take(P * cg1shuffle::HEAD_MSMS * 48); L.st_head = L.take(16);
+  L.down_end = L.total;
+  L.tb = L.take(P * cg1shuffle::head_terms((uint32_t)n) * 4); L.sc = L.take(P * cg1shuffle::head_terms((uint32_t)n) * 32);
+  return L;
+}
+// run f(p) for every prover on the process's worker pool (the caller's thread takes part)
+template <typename F>
+void shuffle_for_provers(size_t P, F f) {
+  std::atomic<size_t> next{0};
+  const std::function<void()> work = [&] { for (size_t p; (p = next.fetch_add(1)) < P;) f(p); };
+  cg1::Pool& pool = cg1::Pool::get();
+  const size_t nt = std::min(P, pool.size() + 1);
+  if (nt <= 1) work(); else pool.run(work, nt);
+}
+struct ShuffleEvents {                                      // the two host waits of a call
+  hipEvent_t head = nullptr, mid = nullptr;
+  ~ShuffleEvents() { if (head) (void)hipEventDestroy(head); if (mid) (void)hipEventDestroy(mid); }
+};
+// after a refusal that came down in mid-pipeline: nothing of the call may still be running when the block is laid out afresh
+int shuffle_refuse(cg1_ctx* ctx, int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+}  // namespace
+
+extern "C" {
+size_t cg1_shuffle_prover_proof_bytes(size_t ell) {
+  const size_t n = ell + cg1shuffle::N_BLINDERS;
+  if (ell < 1 || n < ell || !chain_pow2(n) || n > CG1_SAME_MSM_MAX_N) return 0;
+  return 48 + 288 + cg1_same_perm_proof_bytes(ell, cg1shuffle::N_BLINDERS) + 288 + cg1_same_msm_proof_bytes(n);
+}
+
+int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
+                             const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* rs_affine96, const uint8_t* tu_affine96,
+                             const uint8_t* m48, const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32, const uint8_t* vec_a_blinders32,
+                             const uint8_t* vec_c_blinders32, const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* blinders32, const uint8_t* vec_r32,
+                             int bases_certified, uint8_t* out_proofs, uint32_t* out_clocks) {
+  static const char* const who = "cg1_shuffle_prove_device";
+  static const char* const hashed_m[] = {"M"};
+  constexpr size_t NB = cg1shuffle::N_BLINDERS;
+  if (!ctx) return CG1_ERR_HIP;
+  if (n_provers == 0) return CG1_OK;
+  // ---- 1. refusals: the whole call, before anything is written -- the entry's own, then the three arguments' on what they will see
+  const size_t P = n_provers, n = ell + NB;
+  const bool pointers_ok = g_index && h_index && u_index && gt_index && gu_index && gth_affine96 && rs_affine96 && tu_affine96 && m48 && perm && k32 &&
+                           vec_m_blinders32 && vec_a_blinders32 && vec_c_blinders32 && ipa_r32 && ipa_z_head32 && blinders32 && vec_r32 && out_proofs;
+  if (!t || t->device != ctx->device || !pointers_ok) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
+  const size_t pb = cg1_shuffle_prover_proof_bytes(ell);
+  if (!pb) { snprintf(ctx->err, sizeof ctx->err, "%s: ell + %zu must be a power of two in 8 .. %d", who, NB, CG1_SAME_MSM_MAX_N); return CG1_ERR_ARG; }
+  if (P > CG1_SAME_MSM_MAX_PROVERS || P * 2 * n > CG1_LIGHT_MAX_BASES) {
+    snprintf(ctx->err, sizeof ctx->err, "%s: more than %d provers, or more than %d bases T | U, in one call", who, CG1_SAME_MSM_MAX_PROVERS, CG1_LIGHT_MAX_BASES);
+    return CG1_ERR_ARG; }
+  // what the arguments take: vec_G | vec_H and vec_G | vec_H[:2] | G_t | G_u as index rows, vec_a_blinders | 0 | 0, and the same-MSM
+  // argument's vec_T | Z1 Z1 H Z1 | vec_U | Z1 Z1 Z1 H (the all-zero record is the identity)
+  std::vector<uint32_t> gi_a(P * n), gi_m(P * n);
+  std::vector<uint8_t> abl4(P * NB * 32, 0), tu(P * 2 * n * 96, 0), canon_m(P * 48), tu48;
+  for (size_t p = 0; p < P; ++p) {
+    memcpy(&gi_a[p * n], g_index + p * ell, ell * 4); memcpy(&gi_a[p * n + ell], h_index + p * NB, NB * 4);
+    memcpy(&gi_m[p * n], g_index + p * ell, ell * 4); memcpy(&gi_m[p * n + ell], h_index + p * NB, 2 * 4);
+    gi_m[p * n + ell + 2] = gt_index[p]; gi_m[p * n + ell + 3] = gu_index[p];
+    memcpy(&abl4[p * NB * 32], vec_a_blinders32 + p * 64, 64);
+    uint8_t* T = &tu[p * 2 * n * 96];
+    memcpy(T, tu_affine96 + p * 2 * ell * 96, ell * 96); memcpy(T + (ell + 2) * 96, gth_affine96 + 2 * 96, 96);
+    memcpy(T + n * 96, tu_affine96 + (p * 2 * ell + ell) * 96, ell * 96); memcpy(T + (n + ell + 3) * 96, gth_affine96 + 2 * 96, 96);
+  }
+  const SamePermHead sp{nullptr, nullptr, perm, abl4.data(), vec_m_blinders32};
+  if (const int rc = gprod_check(ctx, who, same_perm_status_error, t, true, ell, NB, P, gi_a.data(), u_index, &sp, m48, 1, hashed_m, canon_m.data(), nullptr, nullptr,
+                                 vec_c_blinders32, ipa_r32, ipa_z_head32)) return rc;
+  if (const int rc = sscalar_check(ctx, who, t, true, ell, P, gth_affine96, rs_affine96, nullptr, k32, blinders32)) return rc;
+  if (const int rc = smsm_check(ctx, who, t, true, n, P, gi_m.data(), nullptr, tu.data(), nullptr, vec_r32, nullptr, tu48)) return rc;
+  // the 2 ell encodings of vec_R | vec_S per prover, for curdleproofs_step1 (vec_T | vec_U: in tu48)
+  std::vector<uint8_t> rs48(P * 2 * ell * 48);
+  {
+    std::vector<uint8_t> blobs(P * 2 * ell * CG1_POINT_BYTES);
+    for (size_t b = 0; b < P * 2 * ell; ++b) (void)cg1_from_affine96(&blobs[b * CG1_POINT_BYTES], rs_affine96 + 96 * b, 0);
+    cg1_batch_compress(rs48.data(), blobs.data(), P * 2 * ell);
+  }
+
+  // ---- the block: states | the entry's fields | same-scalar | same-permutation | same-MSM, and everything a launch could otherwise
+  // allocate in mid-chain
+  ChainLayout C{};
+  const size_t states = C.take(P * 208);
+  const ShuffleLayout SH = shuffle_layout(ell, P, C.total);
+  const SscalarLayout SS = sscalar_layout(ell, P, SH.total, states);
+  GprodPlan gp = gprod_plan(ell, NB, P, true, SS.total, states);
+  const GprodLayout& GP = gp.L;
+  const size_t pb_msm = cg1_same_msm_proof_bytes(n);
+  const SmsmLayout SM = smsm_layout(n, P, pb_msm, GP.total, states);
+  uint8_t* H; uint8_t* D;
+  if (const int rc = chain_reserve(ctx, t, SM.total, H, D)) return rc;
+  const size_t bases_rs = cg1sscalar::SHARED_BASES + P * 2 * ell, bases_tu = P * 2 * n;
+  cg1_light* lt;
+  if (const int rc = chain_light_scratch(ctx, t, std::max(bases_rs, bases_tu), lt)) return rc;
+  const uint32_t Pn = (uint32_t)P, nn = (uint32_t)n, M0 = cg1shuffle::HEAD_MSMS * Pn;
+  const TableShape shape0 = table_pick_shape<FixedKind>(ctx, M0, nn);
+  TableShape shape_ss;
+  {
+    const size_t S = (nn + shape0.slice - 1) / shape0.slice, need = S > 1 ? (size_t)M0 * S : 0;
+    if (const int rc = cg1::grow_device(ctx, t->d_partial, t->cap_partial, need, need)) return rc;
+  }
+  if (const int rc = gprod_reserve(ctx, t, gp)) return rc;
+  if (const int rc = sscalar_reserve(ctx, lt, ell, P, shape_ss)) return rc;
+  if (const int rc = smsm_reserve(ctx, t, lt, n, P)) return rc;
+  ShuffleEvents ev;
+  HIPCHK(hipEventCreateWithFlags(&ev.head, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&ev.mid, hipEventDisableTiming));
+
+  // ---- 2. the head on the host, per prover: curdleproofs_step1 [vec_R + vec_S + vec_T + vec_U], M, curdleproofs_vec_a x ell
+  chain_clear(H, SS, P); chain_clear(H, GP, P); chain_clear(H, SM, P);
+  sscalar_stage(H, SS, ell, P, gth_affine96, rs_affine96, nullptr, k32, blinders32);
+  gprod_stage(H, gp, gi_a.data(), u_index, &sp, nullptr, nullptr, nullptr, vec_c_blinders32, ipa_r32, ipa_z_head32);
+  smsm_stage(H, SM, n, P, gi_m.data(), tu.data(), nullptr, vec_r32);
+  memcpy(H + SH.perm, perm, P * ell * 4); memcpy(H + SH.abl, vec_a_blinders32, P * 64); memcpy(H + SH.gi_a, gi_a.data(), P * n * 4);
+  for (uint32_t p = 0; p < Pn; ++p) cg1shuffle::head_offsets(nn, p * cg1shuffle::head_terms(nn), reinterpret_cast<uint32_t*>(H + SH.offs) + cg1shuffle::HEAD_MSMS * p);
+  shuffle_for_provers(P, [&](size_t p) {
+    static const uint8_t label[] = "curdleproofs", step1[] = "curdleproofs_step1", l_a[] = "curdleproofs_vec_a";
+    uint8_t* st = H + states + 208 * p;
+    std::vector<uint8_t> list(4 * ell * 48);
+    memcpy(&list[0], &rs48[p * 2 * ell * 48], 2 * ell * 48);
+    memcpy(&list[2 * ell * 48], &tu48[p * 2 * n * 48], ell * 48);
+    memcpy(&list[3 * ell * 48], &tu48[(p * 2 * n + n) * 48], ell * 48);
+    cg1_merlin_init(st, label, 12);
+    cg1_merlin_append_list(st, step1, 18, list.data(), 48, 4 * ell);
+    cg1_merlin_append(st, step1, 18, &canon_m[48 * p], 48);
+    for (size_t i = 0; i < ell; ++i) cg1_merlin_challenge_scalar(st, l_a, 18, H + SS.va + (p * ell + i) * 32);
+  });
+  if (const int rc = chain_upload(ctx, t, SH)) return rc;
+  if (const int rc = chain_upload(ctx, t, SS)) return rc;
+  if (const int rc = chain_upload(ctx, t, SM)) return rc;     // (its vx field goes up as it lies: k_shuffle_begin writes it next)
+
+  // ---- 3, 4. k_shuffle_begin, then A | A' as one launch over the CRS table; their encodings come down behind the first event
+  lt->n_bases = bases_rs;
+  const cg1sscalar::SscalarArgs ssa = sscalar_args(D, SS, ell, lt, bases_certified);
+  const cg1smsm::SmsmArgs sma = smsm_args(D, SM, n, pb_msm, t, lt);
+  {
+    cg1shuffle::ShuffleBeginArgs b;
+    b.ell = (uint32_t)ell;
+    b.va = ssa.va; b.perm = (const uint32_t*)(D + SH.perm); b.k = ssa.k; b.bl = ssa.bl; b.abl = (const uint64_t*)(D + SH.abl);
+    b.gi_a = (const uint32_t*)(D + SH.gi_a); b.gi_m = sma.gi;
+    b.tb = (uint32_t*)(D + SH.tb); b.sc = (uint64_t*)(D + SH.sc); b.vx = (uint64_t*)(D + SM.vx);
+    b.ss_tb = ssa.tb; b.ss_sc = ssa.sc;
+    hipLaunchKernelGGL(cg1shuffle::k_shuffle_begin, dim3(Pn), dim3(cg1shuffle::SH_THREADS), 0, ctx->stream, b);
+    if (const int rc = table_enqueue<FixedKind>(ctx, t, b.tb, (const uint32_t*)b.sc, (const uint32_t*)(D + SH.offs), M0, Pn * cg1shuffle::head_terms(nn), nn, shape0, false,
+                                                nullptr, D + SH.pts)) return shuffle_refuse(ctx, rc);
+  }
+  HIPCHK(hipMemcpyAsync(D + SH.st_head, t->d_status, 16, hipMemcpyDeviceToDevice, ctx->stream));
+  if (const int rc = chain_download(ctx, t, SH)) return shuffle_refuse(ctx, rc);
+  HIPCHK(hipEventRecord(ev.head, ctx->stream));
+
+  // ---- 5. behind it, without waiting: the same-scalar block's table and its ten MSMs per prover (k_shuffle_begin wrote their terms)
+  if (const int rc = sscalar_enqueue_msms(ctx, lt, D, SS, ssa, ell, P, bases_certified, shape_ss)) return shuffle_refuse(ctx, rc);
+
+  // ---- 6. the first wait; the same-permutation head on the host, under step 5, then its chain
+  HIPCHK(hipEventSynchronize(ev.head));
+  if (const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + SH.st_head)[0])) return shuffle_refuse(ctx, rc);
+  shuffle_for_provers(P, [&](size_t p) {
+    uint8_t am[96];
+    memcpy(am, H + SH.pts + p * 96, 48); memcpy(am + 48, &canon_m[48 * p], 48);
+    same_perm_head(H, gp, p, am, H + SS.va + p * ell * 32);
+  });
+  HIPCHK(hipMemcpyAsync(D + states, H + states, P * 208, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = chain_upload(ctx, t, GP)) return shuffle_refuse(ctx, rc);
+  const cg1sperm::SamePermArgs spa = gprod_args(ctx, t, D, gp, true);
+  if (const int rc = gprod_enqueue(ctx, t, D, gp, spa, true)) return shuffle_refuse(ctx, rc);
+
+  // ---- 7. the same-scalar block's step on the states the same-permutation chain left; both arguments come down behind the second event
+  hipLaunchKernelGGL(cg1sscalar::k_sscalar_step, dim3(Pn), dim3(cg1sscalar::SS_THREADS), 0, ctx->stream, ssa, cg1sscalar::SS_STEP);
+  HIPCHK(hipMemcpyAsync(H + states, D + states, P * 208, hipMemcpyDeviceToHost, ctx->stream));
+  if (const int rc = chain_download(ctx, t, GP)) return shuffle_refuse(ctx, rc);
+  if (const int rc = chain_download(ctx, t, SS)) return shuffle_refuse(ctx, rc);
+  HIPCHK(hipEventRecord(ev.mid, ctx->stream));
+
+  // ---- 8. behind it, without waiting: the same-MSM chain's begin and its table over T | U, into the scratch the R | S table has left
+  lt->n_bases = bases_tu;
+  smsm_enqueue_begin(ctx, lt, D, SM, sma, n, P);
+
+  // ---- 9. the second wait; same_msm_step1 [A', Z_t, Z_u] and the 2 n encodings on the host, under step 8, then the rest of the chain
+  HIPCHK(hipEventSynchronize(ev.mid));
+  if (const int rc = chain_status_error(ctx, H, GP, who, same_perm_status_error)) return shuffle_refuse(ctx, rc);
+  if (const int rc = chain_status_error(ctx, H, SS, who, same_scalar_status_error)) return shuffle_refuse(ctx, rc);
+  shuffle_for_provers(P, [&](size_t p) {
+    const uint8_t* ss = H + SS.proof + p * cg1sscalar::PROOF_BYTES;         // cm_T = T_1 | T_2, cm_U = U_1 | U_2, ...
+    uint8_t head[144];
+    memcpy(head, H + SH.pts + p * 96 + 48, 48); memcpy(head + 48, ss + 48, 48); memcpy(head + 96, ss + 144, 48);
+    smsm_absorb(H + states + 208 * p, head, &tu48[p * 2 * n * 48], n);
+  });
+  HIPCHK(hipMemcpyAsync(D + states, H + states, P * 208, hipMemcpyHostToDevice, ctx->stream));
+  if (const int rc = smsm_enqueue_rounds(ctx, t, lt, D, SM, sma, n, P)) return shuffle_refuse(ctx, rc);
+
+  // ---- 10. the last copy down, the stream wait, and only then the caller's buffers
+  if (const int rc = chain_download(ctx, t, SM)) return shuffle_refuse(ctx, rc);
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  if (const int rc = chain_status_error(ctx, H, SM, who, nullptr)) return rc;
+  const size_t pb_perm = gp.pb;
+  for (size_t p = 0; p < P; ++p) {                          // A | cm_T | cm_U | R | S | same_perm | cm_A | cm_B | z_k | z_t | z_u | same_msm
+    uint8_t* out = out_proofs + p * pb;
+    const uint8_t* ss = H + SS.proof + p * cg1sscalar::PROOF_BYTES;
+    memcpy(out, H + SH.pts + p * 96, 48);
+    memcpy(out + 48, ss, 288);
+    memcpy(out + 336, H + GP.proof + p * pb_perm, pb_perm);
+    memcpy(out + 336 + pb_perm, ss + 288, 288);
+    memcpy(out + 624 + pb_perm, H + SM.proof + p * pb_msm, pb_msm);
+  }
+  if (out_clocks)                                           // the three chains' clock words, summed
+    for (size_t i = 0; i < P * 4; ++i)
+      out_clocks[i] = reinterpret_cast<const uint32_t*>(H + SS.clocks)[i] + reinterpret_cast<const uint32_t*>(H + GP.clocks)[i] + reinterpret_cast<const uint32_t*>(H + SM.clocks)[i];
+  return CG1_OK;
+}
+}  // extern "C"

@@ -7,6 +7,7 @@
 #include "gprod_rounds.h"
 #include "same_perm_rounds.h"
 #include "same_scalar_rounds.h"
+#include "shuffle_rounds.h"
 #include "../../include/curdle_g1.h"
 
 #include <algorithm>
@@ -754,6 +755,42 @@ int cg1_same_scalar_emulate(size_t ell, const uint8_t* vec_a32, const uint8_t* k
   cg1fr::fr_to_le32(cg1sscalar::response(bl[4], k[0], alpha[0]), out_z96);
   cg1fr::fr_to_le32(cg1sscalar::response(bl[2], bl[0], alpha[0]), out_z96 + 32);
   cg1fr::fr_to_le32(cg1sscalar::response(bl[3], bl[1], alpha[0]), out_z96 + 64);
+  return CG1_OK;
+}
+
+// The formulas and the term schedule of k_shuffle_begin, the first kernel of a whole shuffle proof proved on the device
+// (csrc/shuffle_rounds.h: one lane per element there, a loop here; the same-scalar block's terms from csrc/same_scalar_rounds.h, one
+// prover whose vec_R starts at light-table index 3): for the CPU tests.  Any ell in 1 .. CG1_SAME_SCALAR_MAX_ELL, so that a test can
+// pass 256 elements, where a lane of the kernel owns two.
+int cg1_shuffle_begin_emulate(size_t ell, const uint8_t* vec_a32, const uint32_t* perm, const uint8_t* k32, const uint8_t* blinders32, const uint8_t* vec_a_blinders32,
+                              const uint32_t* gi_a, const uint32_t* gi_m, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets,
+                              uint8_t* out_vec_x32, uint32_t* out_ss_term_base, uint8_t* out_ss_term_scalars32, uint32_t* out_ss_offsets) {
+  using cg1fr::fr;
+  if (ell < 1 || ell > CG1_SAME_SCALAR_MAX_ELL) return CG1_ERR_ARG;
+  if (!vec_a32 || !perm || !k32 || !blinders32 || !vec_a_blinders32 || !gi_a || !gi_m || !out_term_base || !out_term_scalars32 || !out_offsets || !out_vec_x32 ||
+      !out_ss_term_base || !out_ss_term_scalars32 || !out_ss_offsets) return CG1_ERR_ARG;
+  for (size_t i = 0; i < ell; ++i)
+    if (perm[i] >= ell) return CG1_ERR_ARG;
+  bool ok = true;
+  auto load = [&](const uint8_t* src, size_t count) {
+    std::vector<fr> v(count);
+    for (size_t i = 0; i < count; ++i) ok = cg1fr::fr_from_le32(src + 32 * i, v[i]) && ok;
+    return v;
+  };
+  const std::vector<fr> va = load(vec_a32, ell), k = load(k32, 1), bl = load(blinders32, 5), abl = load(vec_a_blinders32, 2);      // bl: r_t r_u r_a r_b r_k
+  if (!ok) return CG1_ERR_ENCODING;
+  const uint32_t L = (uint32_t)ell, n = L + cg1shuffle::N_BLINDERS;
+  std::vector<uint64_t> a64(4 * ell), abl64(8), sc(4 * (size_t)cg1shuffle::head_terms(n)), vx(4 * (size_t)n), ss_sc(4 * (size_t)cg1sscalar::terms(L));
+  memcpy(a64.data(), vec_a32, 32 * ell); memcpy(abl64.data(), vec_a_blinders32, 64);
+  for (uint32_t j = 0; j < n; ++j)
+    cg1shuffle::head_term(gi_a, gi_m, n, L, j, cg1shuffle::x_elem(L, j, a64.data(), perm, abl64.data(), bl[0], bl[1]), out_term_base, sc.data(), vx.data());
+  memcpy(out_term_scalars32, sc.data(), sc.size() * 8);
+  memcpy(out_vec_x32, vx.data(), vx.size() * 8);
+  cg1shuffle::head_offsets(n, 0, out_offsets);
+  for (uint32_t j = 0; j < L; ++j) cg1sscalar::elem_terms(L, cg1sscalar::SHARED_BASES, j, va[j], k[0], bl[4], out_ss_term_base, ss_sc.data());
+  for (uint32_t w = 0; w < 4; ++w) cg1sscalar::blinder_terms(L, w, bl[w], out_ss_term_base, ss_sc.data());
+  memcpy(out_ss_term_scalars32, ss_sc.data(), ss_sc.size() * 8);
+  cg1sscalar::offsets(L, 0, out_ss_offsets);
   return CG1_OK;
 }
 

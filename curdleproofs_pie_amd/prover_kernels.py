@@ -527,3 +527,98 @@ def same_scalar_prove_device(table, crs_G_t: G1Point, crs_G_u: G1Point, crs_H: G
     """curdleproofs.py:92-116 after the draws r_t, r_u and r_a, r_b, r_k, on the device: see same_scalar_prove_device_many.  `transcript`
     is advanced as the reference advances it.  -> (R, S, cm_T, cm_U, cm_A, cm_B, z_k, z_t, z_u), a commitment as the pair (T_1, T_2)."""
     return same_scalar_prove_device_many(table, [(crs_G_t, crs_G_u, crs_H, vec_R, vec_S, vec_a, k, r_t, r_u, r_a, r_b, r_k)], [transcript])[0]
+
+
+def shuffle_draws(ell: int) -> tuple:
+    """The random draws of one CurdleProofsProof.new (N_BLINDERS = 4), made with the package's own randomness in the order the reference
+    makes them: vec_a_blinders (2, curdleproofs.py:73); the same-permutation callee's vec_c_blinders (4), ipa_r (n) and ipa_z_head (n - 2),
+    as same_permutation_prove_device takes them; r_t, r_u (:92-93); r_a, r_b, r_k (same_scalar.py:39-41); the same-MSM vec_r (n).
+    -> (vec_a_blinders, vec_c_blinders, ipa_r, ipa_z_head, r_t, r_u, r_a, r_b, r_k, vec_r), what shuffle_prove_device takes as `draws`."""
+    n = ell + N_BLINDERS
+    draw = lambda m: [random_scalar() for _ in range(m)]
+    vec_a_blinders, vec_c_blinders, ipa_r, ipa_z_head = draw(N_BLINDERS - 2), draw(N_BLINDERS), draw(n), draw(n - 2)
+    r_t, r_u, r_a, r_b, r_k = draw(5)
+    return (vec_a_blinders, vec_c_blinders, ipa_r, ipa_z_head, r_t, r_u, r_a, r_b, r_k, draw(n))
+
+
+def shuffle_prove_device_many(table, provers: Sequence[tuple]) -> List[bytes]:
+    """CurdleProofsProof.new (curdleproofs.py:63-160) for SEVERAL independent shuffles of one ell in step, proved ON THE DEVICE in one
+    native call per batch (csrc/capi_shuffle.h): the `curdleproofs` transcript is created inside the call, A and A' are table MSMs, and the
+    same-permutation, same-scalar and same-MSM arguments run as one pipeline with no Python between them.
+    provers[p] = (crs, vec_R, vec_S, vec_T, vec_U, M, permutation, k, vec_m_blinders, draws): crs is a CurdleproofsCrs whose vec_G, vec_H, H,
+    G_t and G_u are objects of `table` (FixedBaseTable.for_crs(crs)); the vectors are G1Points (deferred ones are materialised in one batch;
+    the identity included); M is a G1Point or its 48-byte encoding; permutation holds ell ints (not required to be a bijection); draws as
+    shuffle_draws(ell) returns them -- the caller's, in the reference's order.  ell + 4 is a power of two in 8 .. 1024.  More provers than
+    one call carries, or a change of CRS points, starts another call.  No input is mutated.
+    vec_R / vec_S must lie in G1: where every one of a call's entries already carries a membership certificate the call says so, otherwise
+    the chain tests them on the device.
+    -> per prover CurdleProofsProof.to_bytes(), byte for byte what the reference writes for those inputs and draws.
+    A refused call changes nothing.  ValueError / TypeError: a shape or a type.  NativeError: a scalar >= r, a point off the curve, a
+    vec_R / vec_S entry outside G1, a permutation entry >= ell, an M that is not the commitment to permutation | vec_m_blinders, and the
+    divisions by zero of generate_ipa_blinders."""
+    from . import _native as N
+    from .py_arkworks_bls12381 import points_to_affine96, points_to_compressed
+
+    provers = [tuple(pr) for pr in provers]
+    if not provers:
+        return []
+    if any(len(pr) != 10 for pr in provers):
+        raise ValueError("a prover is (crs, vec_R, vec_S, vec_T, vec_U, M, permutation, k, vec_m_blinders, draws)")
+    ell = len(provers[0][1])
+    n = ell + N_BLINDERS
+    if ell < 1 or n & (n - 1) or n > N.SAME_MSM_MAX_N:
+        raise ValueError(f"a shuffle proof has ell + {N_BLINDERS} a power of two in 8 .. {N.SAME_MSM_MAX_N}, not ell = {ell}")
+    for pr in provers:
+        crs, dr = pr[0], tuple(pr[9])
+        if not (len(pr[1]) == len(pr[2]) == len(pr[3]) == len(pr[4]) == len(pr[6]) == len(crs.vec_G) == ell and len(crs.vec_H) == N_BLINDERS == len(pr[8])):
+            raise ValueError("provers in step share one ell; the four vectors, the permutation and crs.vec_G have ell entries, crs.vec_H and vec_m_blinders 4")
+        if len(dr) != 10 or not (len(dr[0]) == 2 and len(dr[1]) == N_BLINDERS and len(dr[2]) == n and len(dr[3]) == n - 2 and len(dr[9]) == n):
+            raise ValueError("draws are (vec_a_blinders (2), vec_c_blinders (4), ipa_r (n), ipa_z_head (n - 2), r_t, r_u, r_a, r_b, r_k, vec_r (n))")
+        if any(not isinstance(m, int) or not 0 <= m < 1 << 32 for m in pr[6]):
+            raise ValueError("a permutation holds ints in 0 .. 2^32 - 1")
+        if any(type(x) is not G1Point for v in pr[1:5] for x in v) or any(type(x) is not G1Point for x in (crs.H, crs.G_t, crs.G_u)):
+            raise TypeError("crs.G_t, crs.G_u, crs.H and the entries of vec_R, vec_S, vec_T and vec_U are G1Points")
+        if any(type(x) is not Scalar for x in [pr[7], *pr[8], *dr[0], *dr[1], *dr[2], *dr[3], *dr[4:9], *dr[9]]):
+            raise TypeError("k, vec_m_blinders and the draws are Scalars")
+    enc = iter(points_to_compressed([pr[5] for pr in provers if type(pr[5]) is G1Point]))
+    m48 = [bytes(pr[5]) if type(pr[5]) is not G1Point else next(enc) for pr in provers]
+    if any(len(e) != 48 for e in m48):
+        raise ValueError("M is a G1Point or a 48-byte encoding")
+    pb = int(N.cg1_shuffle_prover_proof_bytes(ell))
+    step = min(N.SAME_MSM_MAX_PROVERS, N.LIGHT_MAX_BASES // (2 * n))
+    out: List[bytes] = []
+    with table._ctx_lock():
+        if table._KIND != "fixed-base":
+            raise TypeError("the device pipeline of a shuffle proof runs over a FixedBaseTable")
+        gth = bytes(points_to_affine96([x for pr in provers for x in (pr[0].G_t, pr[0].G_u, pr[0].H)]))
+        lo = 0
+        while lo < len(provers):
+            hi = lo + 1
+            while hi < len(provers) and hi - lo < step and gth[288 * hi: 288 * hi + 288] == gth[288 * lo: 288 * lo + 288]:
+                hi += 1
+            part = provers[lo:hi]
+            gi, hi_, ui, gti, gui, perm = [], [], [], [], [], []
+            for pr in part:
+                crs = pr[0]
+                gi.extend(table._indices(crs.vec_G, ell)); hi_.extend(table._indices(crs.vec_H, N_BLINDERS))
+                ui.extend(table._indices([crs.H], 1)); gti.extend(table._indices([crs.G_t], 1)); gui.extend(table._indices([crs.G_u], 1))
+                perm.extend(pr[6])
+            rs = [x for pr in part for x in list(pr[1]) + list(pr[2])]
+            tu = [x for pr in part for x in list(pr[3]) + list(pr[4])]
+            certified = all(x._sg is True for x in rs)
+            dr = [tuple(pr[9]) for pr in part]
+            proofs = table._ctx.shuffle_prove_device(
+                table._tab, ell, len(part), gi, hi_, ui, gti, gui, gth[288 * lo: 288 * lo + 288], bytes(points_to_affine96(rs)), bytes(points_to_affine96(tu)),
+                b"".join(m48[lo:hi]), perm, _pack32([pr[7] for pr in part]), _pack32([b for pr in part for b in pr[8]]), _pack32([b for d in dr for b in d[0]]),
+                _pack32([b for d in dr for b in d[1]]), _pack32([b for d in dr for b in d[2]]), _pack32([b for d in dr for b in d[3]]),
+                _pack32([b for d in dr for b in d[4:9]]), _pack32([b for d in dr for b in d[9]]), certified)
+            out.extend(proofs[pb * i: pb * i + pb] for i in range(len(part)))
+            lo = hi
+    return out
+
+
+def shuffle_prove_device(table, crs, vec_R: Sequence[G1Point], vec_S: Sequence[G1Point], vec_T: Sequence[G1Point], vec_U: Sequence[G1Point], M,
+                         permutation: Sequence[int], k: Scalar, vec_m_blinders: Sequence[Scalar], draws: tuple) -> bytes:
+    """CurdleProofsProof.new(crs, vec_R, vec_S, vec_T, vec_U, M, permutation, k, vec_m_blinders).to_bytes() with the caller's `draws`
+    (shuffle_draws(ell)), on the device: see shuffle_prove_device_many."""
+    return shuffle_prove_device_many(table, [(crs, vec_R, vec_S, vec_T, vec_U, M, permutation, k, vec_m_blinders, draws)])[0]

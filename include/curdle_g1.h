@@ -847,6 +847,50 @@ int cg1_same_scalar_emulate(size_t ell, const uint8_t* vec_a32, const uint8_t* k
                             uint8_t* state208 /* nullable with enc480 */, uint32_t* out_term_base, uint8_t* out_term_scalars32, uint32_t* out_offsets,
                             uint8_t* out_alpha32, uint8_t* out_z96);
 
+/* ---- A whole shuffle proof PROVED on the device: CurdleProofsProof.new (curdleproofs.py:63-160) for n_provers shuffles of one ell in
+ * step, as ONE native call -- instances, permutations, k and the draws in, n_provers times CurdleProofsProof.to_bytes() out.  N_BLINDERS = 4
+ * is fixed; n = ell + 4 is a power of two in 8 .. CG1_SAME_MSM_MAX_N; n_provers <= CG1_SAME_MSM_MAX_PROVERS and n_provers 2 n <=
+ * CG1_LIGHT_MAX_BASES (64 provers at ell = 124).  The call creates the `curdleproofs` transcript itself; it takes none.
+ * The pipeline (csrc/capi_shuffle.h; one stream, two event waits and the stream wait at its end):
+ *   host     curdleproofs_step1 [vec_R + vec_S + vec_T + vec_U], M, the ell challenges curdleproofs_vec_a -- per prover, on the process's
+ *            worker pool
+ *   device   k_shuffle_begin (csrc/kernels_shuffle.h, csrc/shuffle_rounds.h): the terms of A and A', vec_x, the terms of the same-scalar
+ *            block's ten MSMs; then A = MSM(vec_G | vec_H, a o perm | a_blinders | 0 | 0) and A' = MSM(vec_G | vec_H[:2] | G_t | G_u,
+ *            a o perm | a_blinders | r_t | r_u) = A + cm_T.T_1 + cm_U.T_1 as ONE k_table_msm launch; then, without a wait, the
+ *            same-scalar block's light table and MSMs
+ *   host     (first wait: A) the same-permutation head; device: its chain (cg1_same_perm_prove_device's), then the same-scalar block's step
+ *            on the states that chain left; then, without a wait, the same-MSM chain's begin and its light table over
+ *            vec_T | O O H O | vec_U | O O O H
+ *   host     (second wait: cm_T, cm_U) same_msm_step1 [A', Z_t, Z_u] and the 2 n encodings; device: the rest of the same-MSM chain
+ *   per prover p, host buffers:
+ *     g_index (ell), h_index (4), u_index, gt_index, gu_index (1 each)   table indices of crs.vec_G, crs.vec_H, crs.H, crs.G_t, crs.G_u
+ *     gth_affine96        G_t | G_u | H: three affine96 records, shared by all provers
+ *     rs_affine96, tu_affine96   per prover vec_R | vec_S and vec_T | vec_U: 2 ell affine96 records each (all-zero = the identity)
+ *     m48                 M, 48 bytes; perm: ell entries < ell (not required to be a bijection); k32: the scalar k
+ *     vec_m_blinders32 (4)   the blinders of M;  the draws, in the reference's order:  vec_a_blinders32 (2) | vec_c_blinders32 (4),
+ *     ipa_r32 (n), ipa_z_head32 (n - 2) as cg1_same_perm_prove_device takes them | blinders32 (5: r_t r_u r_a r_b r_k) | vec_r32 (n)
+ *     bases_certified     as cg1_same_scalar_prove_device's: 1 only when every vec_R | vec_S record is known to lie in G1
+ *     out_proofs          cg1_shuffle_prover_proof_bytes(ell) bytes each: A | cm_T | cm_U | R | S | same_perm | cm_A | cm_B | z_k | z_t | z_u |
+ *                         same_msm -- the verifier's wire proof (cg1_shuffle_proof_bytes of a CRS handle) without its leading M
+ *     out_clocks          NULL, or 4 words per prover: the three chains' clock words, summed
+ *   The returned status covers the whole call, and a refused call leaves out_proofs untouched.  The refusals are those of the three
+ *   entries above, run on the arguments they see, each text with this entry's name: CG1_ERR_ARG for a shape, a null pointer, an index
+ *   outside the table, a perm entry >= ell, an M that is not the commitment to perm | vec_m_blinders (CG1_SAME_PERM_BAD_M) and the
+ *   grand-product chain's own; CG1_ERR_ENCODING for a scalar >= r; cg1_from_affine96's / cg1_validate_compressed's status for a point;
+ *   CG1_ERR_NOT_IN_SUBGROUP for a vec_R | vec_S record outside G1.
+ *   cg1_shuffle_begin_emulate   host only, test support: the formulas and term schedule compiled from the header k_shuffle_begin runs, one
+ *                         prover, any ell in 1 .. CG1_SAME_SCALAR_MAX_ELL: the 2 n terms of A | A' (3 offsets), vec_x (n), and the same-scalar
+ *                         block's 6 ell + 8 terms (11 offsets) as cg1_same_scalar_emulate lays them out.  A perm entry >= ell: CG1_ERR_ARG. */
+size_t cg1_shuffle_prover_proof_bytes(size_t ell);                  /* 0 when ell + 4 is not a power of two in 8 .. CG1_SAME_MSM_MAX_N */
+int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
+                             const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* rs_affine96, const uint8_t* tu_affine96,
+                             const uint8_t* m48, const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32, const uint8_t* vec_a_blinders32,
+                             const uint8_t* vec_c_blinders32, const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* blinders32, const uint8_t* vec_r32,
+                             int bases_certified, uint8_t* out_proofs, uint32_t* out_clocks /* nullable */);
+int cg1_shuffle_begin_emulate(size_t ell, const uint8_t* vec_a32, const uint32_t* perm, const uint8_t* k32, const uint8_t* blinders32 /* r_t r_u r_a r_b r_k */,
+                              const uint8_t* vec_a_blinders32 /* 2 */, const uint32_t* gi_a, const uint32_t* gi_m, uint32_t* out_term_base, uint8_t* out_term_scalars32,
+                              uint32_t* out_offsets, uint8_t* out_vec_x32, uint32_t* out_ss_term_base, uint8_t* out_ss_term_scalars32, uint32_t* out_ss_offsets);
+
 #ifdef __cplusplus
 }
 #endif
