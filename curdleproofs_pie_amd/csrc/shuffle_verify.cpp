@@ -785,6 +785,68 @@ extern "C" {
 // 1 (default): proofs are prepared cg1m::G at a time with batched Keccak permutations; 0: one transcript at a time
 void cg1_shuffle_set_grouped(int on) { g_grouped.store(on ? 1 : 0); }
 
+// Test support: an operation list over 1..G transcripts through cg1m::Group, the way prepare_group drives it (one operation at a
+// time over all of them).  Only what Group takes: appends of at most 64 bytes and scalar challenges.
+int cg1_merlin_group_run(const uint8_t* label, size_t label_len, const cg1_merlin_op* ops, size_t nops, const uint8_t* data,
+                         size_t data_stride, uint8_t* out, size_t out_stride, uint8_t* states, size_t n) {
+  if (n < 1 || n > (size_t)cg1m::G || label_len > 32 || (nops && !ops)) return CG1_ERR_ARG;
+  auto c_label = [](const uint8_t* src, size_t len, char dst[33]) {        // Group takes C strings: no zero byte inside
+    for (size_t i = 0; i < len; ++i)
+      if (!src[i]) return false;
+    memcpy(dst, src, len);
+    dst[len] = 0;
+    return true;
+  };
+  char lab[33];
+  if (!c_label(label, label_len, lab)) return CG1_ERR_ARG;
+  for (size_t i = 0; i < nops; ++i) {
+    const cg1_merlin_op& op = ops[i];
+    char t[33];
+    if (op.label_len > 32 || !c_label(op.label, op.label_len, t)) return CG1_ERR_ARG;
+    if (op.kind == 0) {
+      if (op.len > 64 || (size_t)op.data_off + op.len > data_stride || (op.len && !data)) return CG1_ERR_ARG;
+    } else if (op.kind == 2) {
+      if (op.len != 32 || (size_t)op.out_off + 32 > out_stride || !out) return CG1_ERR_ARG;
+    } else {
+      return CG1_ERR_ARG;
+    }
+  }
+  cg1m::Group tr;
+  tr.init(lab, (int)n);
+  uint8_t flags = 0;
+  {
+    uint8_t one[CG1_MERLIN_STATE_BYTES];
+    cg1_merlin_init(one, label, label_len);
+    flags = one[202];
+  }
+  const uint8_t* ptrs[cg1m::G];
+  uint8_t tmp[cg1m::G][32];
+  static const uint8_t none[8] = {0};
+  for (size_t i = 0; i < nops; ++i) {
+    const cg1_merlin_op& op = ops[i];
+    char t[33];
+    c_label(op.label, op.label_len, t);
+    if (op.kind == 0) {
+      for (size_t k = 0; k < n; ++k) ptrs[k] = op.len ? data + k * data_stride + op.data_off : none;
+      tr.append(t, ptrs, op.len);
+    } else {
+      tr.challenge_scalar(t, tmp);
+      for (size_t k = 0; k < n; ++k) memcpy(out + k * out_stride + op.out_off, tmp[k], 32);
+    }
+    flags = cg1m::FLAG_A;                                                  // both end in ad(.., more = false)
+  }
+  if (states)
+    for (size_t k = 0; k < n; ++k) {
+      uint8_t* s = states + k * CG1_MERLIN_STATE_BYTES;
+      memset(s, 0, CG1_MERLIN_STATE_BYTES);
+      memcpy(s, tr.st[k], 200);
+      s[200] = tr.pos[k];
+      s[201] = tr.pos_begin[k];
+      s[202] = flags;
+    }
+  return CG1_OK;
+}
+
 
 cg1_shuffle_crs* cg1_shuffle_crs_create(const uint8_t* crs_bytes, size_t ell, size_t n_blinders) {
   if (n_blinders != NB || ell == 0) return nullptr;

@@ -453,6 +453,14 @@ int cg1_merlin_last_kernel(const cg1_ctx* ctx);
  * consume, walked the way they walk them); CG1_ERR_ARG when the operation list does not fit the row format. */
 int cg1_merlin_block_program_emulate(const uint8_t* init_state208, const cg1_merlin_op* ops, size_t nops, const uint8_t* data_row, size_t data_bytes,
                                      uint8_t* out_row, size_t out_bytes, uint8_t* state_out208 /* may be NULL */, uint32_t* passes);
+/* Host only, test support: n (1..16) transcripts, all MerlinTranscript(label), run IN STEP through the grouped host path of
+ * cg1_shuffle_prepare (csrc/merlin_group.h: one operation at a time over all of them, Keccak-f eight at a time).  Takes what that path
+ * takes and nothing else: kind 0 with len <= 64, kind 2, labels without a zero byte; anything else is CG1_ERR_ARG.  Transcript k
+ * reads data + k * data_stride and writes its 32-byte challenges to out + k * out_stride (at each op's out_off) and, when states is
+ * given, its final blob to states + k * 208 (byte 202, the current operation's flags, which the group does not keep: what either
+ * operation leaves there). */
+int cg1_merlin_group_run(const uint8_t* label, size_t label_len, const cg1_merlin_op* ops, size_t nops, const uint8_t* data,
+                         size_t data_stride, uint8_t* out, size_t out_stride, uint8_t* states /* may be NULL */, size_t n);
 int cg1_merlin_batch_device(cg1_ctx* ctx, const uint8_t* init_state208, const cg1_merlin_op* ops, size_t nops, const void* d_data,
                             size_t data_stride, void* d_out, size_t out_stride, void* d_states_out, size_t n);
 
