@@ -266,8 +266,9 @@ int cg1_opening_prepare_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96
 namespace {
 // The fixed-base tables of kernels_generator.h / kernels_fixed.h: for bases B_0 .. B_{m-1} (host affine96 records) entry
 // (b * GEN_WINDOWS + w) * GEN_HALF + (d - 1) = d * 2^(c w) * B_b as prepared records -- the scalars d * 2^(c w) through k_batch_mul (one
-// lane per entry, double-and-add with the complete formulas: exact for ANY curve point, where k_batch_mul_quad's table {P, 2P, 3P} takes
-// 3P as finite), then k_prepare_points (all-zero products, the identity, become flagged records).  All bases of a table in one call,
+// lane per entry, double-and-add with the complete formulas: exact for ANY curve point, as k_batch_mul_quad is since its table
+// {P, 2P, 3P} knows an identity 3P; which of the two is quicker at these launch sizes has not been measured), then k_prepare_points
+// (all-zero products, the identity, become flagged records).  All bases of a table in one call,
 // up to 32 of them (131 072 entries) per launch pair.  Synchronous; *out_tab is the caller's to free.
 int build_fixed_table(cg1_ctx* ctx, const uint8_t* bases96, size_t m, cg1::PreparedPoint** out_tab) {
   constexpr size_t E = cg1::GEN_ENTRIES, CHUNK = 32;
@@ -363,8 +364,9 @@ int cg1_opening_prove_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96, 
                      blinders32 ? (const uint8_t*)d_bl : (const uint8_t*)nullptr, seed, n32, (int32_t)CG1_SHUFFLE_BAD_POINT, (int32_t)CG1_SHUFFLE_BAD_SCALAR,
                      (int32_t)CG1_OPENING_BAD_BLINDER, d_gsc, (int32_t*)d_st);
   launch_generator_mul(ctx, d_gsc, 2 * n, nullptr, d_gen48);                               // [k_G ...][A ...]
-  // B = b r_G: k_batch_mul (one lane per proof, xyzz_dbl / xyzz_madd, exact for any curve point).  Not k_batch_mul_quad, which
-  // cg1_batch_mul_add_device picks for small n: its table {P, 2P, 3P} takes 3P as finite, and r_G may have order 3 (T3 = (0, 2)).
+  // B = b r_G: k_batch_mul (one lane per proof, xyzz_dbl / xyzz_madd, exact for any curve point: r_G may have order 3, T3 = (0, 2)).
+  // k_batch_mul_quad, which cg1_batch_mul_add_device picks for small n, is exact for such a base too (its table {P, 2P, 3P} knows an
+  // identity 3P; tests/test_curve_mul_gpu.py); this launch stays on the lane kernel, unmeasured against the quads.
   hipLaunchKernelGGL(cg1::k_batch_mul, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, (const uint32_t*)d_aff, n32, (const uint32_t*)(d_gsc + 32 * n), n32,
                      (const uint32_t*)nullptr, (uint32_t*)d_b96, n32);
   hipLaunchKernelGGL(cg1::k_batch_compress, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t*)d_b96, d_b48, n32);

@@ -67,11 +67,14 @@ __global__ void __launch_bounds__(64) k_batch_mul_quad(const uint32_t* __restric
     const xyzz P1 = xyzz_from_affine(fp_to_mont(fp_from_words(w)), fp_to_mont(fp_from_words(w + 12)));
     const xyzz P2 = quad_dbl(P1, q);
     const xyzz P3 = quad_add(P2, P1, q);
+    // P1 and P2 are finite (the curve has odd order: no point of order 2), but 3P is the identity for a base of order 3, and the entry
+    // picked below carries no flag: the digits whose entry is finite, as a bit mask, so that a digit 3 of such a base adds nothing
+    const uint32_t finite = P3.inf ? 0x6u : 0xeu;
 #pragma unroll 1
     for (int pair = 127; pair >= 0; --pair) {
       acc = quad_dbl(quad_dbl(acc, q), q);
       const uint32_t d = (s[pair >> 4] >> ((pair & 15) * 2)) & 3u;
-      if (d) {                                            // uniform inside the quad (its 4 lanes hold the same scalar)
+      if ((finite >> d) & 1u) {                           // uniform inside the quad (its 4 lanes hold the same scalar)
         xyzz T;
 #pragma unroll
         for (int k = 0; k < NL; ++k) {

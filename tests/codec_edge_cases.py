@@ -188,6 +188,39 @@ def chain_events(order):
     return ev
 
 
+# ------------------------------------------------------------------ points of small order (shared with tests/curve_mul_cases.py)
+def curve_point(rng):
+    """A point of E(Fp) drawn with rng: almost surely of full order h * r, outside G1."""
+    while True:
+        x = rng.randrange(P)
+        y = O.fp_sqrt((x * x * x + 4) % P)
+        if y is not None:
+            return (x, y if rng.randrange(2) else P - y)
+
+
+def small_order_points(rng):
+    """{ell: [t, t']} for every ell of SMALL_PRIMES: two different points of order ell, drawn with rng (order 3 is T3 itself)."""
+    small = {}
+    for ell in SMALL_PRIMES:
+        # the cofactor group is Z/((z-1)/3) x Z/(z-1): its ell-part is (Z/ell)^2, so R * (h / ell^2) maps a curve point into it
+        got = []
+        for _ in range(MAX_STEPS):
+            t = mul_any(curve_point(rng), O.R * (H_COF // (ell * ell)))
+            if t is None:
+                continue
+            assert O.g1_is_on_curve(t) and mul_any(t, ell) is None
+            # independent of the first: checked for ell = 11; for the larger ell a second random element of (Z/ell)^2 lies in the
+            # first's span with probability 1 / ell < 10^-4, and a dependent pair would only repeat a case, not weaken one
+            if got and ell == 11 and any(mul_any(got[0], k) == t for k in range(ell)):
+                continue
+            got.append(t)
+            if len(got) == 2:
+                break
+        assert len(got) == 2 and got[0] != got[1], ell
+        small[ell] = got
+    return small
+
+
 # ------------------------------------------------------------------ everything, once
 class Cases:
     pass
@@ -253,38 +286,15 @@ def cases():
     assert all(O.g1_is_on_curve(p) for p in c.valid_points)
 
     # ---- points for the subgroup tests
-    def curve_point():
-        while True:
-            x = rng.randrange(P)
-            y = O.fp_sqrt((x * x * x + 4) % P)
-            if y is not None:
-                return (x, y if rng.randrange(2) else P - y)
-
     c.g1 = [O.g1_mul(O.G1_GEN, rng.randrange(1, O.R)) for _ in range(6)]
     c.fillers = [O.g1_add(c.g1[1], c.g1[2])]
     while len(c.fillers) < 170:
         c.fillers.append(O.g1_add(c.fillers[-1], c.g1[3]))
-    wild = [curve_point() for _ in range(6)]
+    wild = [curve_point(rng) for _ in range(6)]
     sub = [("g1", p) for p in c.g1] + [("identity", None)] + [("wild", p) for p in wild] + [("t3", T3)]
-    small = {}
+    small = small_order_points(rng)
     for ell in SMALL_PRIMES:
-        # the cofactor group is Z/((z-1)/3) x Z/(z-1): its ell-part is (Z/ell)^2, so R * (h / ell^2) maps a curve point into it
-        got = []
-        for _ in range(MAX_STEPS):
-            t = mul_any(curve_point(), O.R * (H_COF // (ell * ell)))
-            if t is None:
-                continue
-            assert O.g1_is_on_curve(t) and mul_any(t, ell) is None
-            # independent of the first: checked for ell = 11; for the larger ell a second random element of (Z/ell)^2 lies in the
-            # first's span with probability 1 / ell < 10^-4, and a dependent pair would only repeat a case, not weaken one
-            if got and ell == 11 and any(mul_any(got[0], k) == t for k in range(ell)):
-                continue
-            got.append(t)
-            if len(got) == 2:
-                break
-        assert len(got) == 2 and got[0] != got[1], ell
-        small[ell] = got
-        sub += [(f"order {ell}", t) for t in got]
+        sub += [(f"order {ell}", t) for t in small[ell]]
     i = 0
     for ell in SMALL_PRIMES:
         for t in small[ell]:
