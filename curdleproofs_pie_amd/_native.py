@@ -314,6 +314,14 @@ cg1_shuffle_prove_device = _proto("cg1_shuffle_prove_device", c_int, c_void_p, c
                                   c_void_p)
 cg1_shuffle_begin_emulate = _proto("cg1_shuffle_begin_emulate", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+# GenerateWhiskShuffleProof from tracker bytes (csrc/capi_whisk_shuffle.h, csrc/kernels_whisk_shuffle.h; the host twin: csrc/lazy_host.cpp)
+cg1_whisk_shuffle_proof_bytes = _proto("cg1_whisk_shuffle_proof_bytes", c_size_t, c_size_t)
+cg1_whisk_shuffle_front = _proto("cg1_whisk_shuffle_front", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p)
+cg1_whisk_shuffle_prove_device = _proto("cg1_whisk_shuffle_prove_device", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+cg1_whisk_shuffle_front_emulate = _proto("cg1_whisk_shuffle_front_emulate", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p)
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -342,6 +350,7 @@ EXPORTED_SYMBOLS = [
     "cg1_same_perm_proof_bytes", "cg1_same_perm_prove_device", "cg1_same_perm_emulate",
     "cg1_same_scalar_proof_bytes", "cg1_same_scalar_prove_device", "cg1_same_scalar_emulate",
     "cg1_shuffle_prover_proof_bytes", "cg1_shuffle_prove_device", "cg1_shuffle_begin_emulate",
+    "cg1_whisk_shuffle_proof_bytes", "cg1_whisk_shuffle_front", "cg1_whisk_shuffle_prove_device", "cg1_whisk_shuffle_front_emulate",
 ]
 
 
@@ -645,6 +654,41 @@ class Context:
                                             rs_affine96, tu_affine96, m48, u32(perm), k32, vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32,
                                             blinders32, vec_r32, 1 if bases_certified else 0, out, ck))
         return (out.raw, list(ck)) if want_clocks else out.raw
+
+    def whisk_shuffle_front(self, tab: "FixedTable", ell: int, n_provers: int, g_index, h_index, trackers96: bytes, perm, k32: bytes, vec_m_blinders32: bytes):
+        """cg1_whisk_shuffle_front: everything GenerateWhiskShuffleProof does in front of CurdleProofsProof.new, for n_provers shuffles of one
+        ell, on the device with one wait.  trackers96: ell records r_G48 | k_r_G48 per prover.
+        -> (rs_affine96, tu_affine96, post96, m48) as bytes; raises (check) on a refusal."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        P = n_provers
+        assert len(g_index) == ell * P and len(h_index) == 4 * P and len(perm) == ell * P and len(trackers96) == 96 * ell * P and len(k32) == 32 * P
+        assert len(vec_m_blinders32) == 128 * P
+        u32 = lambda v: (ctypes.c_uint32 * max(1, len(v)))(*v)
+        rs, tu = ctypes.create_string_buffer(max(1, 192 * ell * P)), ctypes.create_string_buffer(max(1, 192 * ell * P))
+        post, m48 = ctypes.create_string_buffer(max(1, 96 * ell * P)), ctypes.create_string_buffer(max(1, 48 * P))
+        self.check(cg1_whisk_shuffle_front(self.handle, tab.handle, ell, P, u32(g_index), u32(h_index), trackers96, u32(perm), k32, vec_m_blinders32, rs, tu, post, m48))
+        return rs.raw[: 192 * ell * P], tu.raw[: 192 * ell * P], post.raw[: 96 * ell * P], m48.raw[: 48 * P]
+
+    def whisk_shuffle_prove_device(self, tab: "FixedTable", ell: int, n_provers: int, g_index, h_index, u_index, gt_index, gu_index, gth_affine96: bytes,
+                                   trackers96: bytes, perm, k32: bytes, vec_m_blinders32: bytes, vec_a_blinders32: bytes, vec_c_blinders32: bytes, ipa_r32: bytes,
+                                   ipa_z_head32: bytes, blinders32: bytes, vec_r32: bytes):
+        """cg1_whisk_shuffle_prove_device: n_provers GenerateWhiskShuffleProof calls of one ell in one native call; the arguments are
+        shuffle_prove_device's with the pre-shuffle tracker bytes (ell records r_G48 | k_r_G48 per prover) in place of the four point vectors and M.
+        -> (post96, proofs): ell records T_i48 | U_i48 and cg1_whisk_shuffle_proof_bytes(ell) bytes M || proof per prover; raises (check) on a
+        refusal, and then nothing the caller holds has changed."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        P = n_provers
+        assert len(g_index) == ell * P and len(h_index) == 4 * P and len(u_index) == len(gt_index) == len(gu_index) == P and len(perm) == ell * P
+        assert len(gth_affine96) == 288 and len(trackers96) == 96 * ell * P
+        u32 = lambda v: (ctypes.c_uint32 * max(1, len(v)))(*v)
+        wb = int(cg1_whisk_shuffle_proof_bytes(ell))
+        post, out = ctypes.create_string_buffer(max(1, 96 * ell * P)), ctypes.create_string_buffer(max(1, wb * P))
+        self.check(cg1_whisk_shuffle_prove_device(self.handle, tab.handle, ell, P, u32(g_index), u32(h_index), u32(u_index), u32(gt_index), u32(gu_index), gth_affine96,
+                                                  trackers96, u32(perm), k32, vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32, blinders32,
+                                                  vec_r32, post, out))
+        return post.raw[: 96 * ell * P], out.raw[: wb * P]
 
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""

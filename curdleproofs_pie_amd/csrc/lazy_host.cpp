@@ -8,6 +8,7 @@
 #include "same_perm_rounds.h"
 #include "same_scalar_rounds.h"
 #include "shuffle_rounds.h"
+#include "whisk_shuffle_host.h"
 #include "../../include/curdle_g1.h"
 
 #include <algorithm>
@@ -820,6 +821,60 @@ int cg1_fr_ops_host(int op, const uint8_t* in, size_t n, uint8_t* out) {
     const uint64_t o[8] = {r.l[0], r.l[1], r.l[2], r.l[3], ok, 0, 0, 0};
     memcpy(out + 64 * i, o, 64);
   }
+  return CG1_OK;
+}
+
+// The host twin of cg1_whisk_shuffle_front (capi_whisk_shuffle.h) for ONE prover, over the host G1 code (host_g1.cpp): the same
+// refusals in the same order with the same texts (whisk_shuffle_host.h), the same layouts out.  For the CPU tests.
+int cg1_whisk_shuffle_front_emulate(size_t ell, const uint8_t* trackers96, const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32,
+                                    const uint8_t* gh_affine96, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96, uint8_t* out_post96, uint8_t* out_m_scalars32,
+                                    uint8_t* out_m48, char* out_err256) {
+  static const char* const who = "cg1_whisk_shuffle_front_emulate";
+  char local[256];
+  char* err = out_err256 ? out_err256 : local;
+  err[0] = 0;
+  if (!trackers96 || !perm || !k32 || !vec_m_blinders32 || !out_rs_affine96 || !out_tu_affine96 || !out_post96 || !out_m_scalars32 || (gh_affine96 && !out_m48)) {
+    snprintf(err, 256, "%s: bad argument", who);
+    return CG1_ERR_ARG;
+  }
+  if (const int rc = cg1whisk_host::check_shape(err, 256, who, ell)) return rc;
+  if (const int rc = cg1whisk_host::check_inputs(err, 256, who, ell, 1, perm, k32, vec_m_blinders32)) return rc;
+  const size_t n = ell + cg1whisk_host::N_BLINDERS;
+  // ---- decode (unchecked: the decoder's leniency), then the subgroup test, each in tracker order
+  std::vector<uint8_t> pts(2 * ell * CG1_POINT_BYTES), tmp(CG1_POINT_BYTES);          // vec_R | vec_S
+  for (int pass = 0; pass < 2; ++pass)
+    for (size_t i = 0; i < ell; ++i)
+      for (int half = 0; half < 2; ++half) {
+        uint8_t* dst = pass == 0 ? &pts[(half * ell + i) * CG1_POINT_BYTES] : tmp.data();
+        const int rc = cg1_decompress(dst, trackers96 + 96 * i + 48 * half, pass);
+        if (rc != CG1_OK) return cg1whisk_host::refuse_point(err, 256, who, 0, i, half, rc);
+      }
+  // ---- M = MSM(vec_G | vec_H, perm | vec_m_blinders), before anything is written
+  std::vector<uint8_t> row(32 * n), m_enc(48);
+  cg1whisk_host::m_scalar_row(ell, perm, vec_m_blinders32, row.data());
+  if (gh_affine96) {
+    uint8_t acc[CG1_POINT_BYTES], base[CG1_POINT_BYTES], term[CG1_POINT_BYTES];
+    cg1_identity(acc);
+    for (size_t j = 0; j < n; ++j) {
+      const int rc = cg1_from_affine96(base, gh_affine96 + 96 * j, 1);
+      if (rc != CG1_OK) { snprintf(err, 256, "%s: entry %zu of vec_G | vec_H is not a curve point (status %d)", who, j, rc); return rc; }
+      cg1_mul(term, base, &row[32 * j]);
+      cg1_add(acc, acc, term);
+    }
+    cg1_compress(m_enc.data(), acc);
+  }
+  // ---- the outputs
+  cg1_batch_to_affine96(out_rs_affine96, pts.data(), 2 * ell);
+  std::vector<uint8_t> tu(2 * ell * CG1_POINT_BYTES);
+  for (size_t h = 0; h < 2; ++h)
+    for (size_t i = 0; i < ell; ++i) {
+      uint8_t* dst = &tu[(h * ell + i) * CG1_POINT_BYTES];
+      cg1_mul(dst, &pts[(h * ell + perm[i]) * CG1_POINT_BYTES], k32);
+      cg1_compress(out_post96 + 96 * i + 48 * h, dst);
+    }
+  cg1_batch_to_affine96(out_tu_affine96, tu.data(), 2 * ell);
+  memcpy(out_m_scalars32, row.data(), 32 * n);
+  if (gh_affine96) memcpy(out_m48, m_enc.data(), 48);
   return CG1_OK;
 }
 

@@ -79,6 +79,7 @@ int pick_window(size_t n);
 #include "kernels_same_perm.h"     // k_same_perm_begin: the same-permutation argument's head in front of k_gprod_step's step phase
 #include "kernels_same_scalar.h"   // k_sscalar_step: the same-scalar block's two phases around its one MSM launch
 #include "kernels_shuffle.h"       // k_shuffle_begin: the terms of a whole shuffle proof that depend on no later challenge than vec_a
+#include "kernels_whisk_shuffle.h" // k_whisk_permute_mul: the post-shuffle trackers of a Whisk shuffle, k vec_R | k vec_S through the permutation
 #include "host_context.h"          // Ctx: streams, helper threads, scratch buffers
 #include "host_chains.h"           // planner + launch chains: regime A, k_msm_small, regime B
 #include "capi_core_msm.h"         // cg1_* : host operators, context, memory, parameters, MSM entry points
@@ -97,3 +98,4 @@ int pick_window(size_t n);
 #include "capi_same_perm.h"        // the same-permutation argument proved on the device: cg1_same_perm_prove_device
 #include "capi_same_scalar.h"      // the same-scalar block proved on the device: cg1_same_scalar_prove_device
 #include "capi_shuffle.h"          // a whole shuffle proof proved on the device: cg1_shuffle_prove_device
+#include "capi_whisk_shuffle.h"    // GenerateWhiskShuffleProof from tracker bytes: cg1_whisk_shuffle_front, cg1_whisk_shuffle_prove_device

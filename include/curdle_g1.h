@@ -899,6 +899,46 @@ int cg1_shuffle_begin_emulate(size_t ell, const uint8_t* vec_a32, const uint32_t
                               const uint8_t* vec_a_blinders32 /* 2 */, const uint32_t* gi_a, const uint32_t* gi_m, uint32_t* out_term_base, uint8_t* out_term_scalars32,
                               uint32_t* out_offsets, uint8_t* out_vec_x32, uint32_t* out_ss_term_base, uint8_t* out_ss_term_scalars32, uint32_t* out_ss_offsets);
 
+/* ---- GenerateWhiskShuffleProof (whisk_interface.py:111-140) from tracker BYTES, for n_provers shuffles of one ell in step: pre-shuffle
+ * trackers, permutations, k and the draws in; post-shuffle tracker bytes and M || proof out.  The limits are cg1_shuffle_prove_device's.
+ * cg1_whisk_shuffle_front (csrc/capi_whisk_shuffle.h, csrc/kernels_whisk_shuffle.h) is everything in front of CurdleProofsProof.new, on
+ * the context's stream with one wait at its end:
+ *   k_table_msm + k_fixed_finish   M = MSM(vec_G | vec_H, perm | vec_m_blinders) of every prover as one launch over the CRS table
+ *   k_batch_decompress_row         the n_provers 2 ell encodings -> affine96 (its leniency: the infinity flag wins over the other bits)
+ *   k_subgroup_row, k_whisk_status the G1 certificate of every decoded point, folded with the decoder's status into one word per call
+ *   k_whisk_permute_mul            one wave per output: T_i = k R_perm[i], U_i = k S_perm[i], affine96 and the 48-byte encoding
+ *   per prover p, host buffers:
+ *     g_index (ell), h_index (4)   table indices of crs.vec_G and crs.vec_H
+ *     trackers96          ell records r_G48 | k_r_G48 (cg1_opening_prove's layout): R_i = r_G of tracker i, S_i = its k_r_G
+ *     perm                ell entries < ell (not required to be a bijection); k32; vec_m_blinders32 (4)
+ *     out_rs_affine96, out_tu_affine96   vec_R | vec_S and vec_T | vec_U, 2 ell affine96 records each, as cg1_shuffle_prove_device takes them
+ *     out_post96          ell records T_i48 | U_i48: the post-shuffle trackers;  out_m48: M
+ *   Refusals: a status for the whole call, the text (cg1_ctx_error) starting with the entry's name and, for a point, naming the prover, the
+ *   tracker index and the half (r_G / k_r_G); a refused call leaves every output untouched.  CG1_ERR_ARG: a null pointer, a table of
+ *   another device, ell + 4 not a power of two in 8 .. CG1_SAME_MSM_MAX_N, n_provers beyond cg1_shuffle_prove_device's limits, an index
+ *   outside the table, a perm entry >= ell.  CG1_ERR_ENCODING: k or a blinder >= r, an encoding without the compression flag or with
+ *   x >= p.  CG1_ERR_NOT_ON_CURVE.  CG1_ERR_NOT_IN_SUBGROUP: a tracker point outside G1 -- the reference would go on with it
+ *   (util.py:35-36 decodes unchecked); here k folds into the same-scalar block's scalars, which is exact only in G1.
+ * cg1_whisk_shuffle_prove_device   the front, then cg1_shuffle_prove_device on its vec_R | vec_S, vec_T | vec_U and M with bases_certified
+ *   = 1, in one native call; the remaining arguments are cg1_shuffle_prove_device's.  out_proofs: cg1_whisk_shuffle_proof_bytes(ell) = 48 +
+ *   cg1_shuffle_prover_proof_bytes(ell) bytes per prover, M || proof: the wire form cg1_shuffle_proof_bytes(crs) counts.  A refusal of
+ *   either half leaves out_post96 and out_proofs untouched; the chain's texts come back under this entry's name.
+ * cg1_whisk_shuffle_front_emulate   host only, test support: the front for ONE prover over the host's G1 code, with the same refusals
+ *   and texts (out_err256: nullable, 256 bytes).  gh_affine96 (nullable): the n = ell + 4 records vec_G | vec_H, for out_m48;
+ *   out_m_scalars32: the n scalars of M's row, perm | vec_m_blinders. */
+size_t cg1_whisk_shuffle_proof_bytes(size_t ell);                   /* 0 when cg1_shuffle_prover_proof_bytes(ell) is */
+int cg1_whisk_shuffle_front(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint8_t* trackers96,
+                            const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96,
+                            uint8_t* out_post96, uint8_t* out_m48);
+int cg1_whisk_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
+                                   const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* trackers96, const uint32_t* perm,
+                                   const uint8_t* k32, const uint8_t* vec_m_blinders32, const uint8_t* vec_a_blinders32, const uint8_t* vec_c_blinders32,
+                                   const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* blinders32, const uint8_t* vec_r32, uint8_t* out_post96,
+                                   uint8_t* out_proofs);
+int cg1_whisk_shuffle_front_emulate(size_t ell, const uint8_t* trackers96, const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32,
+                                    const uint8_t* gh_affine96 /* nullable */, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96, uint8_t* out_post96,
+                                    uint8_t* out_m_scalars32, uint8_t* out_m48 /* with gh_affine96 */, char* out_err256 /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif
