@@ -254,6 +254,10 @@ cg1_opening_exact_status = _proto("cg1_opening_exact_status", c_int, c_void_p, c
 cg1_opening_prove = _proto("cg1_opening_prove", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 cg1_opening_prove_device = _proto("cg1_opening_prove_device", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 cg1_generator_mul_device = _proto("cg1_generator_mul_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p)
+# the tracker scan (csrc/kernels_tracker_scan.h): device path, host twin, the timed phases of the last device call
+cg1_tracker_match_device = _proto("cg1_tracker_match_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p)
+cg1_tracker_match = _proto("cg1_tracker_match", c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p)
+cg1_tracker_match_last_ms = _proto("cg1_tracker_match_last_ms", c_int, c_void_p, c_void_p)
 # resident tables of fixed bases (csrc/kernels_fixed.h)
 cg1_fixed_create = _proto("cg1_fixed_create", c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_int))
 cg1_fixed_destroy = _proto("cg1_fixed_destroy", None, c_void_p)
@@ -351,6 +355,7 @@ EXPORTED_SYMBOLS = [
     "cg1_same_scalar_proof_bytes", "cg1_same_scalar_prove_device", "cg1_same_scalar_emulate",
     "cg1_shuffle_prover_proof_bytes", "cg1_shuffle_prove_device", "cg1_shuffle_begin_emulate",
     "cg1_whisk_shuffle_proof_bytes", "cg1_whisk_shuffle_front", "cg1_whisk_shuffle_prove_device", "cg1_whisk_shuffle_front_emulate",
+    "cg1_tracker_match_device", "cg1_tracker_match", "cg1_tracker_match_last_ms",
 ]
 
 

@@ -184,6 +184,7 @@ void cg1_ctx_destroy(cg1_ctx* ctx) {
   if (ctx->d_merlin_rows) (void)hipFree(ctx->d_merlin_rows);
   if (ctx->d_opening) (void)hipFree(ctx->d_opening);
   if (ctx->d_prover) (void)hipFree(ctx->d_prover);
+  if (ctx->d_tscan_tab) (void)hipFree(ctx->d_tscan_tab);
   if (ctx->d_gen_tab) (void)hipFree(ctx->d_gen_tab);
   if (ctx->d_small_partial) (void)hipFree(ctx->d_small_partial);
   if (ctx->d_small_ctr) (void)hipFree(ctx->d_small_ctr);
@@ -331,6 +332,8 @@ int cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value) {
   if (!strcmp(name, "fe_timed")) { ctx->fe_timed = value != 0; return CG1_OK; }
   if (!strcmp(name, "fe_rows")) { ctx->fe_rows = value != 0; return CG1_OK; }
   if (!strcmp(name, "fe_prio")) { if (value < 0 || value > 3) return CG1_ERR_ARG; ctx->fe_prio = value; return CG1_OK; }
+  if (!strcmp(name, "tracker_scan_ladder_max_ks")) { if (value < 0 || value > 1024) return CG1_ERR_ARG; ctx->tscan_ladder_max_ks = value; return CG1_OK; }
+  if (!strcmp(name, "tracker_scan_timing")) { ctx->tscan_timing = value != 0; return CG1_OK; }
   if (!strcmp(name, "decompress_waves")) { if (value != 2 && value != 3) return CG1_ERR_ARG; ctx->decompress_waves = value; return CG1_OK; }
   if (!strcmp(name, "merlin_rows")) { ctx->merlin_rows = value != 0; return CG1_OK; }
   if (!strcmp(name, "merlin_lanes")) { if (value < 1 || value > 64) return CG1_ERR_ARG; ctx->merlin_lanes = value; return CG1_OK; }

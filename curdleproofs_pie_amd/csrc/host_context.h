@@ -119,6 +119,9 @@ struct Ctx {
   int fe_prio = 0;                      // "fe_prio": wave priority of k_shuffle_front_end (s_setprio 0 .. 3)
   int decompress_waves = 3;             // "decompress_waves": waves per SIMD k_batch_decompress<false> is compiled for (2: table in registers, 3: half of it in scratch)
   void* d_opening = nullptr; size_t cap_opening = 0;              // cg1_opening_prepare_device's scratch (940 B per proof)
+  void* d_tscan_tab = nullptr; size_t cap_tscan_tab = 0;          // cg1_tracker_match_device's tile of light-table records (public points only)
+  int tscan_ladder_max_ks = CG1_TRACKER_MATCH_LADDER_MAX_KS;      // "tracker_scan_ladder_max_ks": up to this many secrets a scan runs one ladder per pair (0: always the tables)
+  int tscan_timing = 0; float tscan_ms[2] = {0.f, 0.f};           // "tracker_scan_timing": wait between the phases of a scan and keep build / match wall ms
   void* d_prover = nullptr; size_t cap_prover = 0;                // cg1_opening_prove_device's scratch (1 252 B per proof)
   PreparedPoint* d_gen_tab = nullptr;   // k_generator_mul's table of G (GEN_ENTRIES records), built at the first use (cg1_generator_mul_device)
   int fixed_slice = 0;                  // "fixed_slice": terms per workgroup of k_table_msm (1 .. 128; 0 = by the size of the call).  A/B switch

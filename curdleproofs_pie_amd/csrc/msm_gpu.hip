@@ -67,6 +67,7 @@ int pick_window(size_t n);
 #include "kernels_fixed.h"
 #include "light_digits.h"
 #include "kernels_light.h"
+#include "kernels_tracker_scan.h"
 }  // namespace cg1
 #include "kernels_rows.h"
 #include "kernels_merlin.h"
@@ -99,3 +100,4 @@ int pick_window(size_t n);
 #include "capi_same_scalar.h"      // the same-scalar block proved on the device: cg1_same_scalar_prove_device
 #include "capi_shuffle.h"          // a whole shuffle proof proved on the device: cg1_shuffle_prove_device
 #include "capi_whisk_shuffle.h"    // GenerateWhiskShuffleProof from tracker bytes: cg1_whisk_shuffle_front, cg1_whisk_shuffle_prove_device
+#include "capi_tracker_scan.h"    // which trackers a set of secrets opens: cg1_tracker_match_device and its host twin cg1_tracker_match

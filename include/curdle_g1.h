@@ -939,6 +939,36 @@ int cg1_whisk_shuffle_front_emulate(size_t ell, const uint8_t* trackers96, const
                                     const uint8_t* gh_affine96 /* nullable */, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96, uint8_t* out_post96,
                                     uint8_t* out_m_scalars32, uint8_t* out_m48 /* with gh_affine96 */, char* out_err256 /* nullable */);
 
+/* The tracker scan: which trackers does a set of Whisk secrets open?  For n_trackers trackers (r_G48 | k_r_G48, cg1_opening_prove's layout)
+ * and n_ks secrets (scalar32), bit (i, j) = [ k_j * point_projective_from_bytes(r_G_i) == point_projective_from_bytes(k_r_G_i) ]
+ * (util.py:35-36: unchecked decoding, a point outside G1 is legal and multiplied exactly; the relation opening.py proves).
+ *   out_bitmap           n_trackers x ceil(n_ks / 64) 64-bit words, word (i, j / 64), bit j % 64; padding bits are zero
+ *   out_tracker_status   per tracker: 0, or CG1_SHUFFLE_BAD_POINT when r_G or k_r_G does not decode (its row is zero)
+ *   out_k_status         per secret: 0, or CG1_SHUFFLE_BAD_SCALAR when k >= r (its column is zero); k = 0 is a legal scalar
+ *   tile_bases           trackers whose light tables (csrc/kernels_light.h: 128 KiB each) are resident at a time on the device; 0 = the
+ *                        default CG1_TRACKER_MATCH_DEFAULT_TILE (128 MiB of records).  The host twin ignores the value but refuses the same ones.
+ * Host buffers in and out; the device call runs on the context's stream and waits once.  Refusals come before anything is written:
+ * CG1_ERR_ARG for a null buffer, n_trackers > CG1_TRACKER_MATCH_MAX_TRACKERS, n_ks > CG1_TRACKER_MATCH_MAX_KS, a bitmap above
+ * CG1_TRACKER_MATCH_MAX_BITMAP_BYTES or tile_bases > CG1_TRACKER_MATCH_MAX_TILE (larger jobs: call in chunks of trackers and secrets, as
+ * the Python face does).  No error text ever holds a secret, and the device copy of the secrets is zeroed and freed before the call returns.
+ * cg1_tracker_match is the host twin on the worker pool (decode, multiply, compare): the same bits and statuses, what a machine without
+ * a GPU and small calls take.  cg1_tracker_match_last_ms: with the context parameter "tracker_scan_timing" = 1 the device call waits
+ * between its phases and keeps the wall milliseconds of the table builds (ms[0]) and the match kernels (ms[1]) of the last call.
+ * Up to CG1_TRACKER_MATCH_LADDER_MAX_KS secrets (context parameter "tracker_scan_ladder_max_ks", 0 .. 1024; 0 = never) the device call
+ * builds no table: it runs one double-and-add ladder per pair (k_batch_mul) and compares the affine results on the device -- the same
+ * bits and statuses, cheaper below the measured crossover; ms[0] is then 0. */
+#define CG1_TRACKER_MATCH_MAX_TRACKERS     65536
+#define CG1_TRACKER_MATCH_MAX_KS           1048576
+#define CG1_TRACKER_MATCH_MAX_BITMAP_BYTES (1ull << 30)
+#define CG1_TRACKER_MATCH_MAX_TILE         4096
+#define CG1_TRACKER_MATCH_DEFAULT_TILE     1024
+#define CG1_TRACKER_MATCH_LADDER_MAX_KS    32   /* up to this many secrets the device call runs one ladder per pair instead of the tables */
+int cg1_tracker_match_device(cg1_ctx* ctx, const uint8_t* trackers96 /* r_G | k_r_G */, size_t n_trackers, const uint8_t* ks32, size_t n_ks,
+                             size_t tile_bases, uint64_t* out_bitmap, int32_t* out_tracker_status, int32_t* out_k_status);
+int cg1_tracker_match(const uint8_t* trackers96 /* r_G | k_r_G */, size_t n_trackers, const uint8_t* ks32, size_t n_ks, size_t tile_bases,
+                      uint64_t* out_bitmap, int32_t* out_tracker_status, int32_t* out_k_status);
+int cg1_tracker_match_last_ms(const cg1_ctx* ctx, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif
