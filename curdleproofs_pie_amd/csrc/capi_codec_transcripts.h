@@ -125,12 +125,7 @@ int cg1_merlin_batch_device(cg1_ctx* ctx, const uint8_t* init_state208, const cg
       const unsigned nb = (unsigned)((n + lanes_used - 1) / lanes_used);
       const size_t need = build_block_program(cops, labels, init_state208, nullptr, true, desc, nn) ? (size_t)nb * lanes_used * nn * cg1merlin::ROW_WORDS * 4 : 0;
       if (need && need <= ((size_t)8 << 30)) {
-        if (need > ctx->merlin_rows_cap) {
-          if (ctx->d_merlin_rows) (void)hipFree(ctx->d_merlin_rows);
-          ctx->d_merlin_rows = nullptr; ctx->merlin_rows_cap = 0;
-          HIPCHK(hipMalloc(&ctx->d_merlin_rows, need));
-          ctx->merlin_rows_cap = need;
-        }
+        if (const int rc = cg1::grow_bufs(ctx, ctx->merlin_rows_cap, need, need, {cg1::dev_buf(ctx->d_merlin_rows, need)})) return rc;
         DevBuf ddesc, dpass;
         HIPCHK(ddesc.alloc(desc.size() * sizeof(cg1merlin::RowDesc)));
         HIPCHK(dpass.alloc(4 * (size_t)nb));
@@ -218,12 +213,7 @@ int cg1_opening_prepare_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96
   HIPCHK(hipSetDevice(ctx->device));
   // scratch: trackers 96 | k_commitments 48 | proofs 128 | weights 64 | wire 240 | rows 288 | challenges 32 | g scalars 32 | status 4 | point status 5 (+3)
   const size_t per = 96 + 48 + 128 + 64 + 240 + cg1open::ROW_BYTES + 32 + 32 + 4 + 8, need = per * n;
-  if (need > ctx->cap_opening) {
-    if (ctx->d_opening) (void)hipFree(ctx->d_opening);
-    ctx->d_opening = nullptr; ctx->cap_opening = 0;
-    HIPCHK(hipMalloc(&ctx->d_opening, need));
-    ctx->cap_opening = need;
-  }
+  if (const int rc = cg1::grow_bufs(ctx, ctx->cap_opening, need, need, {cg1::dev_buf(ctx->d_opening, need)})) return rc;
   uint8_t* base = (uint8_t*)ctx->d_opening;
   uint8_t *d_trk = base, *d_kc = d_trk + 96 * n, *d_pf = d_kc + 48 * n, *d_w = d_pf + 128 * n, *d_wire = d_w + 64 * n, *d_rows = d_wire + 240 * n,
           *d_ch = d_rows + (size_t)cg1open::ROW_BYTES * n, *d_gs = d_ch + 32 * n, *d_st = d_gs + 32 * n, *d_ps = d_st + 4 * n;
@@ -341,12 +331,7 @@ int cg1_opening_prove_device(cg1_ctx* ctx, size_t n, const uint8_t* trackers96, 
   // scratch: trackers 96 | k 32 | blinders 32 | wire 96 | affine 192 | gen scalars 64 | gen48 96 | B affine 96 | B48 48 | rows 288 |
   //          challenges 32 | status 4 | proofs 128 | k_G 48 | point status 2
   const size_t per = 96 + 32 + 32 + 96 + 192 + 64 + 96 + 96 + 48 + cg1open::ROW_BYTES + 32 + 4 + 128 + 48 + 2, need = per * n;
-  if (need > ctx->cap_prover) {
-    if (ctx->d_prover) (void)hipFree(ctx->d_prover);
-    ctx->d_prover = nullptr; ctx->cap_prover = 0;
-    HIPCHK(hipMalloc(&ctx->d_prover, need));
-    ctx->cap_prover = need;
-  }
+  if (const int rc = cg1::grow_bufs(ctx, ctx->cap_prover, need, need, {cg1::dev_buf(ctx->d_prover, need)})) return rc;
   uint8_t* base = (uint8_t*)ctx->d_prover;
   uint8_t *d_trk = base, *d_k = d_trk + 96 * n, *d_bl = d_k + 32 * n, *d_wire = d_bl + 32 * n, *d_aff = d_wire + 96 * n, *d_gsc = d_aff + 192 * n,
           *d_gen48 = d_gsc + 64 * n, *d_b96 = d_gen48 + 96 * n, *d_b48 = d_b96 + 96 * n, *d_rows = d_b48 + 48 * n, *d_ch = d_rows + (size_t)cg1open::ROW_BYTES * n,

@@ -181,19 +181,16 @@ void cg1_ctx_destroy(cg1_ctx* ctx) {
   if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
   if (ctx->ev_acc) (void)hipEventDestroy(ctx->ev_acc);
   cg1::free_bufs(ctx);
-  if (ctx->d_merlin_rows) (void)hipFree(ctx->d_merlin_rows);
-  if (ctx->d_opening) (void)hipFree(ctx->d_opening);
-  if (ctx->d_prover) (void)hipFree(ctx->d_prover);
-  if (ctx->d_tscan_tab) (void)hipFree(ctx->d_tscan_tab);
-  if (ctx->d_gen_tab) (void)hipFree(ctx->d_gen_tab);
-  if (ctx->d_small_partial) (void)hipFree(ctx->d_small_partial);
-  if (ctx->d_small_ctr) (void)hipFree(ctx->d_small_ctr);
-  if (ctx->d_small_pts) (void)hipFree(ctx->d_small_pts);
-  if (ctx->d_small_flags) (void)hipFree(ctx->d_small_flags);
-  if (ctx->h_small_out) (void)hipHostFree(ctx->h_small_out);
-  if (ctx->d_stage_pts) (void)hipFree(ctx->d_stage_pts);
-  if (ctx->d_stage_sc) (void)hipFree(ctx->d_stage_sc);
-  if (ctx->h_flag) (void)hipHostFree(ctx->h_flag);
+  cg1::release_bufs(ctx->merlin_rows_cap, {cg1::dev_buf(ctx->d_merlin_rows)});
+  cg1::release_bufs(ctx->cap_opening, {cg1::dev_buf(ctx->d_opening)});
+  cg1::release_bufs(ctx->cap_prover, {cg1::dev_buf(ctx->d_prover)});
+  cg1::release_bufs(ctx->cap_tscan_tab, {cg1::dev_buf(ctx->d_tscan_tab)});
+  cg1::release_bufs(ctx->cap_small_partial, {cg1::dev_buf(ctx->d_small_partial)});
+  cg1::release_bufs(ctx->cap_small_pts, {cg1::dev_buf(ctx->d_small_pts), cg1::dev_buf(ctx->d_small_flags)});
+  cg1::release_bufs(ctx->cap_stage_pts, {cg1::dev_buf(ctx->d_stage_pts)});
+  cg1::release_bufs(ctx->cap_stage_sc, {cg1::dev_buf(ctx->d_stage_sc)});
+  cg1::release_bufs({cg1::dev_buf(ctx->d_gen_tab), cg1::dev_buf(ctx->d_small_ctr), cg1::host_buf(ctx->h_small_out, 0, 0u, &ctx->h_small_out_dev),
+                     cg1::host_buf(ctx->h_flag, 0, 0u, &ctx->h_flag_dev)});      // allocated once, at fixed sizes
   for (int i = 0; i <= CG1_NPHASE; ++i) (void)hipEventDestroy(ctx->ev[i]);
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->copy_ev) (void)hipEventDestroy(ctx->copy_ev);
@@ -288,6 +285,7 @@ int cg1_ctx_device(const cg1_ctx* ctx) { return ctx ? ctx->device : -1; }
 void* cg1_ctx_stream(cg1_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value) {
   if (!ctx || !name) return CG1_ERR_ARG;
+  if (!strcmp(name, "alloc_fail_at")) { if (value < 0) return CG1_ERR_ARG; ctx->alloc_fail_at = value; return CG1_OK; }
   if (!strcmp(name, "chunk_rule")) { ctx->chunk_rule = value != 0; return CG1_OK; }
   if (!strcmp(name, "chunk_len")) { if (value < 1 || value > 65536) return CG1_ERR_ARG; ctx->L0 = (uint32_t)value; cg1::free_bufs(ctx); return CG1_OK; }
   if (!strcmp(name, "stage_sort")) { ctx->stage_sort = value ? 1 : 0; return CG1_OK; }
@@ -398,33 +396,15 @@ int cg1_msm_multi_device(cg1_ctx* const* ctxs, size_t n_ctx, const void* const* 
 
 // device staging for the host-pointer entry points (grown geometrically, kept by the context)
 static int ensure_stage(cg1_ctx* ctx, size_t pts_bytes, size_t sc_bytes) {
-  if (pts_bytes > ctx->cap_stage_pts) {
-    if (ctx->d_stage_pts) (void)hipFree(ctx->d_stage_pts);
-    ctx->d_stage_pts = nullptr; ctx->cap_stage_pts = 0;
-    const size_t want = pts_bytes + pts_bytes / 4 + 256;
-    HIPCHK(hipMalloc(&ctx->d_stage_pts, want));
-    ctx->cap_stage_pts = want;
-  }
-  if (sc_bytes > ctx->cap_stage_sc) {
-    if (ctx->d_stage_sc) (void)hipFree(ctx->d_stage_sc);
-    ctx->d_stage_sc = nullptr; ctx->cap_stage_sc = 0;
-    const size_t want = sc_bytes + sc_bytes / 4 + 256;
-    HIPCHK(hipMalloc(&ctx->d_stage_sc, want));
-    ctx->cap_stage_sc = want;
-  }
-  return CG1_OK;
+  const size_t want_pts = pts_bytes + pts_bytes / 4 + 256, want_sc = sc_bytes + sc_bytes / 4 + 256;
+  if (const int rc = cg1::grow_bufs(ctx, ctx->cap_stage_pts, pts_bytes, want_pts, {cg1::dev_buf(ctx->d_stage_pts, want_pts)})) return rc;
+  return cg1::grow_bufs(ctx, ctx->cap_stage_sc, sc_bytes, want_sc, {cg1::dev_buf(ctx->d_stage_sc, want_sc)});
 }
 
 // the context's mapped page-locked scratch (cg1_lincomb_batch's gather buffer, cg1_msm's small inputs): at least `bytes`
 static int ensure_lin(cg1_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->cap_h_lin) return CG1_OK;
-  if (ctx->h_lin) (void)hipHostFree(ctx->h_lin);
-  ctx->h_lin = nullptr; ctx->h_lin_dev = nullptr; ctx->cap_h_lin = 0;
   const size_t want = bytes + bytes / 4 + 4096;
-  HIPCHK(hipHostMalloc((void**)&ctx->h_lin, want, hipHostMallocMapped));
-  HIPCHK(hipHostGetDevicePointer((void**)&ctx->h_lin_dev, ctx->h_lin, 0));
-  ctx->cap_h_lin = want;
-  return CG1_OK;
+  return cg1::grow_bufs(ctx, ctx->cap_h_lin, bytes, want, {cg1::host_buf(ctx->h_lin, want, hipHostMallocMapped, &ctx->h_lin_dev)});
 }
 
 int cg1_msm(cg1_ctx* ctx, const uint8_t* points, const uint8_t* scalars, size_t n, uint8_t* out) {

@@ -26,13 +26,9 @@ struct cg1_table {
     return CG1_OK;
   }
   void release() {
-    if (d_ctr) (void)hipFree(d_ctr);
-    if (d_status) (void)hipFree(d_status);
-    if (d_partial) (void)hipFree(d_partial);
-    if (d_sum) (void)hipFree(d_sum);
-    if (d_in) (void)hipFree(d_in);
-    if (h_out) (void)hipHostFree(h_out);
-    if (h_in) (void)hipHostFree(h_in);
+    cg1::release_bufs({cg1::dev_buf(d_ctr), cg1::dev_buf(d_status), cg1::dev_buf(d_sum), cg1::host_buf(h_out, 0, 0u, &h_out_dev)});
+    cg1::release_bufs(cap_partial, {cg1::dev_buf(d_partial)});
+    cg1::release_bufs(cap_in, {cg1::host_buf(h_in, 0, 0u, &h_in_dev), cg1::dev_buf(d_in)});
   }
 };
 
@@ -220,10 +216,9 @@ cg1_fixed* cg1_fixed_create(cg1_ctx* ctx, const uint8_t* bases_affine96, size_t 
 void cg1_fixed_destroy(cg1_fixed* t) {
   if (!t) return;
   (void)hipSetDevice(t->device);
-  if (t->d_tab) (void)hipFree(t->d_tab);
+  cg1::release_bufs({cg1::dev_buf(t->d_tab)});
   t->release();
-  if (t->d_chain) (void)hipFree(t->d_chain);
-  if (t->h_chain) (void)hipHostFree(t->h_chain);
+  cg1::release_bufs(t->cap_chain, {cg1::host_buf(t->h_chain), cg1::dev_buf(t->d_chain)});
   if (t->smsm_light) cg1_light_destroy(t->smsm_light);
   delete t;
 }

@@ -231,8 +231,11 @@ extern "C" {
 void cg1_shuffle_fe_destroy(cg1_shuffle_fe* fe) {
   if (!fe) return;
   (void)hipSetDevice(fe->device);
-  for (void* p : {fe->d_init, fe->d_ops, fe->d_labels, fe->d_consts, fe->d_tabG, fe->d_tabH, fe->d_four, fe->d_scratch, fe->d_desc, fe->d_rows, fe->d_passes})
-    if (p) (void)hipFree(p);
+  cg1::release_bufs({cg1::dev_buf(fe->d_init), cg1::dev_buf(fe->d_ops), cg1::dev_buf(fe->d_labels), cg1::dev_buf(fe->d_consts), cg1::dev_buf(fe->d_tabG),
+                     cg1::dev_buf(fe->d_tabH), cg1::dev_buf(fe->d_desc)});      // the program and its tables, allocated once
+  cg1::release_bufs(fe->cap_n, {cg1::dev_buf(fe->d_four), cg1::dev_buf(fe->d_scratch)});
+  cg1::release_bufs(fe->cap_rows, {cg1::dev_buf(fe->d_rows)});
+  cg1::release_bufs(fe->cap_blocks, {cg1::dev_buf(fe->d_passes)});
   delete fe;
 }
 
@@ -484,14 +487,7 @@ int cg1_shuffle_fe_enqueue(cg1_shuffle_fe* fe, cg1_ctx* ctx, size_t n, const voi
   if (!d_wire48 || !d_pts_affine96 || !d_aux || !d_rowin || !d_status || n >= (1u << 24) || ctx->device != fe->device) return CG1_ERR_ARG;
   if (lanes_per_wave < 1 || lanes_per_wave > cg1merlin::LANES) lanes_per_wave = cg1merlin::LANES;
   HIPCHK(hipSetDevice(ctx->device));
-  if (n > fe->cap_n) {
-    if (fe->d_four) (void)hipFree(fe->d_four);
-    if (fe->d_scratch) (void)hipFree(fe->d_scratch);
-    fe->d_four = fe->d_scratch = nullptr; fe->cap_n = 0;
-    HIPCHK(hipMalloc(&fe->d_four, n * 4 * sizeof(cg1::PreparedPoint)));
-    HIPCHK(hipMalloc(&fe->d_scratch, n * (size_t)fe->pr.out_stride));
-    fe->cap_n = n;
-  }
+  if (const int rc = cg1::grow_bufs(ctx, fe->cap_n, n, n, {cg1::dev_buf(fe->d_four, n * 4 * sizeof(cg1::PreparedPoint)), cg1::dev_buf(fe->d_scratch, n * (size_t)fe->pr.out_stride)})) return rc;
   hipLaunchKernelGGL(cg1fe::k_fe_gather4, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_pts_affine96, fe->pr, (uint32_t)n,
                      (cg1::PreparedPoint*)fe->d_four);
   const unsigned nblk = (unsigned)((n + lanes_per_wave - 1) / lanes_per_wave);
@@ -499,14 +495,8 @@ int cg1_shuffle_fe_enqueue(cg1_shuffle_fe* fe, cg1_ctx* ctx, size_t n, const voi
   if (fe->n_nodes && ctx->fe_rows) {
     const size_t row_words = (size_t)fe->n_nodes * cg1fe::ROW_WORDS;
     const size_t need = (size_t)nblk * lanes_per_wave * row_words;          // rows are laid out per wave: the last wave's unused lanes count
-    if (need > fe->cap_rows || nblk > fe->cap_blocks) {
-      if (fe->d_rows) (void)hipFree(fe->d_rows);
-      if (fe->d_passes) (void)hipFree(fe->d_passes);
-      fe->d_rows = fe->d_passes = nullptr; fe->cap_rows = 0; fe->cap_blocks = 0; fe->last_blocks = 0;
-      HIPCHK(hipMalloc(&fe->d_rows, need * 4));
-      HIPCHK(hipMalloc(&fe->d_passes, (size_t)nblk * 32));
-      fe->cap_rows = need; fe->cap_blocks = nblk;
-    }
+    if (const int rc = cg1::grow_bufs(ctx, fe->cap_rows, need, need, {cg1::dev_buf(fe->d_rows, need * 4)})) return rc;
+    if (const int rc = cg1::grow_bufs(ctx, fe->cap_blocks, nblk, nblk, {cg1::dev_buf(fe->d_passes, (size_t)nblk * 32)})) return rc;
     fe->last_blocks = nblk;
     hipLaunchKernelGGL(cg1merlin::k_fill_rows, dim3((unsigned)((row_words + 255) / 256), (unsigned)std::min<size_t>(n, 65535)), dim3(256), 0, ctx->stream, (const cg1fe::RowDesc*)fe->d_desc, fe->n_nodes,
                        (const uint8_t*)d_wire48, (size_t)fe->pr.L * 48, 1u, (uint32_t)n, (uint32_t)lanes_per_wave, (uint32_t*)fe->d_rows);

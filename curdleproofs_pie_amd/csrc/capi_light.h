@@ -82,7 +82,7 @@ cg1_light* cg1_light_create(cg1_ctx* ctx, const uint8_t* bases_affine96, size_t 
 void cg1_light_destroy(cg1_light* t) {
   if (!t) return;
   (void)hipSetDevice(t->device);
-  if (t->d_tab) (void)hipFree(t->d_tab);
+  cg1::release_bufs({cg1::dev_buf(t->d_tab)});
   t->release();
   delete t;
 }

@@ -45,12 +45,7 @@ int cg1_tracker_match_device(cg1_ctx* ctx, const uint8_t* trackers96, size_t n_t
   // a handful of secrets: one ladder per pair instead of a table per tracker (kernels_tracker_scan.h; "tracker_scan_ladder_max_ks")
   const bool ladder = V && V <= (size_t)ctx->tscan_ladder_max_ks && T * V <= ((size_t)1 << 24);
   const size_t tab_bytes = std::min(tile, T) * (size_t)cg1::LT_ENTRIES * sizeof(cg1::PointSum);
-  if (V && !ladder && tab_bytes > ctx->cap_tscan_tab) {
-    if (ctx->d_tscan_tab) (void)hipFree(ctx->d_tscan_tab);
-    ctx->d_tscan_tab = nullptr; ctx->cap_tscan_tab = 0;
-    HIPCHK(hipMalloc(&ctx->d_tscan_tab, tab_bytes));
-    ctx->cap_tscan_tab = tab_bytes;
-  }
+  if (V && !ladder) { const int rc = cg1::grow_bufs(ctx, ctx->cap_tscan_tab, tab_bytes, tab_bytes, {cg1::dev_buf(ctx->d_tscan_tab, tab_bytes)}); if (rc) return rc; }
   // scratch: trackers 96 | wire 96 | affine 192 | point status 2 (padded) | bitmap 8 words, per tracker; the ladder route: V products 96
   const size_t o_wire = 96 * T, o_aff = o_wire + 96 * T, o_ps = o_aff + 192 * T, o_bm = (o_ps + 2 * T + 15) & ~(size_t)15,
                o_prod = (o_bm + 8 * words * T + 15) & ~(size_t)15, bytes = o_prod + (ladder ? 96 * T * V : 0);

@@ -30,8 +30,7 @@ cg1_vec* cg1_vec_create(cg1_ctx* ctx, const uint8_t* blobs144, size_t n, int all
 void cg1_vec_destroy(cg1_vec* v) {
   if (!v) return;
   (void)hipSetDevice(v->device);
-  if (v->d_pts) (void)hipFree(v->d_pts);
-  if (v->d_flags) (void)hipFree(v->d_flags);
+  cg1::release_bufs({cg1::dev_buf(v->d_pts), cg1::dev_buf(v->d_flags)});
   delete v;
 }
 size_t cg1_vec_len(const cg1_vec* v) { return v ? v->n : 0; }

@@ -68,30 +68,6 @@ static int wait_export_flag(Ctx* ctx, uint32_t seq) {
   return CG1_OK;
 }
 
-// Regrow a buffer a handle keeps between calls, only when it is too small for `need`: freed, then `grown` (>= need: the site's growth
-// policy) allocated; a failure leaves it empty.  A device buffer of T ...
-template <class T>
-static int grow_device(Ctx* ctx, T*& d, size_t& cap, size_t need, size_t grown) {
-  if (need <= cap) return CG1_OK;
-  if (d) (void)hipFree(d);
-  d = nullptr; cap = 0;
-  HIPCHK(hipMalloc((void**)&d, grown * sizeof(T)));
-  cap = grown;
-  return CG1_OK;
-}
-// ... and a page-locked block with its device twin.  flags: hipHostMalloc's; h_dev (nullable): where a mapped block's device address goes
-static int grow_pinned_pair(Ctx* ctx, uint8_t*& h, uint8_t** h_dev, uint8_t*& d, size_t& cap, size_t need, size_t grown, unsigned flags) {
-  if (need <= cap) return CG1_OK;
-  if (h) (void)hipHostFree(h);
-  if (d) (void)hipFree(d);
-  h = nullptr; d = nullptr; cap = 0;
-  HIPCHK(hipHostMalloc((void**)&h, grown, flags));
-  if (h_dev) HIPCHK(hipHostGetDevicePointer((void**)h_dev, h, 0));
-  HIPCHK(hipMalloc((void**)&d, grown));
-  cap = grown;
-  return CG1_OK;
-}
-
 // Where an MSM's points come from (all device memory):
 //   AFFINE96  n x 96 B standard-form affine records (the C ABI's "affine96")                      -> k_prepare_points
 //   BLOBS     n x 144 B host point blobs as G1Point objects hold them (Jacobian, radix 2^384)     -> k_prepare_blobs
@@ -516,12 +492,7 @@ static int msm_enqueue_small(Ctx* ctx, const PtSrc& src, const void* d_scalars32
     HIPCHK(hipMemsetAsync(ctx->d_small_ctr, 0, (SM_MAX_MSMS * 64 + 8) * 4, ctx->stream));
   }
   const size_t need_partial = (size_t)M * nwin * S * nitems;
-  if (S > 1 && need_partial > ctx->cap_small_partial) {
-    if (ctx->d_small_partial) (void)hipFree(ctx->d_small_partial);
-    ctx->d_small_partial = nullptr; ctx->cap_small_partial = 0;
-    HIPCHK(hipMalloc(&ctx->d_small_partial, need_partial * sizeof(PointSum)));
-    ctx->cap_small_partial = need_partial;
-  }
+  if (S > 1) { const int rc = grow_device(ctx, ctx->d_small_partial, ctx->cap_small_partial, need_partial, need_partial); if (rc) return rc; }
   hipStream_t st = ctx->stream;
   SmallArgs a;
   a.src = src.p; a.flags = src.flags; a.scalars = static_cast<const uint32_t*>(d_scalars32); a.offs = d_offs;
@@ -532,15 +503,8 @@ static int msm_enqueue_small(Ctx* ctx, const PtSrc& src, const void* d_scalars32
   a.glv = glv ? 1u : 0u;
   int kind = (int)src.kind;
   if (src.kind == PtSrc::BLOBS && !src.normalised) {           // invert first (one lane per point), then run on the prepared records
-    if (n > ctx->cap_small_pts) {
-      if (ctx->d_small_pts) (void)hipFree(ctx->d_small_pts);
-      if (ctx->d_small_flags) (void)hipFree(ctx->d_small_flags);
-      ctx->d_small_pts = nullptr; ctx->d_small_flags = nullptr; ctx->cap_small_pts = 0;
-      const size_t cap = n < SM_MAX_N ? SM_MAX_N : n;
-      HIPCHK(hipMalloc(&ctx->d_small_pts, cap * sizeof(PreparedPoint)));
-      HIPCHK(hipMalloc(&ctx->d_small_flags, cap + 16));
-      ctx->cap_small_pts = cap;
-    }
+    const size_t cap = n < SM_MAX_N ? SM_MAX_N : n;
+    { const int rc = grow_bufs(ctx, ctx->cap_small_pts, n, cap, {dev_buf(ctx->d_small_pts, cap * sizeof(PreparedPoint)), dev_buf(ctx->d_small_flags, cap + 16)}); if (rc) return rc; }
     launch_prepare(st, src, ctx->d_small_pts, ctx->d_small_flags, (uint32_t)n, nullptr);
     a.src = ctx->d_small_pts; a.flags = ctx->d_small_flags;
     kind = (int)PtSrc::PREPARED;
@@ -745,28 +709,16 @@ static int batched_chain_enqueue(Ctx* ctx, const void* d_points96, const void* d
   int rc = ensure(ctx, Nv, nb_total, nwin, 1, L0);
   if (rc) return rc;
   // batch-only buffers
-  if ((M + 1) > ctx->cap_boffs) {
-    if (ctx->d_boffs) (void)hipFree(ctx->d_boffs);
-    HIPCHK(hipMalloc(&ctx->d_boffs, (M + 1) * 4));
-    ctx->cap_boffs = M + 1;
-  }
-  if (G > ctx->cap_gsum) {
-    if (ctx->d_gsum) (void)hipFree(ctx->d_gsum);
-    HIPCHK(hipMalloc(&ctx->d_gsum, G * sizeof(PointSum)));
-    ctx->cap_gsum = G;
-  }
-  if (M > ctx->cap_bout) {
-    if (ctx->d_bout) (void)hipFree(ctx->d_bout);
-    if (ctx->h_bout) (void)hipHostFree(ctx->h_bout);
-    HIPCHK(hipMalloc(&ctx->d_bout, (M + 1) * sizeof(PointWords)));         // + one record: the input-validation flag word
-    HIPCHK(hipHostMalloc(&ctx->h_bout, (M + 1) * sizeof(PointWords)));
-    ctx->cap_bout = M;
-  }
-  if (Nv * nwin > ctx->cap_digits) {
-    if (ctx->d_digits) (void)hipFree(ctx->d_digits);
-    HIPCHK(hipMalloc(&ctx->d_digits, Nv * nwin * 2 + 16));
-    ctx->cap_digits = Nv * nwin;
-  }
+  if ((rc = grow_device(ctx, ctx->d_boffs, ctx->cap_boffs, M + 1, M + 1))) return rc;
+  if ((rc = grow_device(ctx, ctx->d_gsum, ctx->cap_gsum, G, G))) return rc;
+  if ((rc = grow_bufs(ctx, ctx->cap_bout, M, M, {dev_buf(ctx->d_bout, (M + 1) * sizeof(PointWords)),         // + one record: the input-validation flag word
+                                                 host_buf(ctx->h_bout, (M + 1) * sizeof(PointWords))}))) return rc;
+  if ((rc = grow_bufs(ctx, ctx->cap_digits, Nv * nwin, Nv * nwin, {dev_buf(ctx->d_digits, Nv * nwin * 2 + 16)}))) return rc;
+  // The Horner over an MSM's window sums is 255 DEPENDENT doublings: ~1.0 ms for a DPP quad, ~65 us for a host core.  A handful of
+  // MSMs (the prover's halving rounds: 4-6 per call) therefore finish on the host, on the context's four threads; hundreds of them
+  // (a batch of accumulator MSMs) keep the device's one-quad-per-MSM kernel, which does them all in the same millisecond.
+  const bool host_horner = M <= (size_t)ctx->batched_host_horner_max;
+  if (host_horner && (rc = grow_bufs(ctx, ctx->cap_gout, G, G, {dev_buf(ctx->d_gout, G * sizeof(PointWords)), host_buf(ctx->h_gout, G * sizeof(PointWords))}))) return rc;
   hipStream_t st = ctx->stream;
   const uint32_t N32 = (uint32_t)N_real, gn = (N32 + 255) / 256, Nv32 = (uint32_t)Nv, split = glv ? N32 : 0u;
   auto h0 = std::chrono::steady_clock::now();
@@ -801,19 +753,7 @@ static int batched_chain_enqueue(Ctx* ctx, const void* d_points96, const void* d
   hipLaunchKernelGGL(k_seg_reduce, dim3((nseg_total + 255) / 256), dim3(256), 0, st, ctx->d_choff, ctx->d_sums, ctx->d_combined, ctx->d_segrun, ctx->d_segtot, nseg_total, m);
   hipLaunchKernelGGL(k_group_reduce, dim3((uint32_t)((G + 255) / 256)), dim3(256), 0, st, ctx->d_segrun, ctx->d_segtot, ctx->d_gsum, (uint32_t)G, J, log2m);
   if (ctx->profile >= 2) HIPCHK(hipEventRecord(ctx->ev[6], st));
-  // The Horner over an MSM's window sums is 255 DEPENDENT doublings: ~1.0 ms for a DPP quad, ~65 us for a host core.  A handful of
-  // MSMs (the prover's halving rounds: 4-6 per call) therefore finish on the host, on the context's four threads; hundreds of them
-  // (a batch of accumulator MSMs) keep the device's one-quad-per-MSM kernel, which does them all in the same millisecond.
-  const bool host_horner = M <= (size_t)ctx->batched_host_horner_max;
   if (host_horner) {
-    if (G > ctx->cap_gout) {
-      if (ctx->d_gout) (void)hipFree(ctx->d_gout);
-      if (ctx->h_gout) (void)hipHostFree(ctx->h_gout);
-      ctx->d_gout = nullptr; ctx->h_gout = nullptr; ctx->cap_gout = 0;
-      HIPCHK(hipMalloc(&ctx->d_gout, G * sizeof(PointWords)));
-      HIPCHK(hipHostMalloc(&ctx->h_gout, G * sizeof(PointWords)));
-      ctx->cap_gout = G;
-    }
     hipLaunchKernelGGL(k_export_sums, dim3((uint32_t)((G + 63) / 64)), dim3(64), 0, st, ctx->d_gsum, ctx->d_gout, (uint32_t)G);
     HIPCHK(hipMemcpyAsync(ctx->h_gout, ctx->d_gout, G * sizeof(PointWords), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(ctx->h_bout + M, ctx->d_bout + M, sizeof(PointWords), hipMemcpyDeviceToHost, st));      // the status words
@@ -903,12 +843,7 @@ int msm_batched_device(Ctx* ctx, const void* d_points96, const void* d_scalars32
       HIPCHK(hipSetDevice(ctx->device));
       const uint32_t* d_offs = d_offsets_ready;
       if (!d_offs) {
-        if ((M + 1) > ctx->cap_boffs) {
-          if (ctx->d_boffs) (void)hipFree(ctx->d_boffs);
-          ctx->d_boffs = nullptr; ctx->cap_boffs = 0;
-          HIPCHK(hipMalloc(&ctx->d_boffs, (M + 1) * 4));
-          ctx->cap_boffs = M + 1;
-        }
+        { const int rc = grow_device(ctx, ctx->d_boffs, ctx->cap_boffs, M + 1, M + 1); if (rc) return rc; }
         HIPCHK(hipMemcpyAsync(ctx->d_boffs, h_offsets, (M + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
         d_offs = ctx->d_boffs;
       }

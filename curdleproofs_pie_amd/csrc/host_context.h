@@ -87,6 +87,7 @@ struct Ctx {
   hipEvent_t sync_ev = nullptr;         // blocking-sync event: waits sleep on an interrupt instead of spinning a core
   int blocking_sync = 0;
   char err[256] = {0};
+  int alloc_fail_at = 0;                // "alloc_fail_at": the k-th allocation grow_bufs attempts from now on fails as out of memory (a test's hook; 0 = off)
   // capacity
   size_t cap_n = 0, cap_nb = 0, cap_chunks = 0, cap_entries = 0, cap_out = 0;
   PreparedPoint* d_pts = nullptr;
@@ -221,132 +222,130 @@ struct Ctx {
   uint32_t seg_m = 4;
 };
 
+// ------------------------------------------------------------------ kept buffers: one way to grow them, one way to release them
+// A buffer a handle keeps between calls: where its pointer lives, the bytes a growth allocates, and for page-locked host memory the
+// hipHostMalloc flags and (mapped memory) where the device's address of it goes.
+struct KeptBuf {
+  void** p; size_t bytes; bool host; unsigned flags; void** dev;
+};
+template <class T>
+static KeptBuf dev_buf(T*& p, size_t bytes = 0) { return {(void**)&p, bytes, false, 0u, nullptr}; }
+template <class T>
+static KeptBuf host_buf(T*& p, size_t bytes = 0, unsigned flags = hipHostMallocDefault, T** dev = nullptr) { return {(void**)&p, bytes, true, flags, (void**)dev}; }
+
+// Free the buffers of a group: every pointer null (a mapped block's device address too) and, with it, their shared capacity zero.
+static void release_bufs(std::initializer_list<KeptBuf> bufs) {
+  for (const KeptBuf& b : bufs) {
+    if (*b.p) (void)(b.host ? hipHostFree(*b.p) : hipFree(*b.p));
+    *b.p = nullptr;
+    if (b.dev) *b.dev = nullptr;
+  }
+}
+static void release_bufs(size_t& cap, std::initializer_list<KeptBuf> bufs) { release_bufs(bufs); cap = 0; }
+
+// Regrow a group of buffers that share one capacity, only when it is too small for `need`: all freed, then each allocated at its own
+// size, and the capacity becomes `grown` (>= need, in the field's own units: the site's growth policy).  Any failure leaves the whole
+// group empty -- pointers null, capacity zero -- so that the next call grows it again instead of running on freed memory, and takes
+// the runtime's sticky error with it.  "alloc_fail_at" (cg1_ctx_set_param): the k-th allocation attempted here fails without a call
+// into the runtime, down the same path.
+static int grow_bufs(Ctx* ctx, size_t& cap, size_t need, size_t grown, std::initializer_list<KeptBuf> bufs) {
+  if (need <= cap) return CG1_OK;
+  release_bufs(cap, bufs);
+  for (const KeptBuf& b : bufs) {
+    const bool injected = ctx->alloc_fail_at && --ctx->alloc_fail_at == 0;
+    hipError_t e = injected ? hipErrorOutOfMemory : b.host ? hipHostMalloc(b.p, b.bytes, b.flags) : hipMalloc(b.p, b.bytes);
+    if (e == hipSuccess && b.dev) e = hipHostGetDevicePointer(b.dev, *b.p, 0);
+    if (e == hipSuccess) continue;
+    if (!injected) (void)hipGetLastError();
+    release_bufs(cap, bufs);
+    snprintf(ctx->err, sizeof ctx->err, "growing a kept buffer to %zu bytes failed: %s%s", b.bytes, hipGetErrorString(e), injected ? " (injected: alloc_fail_at)" : "");
+    return CG1_ERR_HIP;
+  }
+  cap = grown;
+  return CG1_OK;
+}
+// ... one device buffer of T ...
+template <class T>
+static int grow_device(Ctx* ctx, T*& d, size_t& cap, size_t need, size_t grown) { return grow_bufs(ctx, cap, need, grown, {dev_buf(d, grown * sizeof(T))}); }
+// ... and a page-locked block with its device twin.  flags: hipHostMalloc's; h_dev (nullable): where a mapped block's device address goes
+static int grow_pinned_pair(Ctx* ctx, uint8_t*& h, uint8_t** h_dev, uint8_t*& d, size_t& cap, size_t need, size_t grown, unsigned flags) {
+  return grow_bufs(ctx, cap, need, grown, {host_buf(h, grown, flags, h_dev), dev_buf(d, grown)});
+}
+
+// the views into d_zblock (none while it is empty): [lenhist 2*LEN_BINS words][any_multi][combined: nb_total bytes][heavy count][heavy ids]
+static void zblock_views(Ctx* c, size_t nb_total, size_t hcap) {
+  uint32_t* z = c->d_zblock;
+  const size_t z0 = 2 * LEN_BINS + 1, h0 = z0 + (nb_total + 3) / 4;
+  c->d_lenhist = z;
+  c->d_any_multi = z ? z + 2 * LEN_BINS : nullptr;
+  c->d_combined = z ? reinterpret_cast<uint8_t*>(z + z0) : nullptr;
+  c->d_heavy = z ? z + h0 : nullptr;
+  c->cap_heavy = z ? hcap : 0;
+  c->cap_combined = z ? nb_total : 0;
+}
+
+// the MSM chains' scratch (what ensure() and batched_chain_enqueue grow); the context's other kept buffers go with cg1_ctx_destroy
 static void free_bufs(Ctx* c) {
-  auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  F(c->d_pts); F(c->d_flags); F(c->d_hist); F(c->d_off); F(c->d_choff); F(c->d_sorted); F(c->d_blocktot); F(c->d_desc);
-  F(c->d_sums); F(c->d_segrun); F(c->d_segtot); F(c->d_out); F(c->d_order); F(c->d_zblock); F(c->d_partial);
-  c->d_lenhist = c->d_heavy = c->d_any_multi = nullptr; c->d_combined = nullptr; c->cap_zblock = 0; c->cap_heavy = 0; c->cap_combined = 0;
-  c->cap_partial = 0;
-  F(c->d_digits); F(c->d_part); F(c->d_blockcnt); F(c->d_ublocktot); F(c->d_boffs); F(c->d_gsum); F(c->d_bout);
-  F(c->d_slice_base); F(c->d_slicehist); F(c->d_subbase); F(c->d_bigflag); c->cap_bigflag = 0; c->cap_slices = 0;
-  if (c->h_bout) { (void)hipHostFree(c->h_bout); c->h_bout = nullptr; }
-  if (c->h_lin) { (void)hipHostFree(c->h_lin); c->h_lin = nullptr; c->h_lin_dev = nullptr; c->cap_h_lin = 0; }
-  if (c->d_gout) { (void)hipFree(c->d_gout); c->d_gout = nullptr; }
-  if (c->h_gout) { (void)hipHostFree(c->h_gout); c->h_gout = nullptr; }
-  c->cap_gout = 0;
-  c->cap_boffs = c->cap_gsum = c->cap_bout = 0;
-  c->cap_digits = c->cap_part = c->cap_blockcnt = 0;
-  if (c->h_out) { (void)hipHostFree(c->h_out); c->h_out = nullptr; }
-  c->cap_n = c->cap_nb = c->cap_chunks = c->cap_entries = c->cap_out = 0;
+  release_bufs(c->cap_n, {dev_buf(c->d_pts), dev_buf(c->d_flags)});
+  release_bufs(c->cap_nb, {dev_buf(c->d_hist), dev_buf(c->d_off), dev_buf(c->d_choff), dev_buf(c->d_blocktot), dev_buf(c->d_segrun), dev_buf(c->d_segtot)});
+  release_bufs(c->cap_entries, {dev_buf(c->d_sorted)});
+  release_bufs(c->cap_chunks, {dev_buf(c->d_order), dev_buf(c->d_desc), dev_buf(c->d_sums)});
+  release_bufs(c->cap_zblock, {dev_buf(c->d_zblock)});
+  zblock_views(c, 0, 0);
+  release_bufs(c->cap_digits, {dev_buf(c->d_digits)});
+  release_bufs(c->cap_part, {dev_buf(c->d_part)});
+  release_bufs(c->cap_bigflag, {dev_buf(c->d_bigflag), dev_buf(c->d_slice_base), dev_buf(c->d_subbase)});
+  release_bufs(c->cap_slices, {dev_buf(c->d_slicehist)});
+  release_bufs(c->cap_blockcnt, {dev_buf(c->d_blockcnt), dev_buf(c->d_ublocktot)});
+  release_bufs(c->cap_partial, {dev_buf(c->d_partial)});
+  release_bufs(c->cap_out, {dev_buf(c->d_out), host_buf(c->h_out, 0, 0u, &c->h_out_dev)});
+  release_bufs(c->cap_boffs, {dev_buf(c->d_boffs)});
+  release_bufs(c->cap_gsum, {dev_buf(c->d_gsum)});
+  release_bufs(c->cap_bout, {dev_buf(c->d_bout), host_buf(c->h_bout)});
+  release_bufs(c->cap_gout, {dev_buf(c->d_gout), host_buf(c->h_gout)});
+  release_bufs(c->cap_h_lin, {host_buf(c->h_lin, 0, 0u, &c->h_lin_dev)});
 }
 
 static int ensure(Ctx* ctx, size_t n, size_t nb_total, size_t nlw, size_t nitems, uint32_t L, bool need_points = true) {
   size_t entries = n * nlw;
   size_t chunks = nb_total + entries / L + 1;
-  if (need_points && n > ctx->cap_n) {
-    if (ctx->d_pts) (void)hipFree(ctx->d_pts);
-    if (ctx->d_flags) (void)hipFree(ctx->d_flags);
-    HIPCHK(hipMalloc(&ctx->d_pts, n * sizeof(PreparedPoint)));
-    HIPCHK(hipMalloc(&ctx->d_flags, n + 16));
-    ctx->cap_n = n;
-  }
-  if (nb_total > ctx->cap_nb) {
-    auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(ctx->d_hist); F(ctx->d_off); F(ctx->d_choff); F(ctx->d_blocktot); F(ctx->d_segrun); F(ctx->d_segtot);
-    HIPCHK(hipMalloc(&ctx->d_hist, nb_total * 4));
-    HIPCHK(hipMalloc(&ctx->d_off, (nb_total + 1) * 4));
-    HIPCHK(hipMalloc(&ctx->d_choff, (nb_total + 1) * 4));
-    HIPCHK(hipMalloc(&ctx->d_blocktot, (nb_total / SCAN_ITEMS + 2) * sizeof(uint2)));
-    HIPCHK(hipMalloc(&ctx->d_segrun, nb_total * sizeof(PointSum)));   // >= nb_total / m segments
-    HIPCHK(hipMalloc(&ctx->d_segtot, nb_total * sizeof(PointSum)));
-    ctx->cap_nb = nb_total;
-  }
-  if (entries > ctx->cap_entries) {
-    if (ctx->d_sorted) (void)hipFree(ctx->d_sorted);
-    HIPCHK(hipMalloc(&ctx->d_sorted, (entries + 1) * 4));
-    ctx->cap_entries = entries;
-  }
-  if (chunks > ctx->cap_chunks) {
-    if (ctx->d_desc) (void)hipFree(ctx->d_desc);
-    if (ctx->d_sums) (void)hipFree(ctx->d_sums);
-    if (ctx->d_order) (void)hipFree(ctx->d_order);
-    HIPCHK(hipMalloc(&ctx->d_order, chunks * 4));
-    HIPCHK(hipMalloc(&ctx->d_desc, chunks * sizeof(uint2)));
-    HIPCHK(hipMalloc(&ctx->d_sums, chunks * sizeof(PointSum)));
-    ctx->cap_chunks = chunks;
-  }
+  int rc = CG1_OK;
+  if (need_points && (rc = grow_bufs(ctx, ctx->cap_n, n, n, {dev_buf(ctx->d_pts, n * sizeof(PreparedPoint)), dev_buf(ctx->d_flags, n + 16)}))) return rc;
+  if ((rc = grow_bufs(ctx, ctx->cap_nb, nb_total, nb_total,
+                      {dev_buf(ctx->d_hist, nb_total * 4), dev_buf(ctx->d_off, (nb_total + 1) * 4), dev_buf(ctx->d_choff, (nb_total + 1) * 4),
+                       dev_buf(ctx->d_blocktot, (nb_total / SCAN_ITEMS + 2) * sizeof(uint2)),
+                       dev_buf(ctx->d_segrun, nb_total * sizeof(PointSum)),      // >= nb_total / m segments
+                       dev_buf(ctx->d_segtot, nb_total * sizeof(PointSum))}))) return rc;
+  if ((rc = grow_bufs(ctx, ctx->cap_entries, entries, entries, {dev_buf(ctx->d_sorted, (entries + 1) * 4)}))) return rc;
+  if ((rc = grow_bufs(ctx, ctx->cap_chunks, chunks, chunks,
+                      {dev_buf(ctx->d_order, chunks * 4), dev_buf(ctx->d_desc, chunks * sizeof(uint2)), dev_buf(ctx->d_sums, chunks * sizeof(PointSum))}))) return rc;
   {
-    // [lenhist 2*LEN_BINS words][any_multi][combined: nb_total bytes][heavy count][heavy ids]: the call clears everything up to
-    // and including the heavy count with one memset
+    // the call clears everything up to and including the heavy count with one memset
     const size_t hcap = entries / ((size_t)L * (HEAVY_MIN_CHUNKS - 1)) + 2;     // a heavy bucket holds > (MIN-1)*L entries
-    const size_t z0 = 2 * LEN_BINS + 1, h0 = z0 + (nb_total + 3) / 4, words = h0 + 1 + hcap + 64;     // (+64: room for the 256-byte round-up of the per-call memset)
-    if (words > ctx->cap_zblock) {
-      if (ctx->d_zblock) (void)hipFree(ctx->d_zblock);
-      ctx->d_zblock = nullptr; ctx->cap_zblock = 0;
-      HIPCHK(hipMalloc(&ctx->d_zblock, words * 4));
-      ctx->cap_zblock = words;
-    }
-    ctx->d_lenhist = ctx->d_zblock;
-    ctx->d_any_multi = ctx->d_zblock + 2 * LEN_BINS;
-    ctx->d_combined = reinterpret_cast<uint8_t*>(ctx->d_zblock + z0);
-    ctx->d_heavy = ctx->d_zblock + h0;
-    ctx->cap_heavy = hcap;
-    ctx->cap_combined = nb_total;
+    const size_t words = 2 * LEN_BINS + 1 + (nb_total + 3) / 4 + 1 + hcap + 64;     // (+64: room for the 256-byte round-up of the per-call memset)
+    rc = grow_bufs(ctx, ctx->cap_zblock, words, words, {dev_buf(ctx->d_zblock, words * 4)});
+    zblock_views(ctx, nb_total, hcap);
+    if (rc) return rc;
   }
   if (ctx->use_partition_sort && n <= PART_MAX_N) {
     const size_t nslices = (n + PART_TILE - 1) / PART_TILE;
     const size_t nbc = nlw * 128 * nslices + 1;            // nbins <= 128
-    if (entries > ctx->cap_digits) {
-      if (ctx->d_digits) (void)hipFree(ctx->d_digits);
-      HIPCHK(hipMalloc(&ctx->d_digits, entries * 2 + 16));
-      ctx->cap_digits = entries;
-    }
-    if (entries > ctx->cap_part) {
-      if (ctx->d_part) (void)hipFree(ctx->d_part);
-      HIPCHK(hipMalloc(&ctx->d_part, (entries + 1) * 4));
-      ctx->cap_part = entries;
-    }
-    if (nlw * 128 > ctx->cap_bigflag) {
-      auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-      F(ctx->d_bigflag); F(ctx->d_slice_base); F(ctx->d_subbase);
-      HIPCHK(hipMalloc(&ctx->d_bigflag, nlw * 128 + 16));
-      HIPCHK(hipMalloc(&ctx->d_slice_base, (nlw * 128 + 1) * 4));
-      HIPCHK(hipMalloc(&ctx->d_subbase, nlw * 128 * 256 * 4));
-      ctx->cap_bigflag = nlw * 128;
-    }
-    {
-      const size_t max_slices = entries / SLICE + nlw * 128 + 1;       // sum over bins of ceil(size / SLICE)
-      if (max_slices > ctx->cap_slices) {
-        if (ctx->d_slicehist) (void)hipFree(ctx->d_slicehist);
-        HIPCHK(hipMalloc(&ctx->d_slicehist, max_slices * 256 * 4));
-        ctx->cap_slices = max_slices;
-      }
-    }
-    if (nbc > ctx->cap_blockcnt) {
-      if (ctx->d_blockcnt) (void)hipFree(ctx->d_blockcnt);
-      if (ctx->d_ublocktot) (void)hipFree(ctx->d_ublocktot);
-      HIPCHK(hipMalloc(&ctx->d_blockcnt, nbc * 4));
-      HIPCHK(hipMalloc(&ctx->d_ublocktot, (nbc / SCAN_ITEMS + 2) * 4));
-      ctx->cap_blockcnt = nbc;
-    }
+    const size_t nbins = nlw * 128;
+    const size_t max_slices = entries / SLICE + nbins + 1;       // sum over bins of ceil(size / SLICE)
+    if ((rc = grow_bufs(ctx, ctx->cap_digits, entries, entries, {dev_buf(ctx->d_digits, entries * 2 + 16)}))) return rc;
+    if ((rc = grow_bufs(ctx, ctx->cap_part, entries, entries, {dev_buf(ctx->d_part, (entries + 1) * 4)}))) return rc;
+    if ((rc = grow_bufs(ctx, ctx->cap_bigflag, nbins, nbins,
+                        {dev_buf(ctx->d_bigflag, nbins + 16), dev_buf(ctx->d_slice_base, (nbins + 1) * 4), dev_buf(ctx->d_subbase, nbins * 256 * 4)}))) return rc;
+    if ((rc = grow_bufs(ctx, ctx->cap_slices, max_slices, max_slices, {dev_buf(ctx->d_slicehist, max_slices * 256 * 4)}))) return rc;
+    if ((rc = grow_bufs(ctx, ctx->cap_blockcnt, nbc, nbc, {dev_buf(ctx->d_blockcnt, nbc * 4), dev_buf(ctx->d_ublocktot, (nbc / SCAN_ITEMS + 2) * 4)}))) return rc;
   }
   size_t nout = nlw * nitems;
-  if (nout * 64 > ctx->cap_partial) {
-    if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-    HIPCHK(hipMalloc(&ctx->d_partial, nout * 64 * sizeof(PointSum)));
-    ctx->cap_partial = nout * 64;
-  }
-  if (nout > ctx->cap_out) {
-    if (ctx->d_out) (void)hipFree(ctx->d_out);
-    if (ctx->h_out) (void)hipHostFree(ctx->h_out);
-    HIPCHK(hipMalloc(&ctx->d_out, (nout + 1) * sizeof(PointWords)));      // + one record: the input-validation flag word
-    // mapped + coherent, said explicitly: the export kernel writes it and the host polls the flag word without any runtime call in
-    // between (with HIP_HOST_COHERENT=0 the default allocation is non-coherent and the poll would only end through its stream query)
-    HIPCHK(hipHostMalloc(&ctx->h_out, (nout + 1) * sizeof(PointWords), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer((void**)&ctx->h_out_dev, ctx->h_out, 0));
-    ctx->cap_out = nout;
-  }
-  return CG1_OK;
+  if ((rc = grow_bufs(ctx, ctx->cap_partial, nout * 64, nout * 64, {dev_buf(ctx->d_partial, nout * 64 * sizeof(PointSum))}))) return rc;
+  // h_out mapped + coherent, said explicitly: the export kernel writes it and the host polls the flag word without any runtime call in
+  // between (with HIP_HOST_COHERENT=0 the default allocation is non-coherent and the poll would only end through its stream query)
+  return grow_bufs(ctx, ctx->cap_out, nout, nout,
+                   {dev_buf(ctx->d_out, (nout + 1) * sizeof(PointWords)),      // + one record: the input-validation flag word
+                    host_buf(ctx->h_out, (nout + 1) * sizeof(PointWords), hipHostMallocMapped | hipHostMallocCoherent, &ctx->h_out_dev)});
 }
 
 // bytes of d_zblock the per-call memset clears: everything up to and including the heavy-bucket count, rounded up to 256 B

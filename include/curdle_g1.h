@@ -108,6 +108,9 @@ void* cg1_ctx_stream(cg1_ctx* ctx);                                  /* the cont
  *   verifier front-end  "fe_rows" (1: block program, 0: byte-level machine), "fe_timed" (shader-clock split of a launch), "fe_prio" (0..3)
  *   fixed-base tables   "fixed_slice" (terms per workgroup of k_table_msm, 1..128; 0: by the size of the call), "fixed_waves" (4, 8, 16 waves per
  *                       workgroup; 0: by the size of the call)
+ *   test support        "alloc_fail_at" (k >= 1: the k-th allocation this context attempts from now on while growing a buffer it keeps between calls
+ *                       -- its own, or a table's / front-end handle's -- fails as out of memory without reaching the runtime, then the parameter is
+ *                       0 again; 0 disarms.  The refused call returns CG1_ERR_HIP and leaves the buffers it was growing empty, as a real failure does)
  * Unknown names and out-of-range values return CG1_ERR_ARG. */
 int  cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value);
 
