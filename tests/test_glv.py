@@ -8,20 +8,12 @@ import numpy as np
 import pytest
 
 from curdleproofs_pie_amd import _native as N
+from msm_digit_model import split_native as _split
 from oracle import bls12_381 as O
 
 Z = 0xD201000000010000
 LAM = Z * Z - 1
 R = O.R
-
-
-def _split(k: int):
-    k1 = ctypes.create_string_buffer(16)
-    k2 = ctypes.create_string_buffer(16)
-    n1, n2 = ctypes.c_int(), ctypes.c_int()
-    N.cg1_glv_split(k.to_bytes(32, "little"), k1, k2, ctypes.byref(n1), ctypes.byref(n2))
-    a, b = int.from_bytes(k1.raw, "little"), int.from_bytes(k2.raw, "little")
-    return (-a if n1.value else a), (-b if n2.value else b)
 
 
 def test_lambda_is_the_eigenvalue_of_phi():
