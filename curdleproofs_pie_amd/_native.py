@@ -326,6 +326,12 @@ cg1_whisk_shuffle_prove_device = _proto("cg1_whisk_shuffle_prove_device", c_int,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 cg1_whisk_shuffle_front_emulate = _proto("cg1_whisk_shuffle_front_emulate", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p)
+# Whisk shuffles proved from a seed: the draws on the device (csrc/capi_whisk_shuffle.h; the format: csrc/whisk_shuffle_host.h)
+cg1_whisk_shuffle_draws_device = _proto("cg1_whisk_shuffle_draws_device", c_int, c_void_p, c_size_t, c_size_t, c_void_p, ctypes.c_uint64, c_void_p, c_void_p)
+cg1_whisk_shuffle_draws = _proto("cg1_whisk_shuffle_draws", c_int, c_size_t, c_size_t, c_void_p, ctypes.c_uint64, c_void_p, c_void_p)
+cg1_whisk_shuffle_prove_seeded = _proto("cg1_whisk_shuffle_prove_seeded", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p)
+WHISK_SHUFFLE_DRAWS_MAX_PROVERS, WHISK_SHUFFLE_NO_DECODE, WHISK_SHUFFLE_NOT_G1 = 4096, 2, 3      # CG1_WHISK_SHUFFLE_* of include/curdle_g1.h
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -355,6 +361,7 @@ EXPORTED_SYMBOLS = [
     "cg1_same_scalar_proof_bytes", "cg1_same_scalar_prove_device", "cg1_same_scalar_emulate",
     "cg1_shuffle_prover_proof_bytes", "cg1_shuffle_prove_device", "cg1_shuffle_begin_emulate",
     "cg1_whisk_shuffle_proof_bytes", "cg1_whisk_shuffle_front", "cg1_whisk_shuffle_prove_device", "cg1_whisk_shuffle_front_emulate",
+    "cg1_whisk_shuffle_draws_device", "cg1_whisk_shuffle_draws", "cg1_whisk_shuffle_prove_seeded",
     "cg1_tracker_match_device", "cg1_tracker_match", "cg1_tracker_match_last_ms",
 ]
 
@@ -694,6 +701,33 @@ class Context:
                                                   trackers96, u32(perm), k32, vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32, blinders32,
                                                   vec_r32, post, out))
         return post.raw[: 96 * ell * P], out.raw[: wb * P]
+
+    def whisk_shuffle_draws_device(self, ell: int, n_provers: int, seed32: bytes, first_index: int = 0):
+        """cg1_whisk_shuffle_draws_device: the seeded draws of n_provers shuffles, made on the device.
+        -> (perm as a list of n_provers * ell ints, the (3 (ell + 4) + 14) * n_provers scalars in the column layout, as bytes)."""
+        assert len(seed32) == 32
+        perm = (ctypes.c_uint32 * max(1, ell * n_provers))()
+        sc = ctypes.create_string_buffer(max(1, 32 * (3 * (ell + 4) + 14) * n_provers))
+        self.check(cg1_whisk_shuffle_draws_device(self.handle, ell, n_provers, seed32, first_index, perm, sc))
+        return list(perm)[: ell * n_provers], sc.raw[: 32 * (3 * (ell + 4) + 14) * n_provers]
+
+    def whisk_shuffle_prove_seeded(self, tab: "FixedTable", ell: int, n_provers: int, g_index, h_index, u_index, gt_index, gu_index, gth_affine96: bytes,
+                                   trackers96: bytes, seed32: bytes, first_index: int):
+        """cg1_whisk_shuffle_prove_seeded: n_provers Whisk shuffles of one ell proved in one native call from tracker bytes and a 32-byte
+        seed, every draw made on the device.  -> (post96, proofs, status, bad_at): zero bytes, a code (WHISK_SHUFFLE_*) and tracker * 2 + half
+        for a prover whose trackers were refused; raises (check) on a refusal of the whole call."""
+        if not tab.handle:
+            raise NativeError("the fixed-base table is closed")
+        P = n_provers
+        assert len(g_index) == ell * P and len(h_index) == 4 * P and len(u_index) == len(gt_index) == len(gu_index) == P
+        assert len(gth_affine96) == 288 and len(trackers96) == 96 * ell * P and len(seed32) == 32
+        u32 = lambda v: (ctypes.c_uint32 * max(1, len(v)))(*v)
+        wb = int(cg1_whisk_shuffle_proof_bytes(ell))
+        post, out = ctypes.create_string_buffer(max(1, 96 * ell * P)), ctypes.create_string_buffer(max(1, wb * P))
+        st, at = (ctypes.c_int32 * max(1, P))(), (ctypes.c_uint32 * max(1, P))()
+        self.check(cg1_whisk_shuffle_prove_seeded(self.handle, tab.handle, ell, P, u32(g_index), u32(h_index), u32(u_index), u32(gt_index), u32(gu_index), gth_affine96,
+                                                  trackers96, seed32, first_index, post, out, st, at))
+        return post.raw[: 96 * ell * P], out.raw[: wb * P], list(st)[:P], list(at)[:P]
 
     def last_counts(self) -> dict:
         """Of the last MSM call: bucket entries (non-zero digits), chunks, and mixed additions = entries - chunks."""

@@ -74,6 +74,7 @@ int chain_reserve(cg1_ctx* ctx, cg1_fixed* t, size_t total, uint8_t*& H, uint8_t
   ctx->pend.active = false;
   { const int rc = cg1::grow_pinned_pair(ctx, t->h_chain, nullptr, t->d_chain, t->cap_chain, total, total, hipHostMallocDefault); if (rc) return rc; }
   H = t->h_chain; D = t->d_chain;
+  t->chain_used = std::max(t->chain_used, total);
   return CG1_OK;
 }
 void chain_clear(uint8_t* H, const ChainLayout& L, size_t P) { memset(H + L.status, 0, 16); memset(H + L.clocks, 0, P * 16); }

@@ -35,6 +35,7 @@ struct cg1_table {
 struct cg1_fixed : cg1_table {
   cg1::PreparedPoint* d_tab = nullptr;                      // n_bases x GEN_ENTRIES records (build_fixed_table)
   uint8_t* h_chain = nullptr; uint8_t* d_chain = nullptr; size_t cap_chain = 0;      // the device provers' staging block and its device twin, re-laid-out by every call (capi_chain.h)
+  size_t chain_used = 0;                // the largest layout of that block since a caller last reset it: what a call that wipes it has to cover
   cg1_light* smsm_light = nullptr; size_t cap_smsm_bases = 0;                  // the light table a device prover builds over per-proof bases (chain_light_scratch, capi_light.h): regrown only when too small
 };
 

@@ -3,6 +3,8 @@
 //                                    k vec_S) by k_whisk_permute_mul (kernels_whisk_shuffle.h), M as one k_table_msm over the CRS table --
 //                                    one stream, one wait
 //   cg1_whisk_shuffle_prove_device   the front, then cg1_shuffle_prove_device (capi_shuffle.h) on what it left, bases certified
+//   cg1_whisk_shuffle_draws_device   permutation, k and every blinder of n_provers shuffles from a 32-byte seed (k_whisk_draws, k_whisk_fisher_yates)
+//   cg1_whisk_shuffle_prove_seeded   those draws, the front with a status PER PROVER, and the chain on the provers the front did not refuse
 // The refusals and their texts are shared with the host twin cg1_whisk_shuffle_front_emulate (whisk_shuffle_host.h, lazy_host.cpp).
 // Part of the single translation unit csrc/msm_gpu.hip (included there; not a stand-alone header).
 #pragma once
@@ -12,7 +14,7 @@ namespace {
 struct WhiskLayout : ChainLayout {
   size_t enc, perm, k, tb, sc, offs;                        // uploaded
   size_t wst;                                               // uploaded as zeros, read back: k_whisk_status's word
-  size_t rs, tu, post, m48, st_dec, in_g1, st_msm;          // read back
+  size_t rs, tu, post, m48, st_dec, in_g1, st_msm, pst;     // read back (pst: k_whisk_status_provers' words)
 };
 WhiskLayout whisk_layout(size_t ell, size_t P) {
   WhiskLayout L{};
@@ -24,16 +26,18 @@ WhiskLayout whisk_layout(size_t ell, size_t P) {
   L.wst = L.take(16);
   L.up_end = L.total;
   L.rs = L.take(pts * 96); L.tu = L.take(pts * 96); L.post = L.take(pts * 48); L.m48 = L.take(P * 48);
-  L.st_dec = L.take(pts); L.in_g1 = L.take(pts); L.st_msm = L.take(16);
+  L.st_dec = L.take(pts); L.in_g1 = L.take(pts); L.st_msm = L.take(16); L.pst = L.take(P * 4);
   L.down_end = L.total;
   return L;
 }
 
 // The front on the context's stream.  The outputs are host buffers of the caller's or of the whole call's; nothing is written into them
-// before every refusal has been ruled out.
+// before every refusal has been ruled out.  out_status / out_bad_at (both or neither): a tracker point that does not decode or lies
+// outside G1 then refuses ITS prover only -- code and tracker 2 + half of its first such point; its four outputs are zeros -- and the call
+// goes on for the others.
 int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t P, const uint32_t* g_index, const uint32_t* h_index, const uint8_t* trackers96,
                 const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96, uint8_t* out_post96,
-                uint8_t* out_m48) {
+                uint8_t* out_m48, int32_t* out_status = nullptr, uint32_t* out_bad_at = nullptr) {
   constexpr size_t NB = cg1whisk_host::N_BLINDERS;
   if (const int rc = cg1whisk_host::check_shape(ctx->err, sizeof ctx->err, who, ell)) return rc;
   const size_t n = ell + NB, pts = P * 2 * ell;
@@ -77,12 +81,17 @@ int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t 
   // ---- decode, certify, the call's status word, then the multiplications
   hipLaunchKernelGGL(cg1::k_batch_decompress_row, dim3((np + 3u) / 4u), dim3(64), 0, ctx->stream, (const uint8_t*)(D + L.enc), (uint32_t*)(D + L.rs), D + L.st_dec, np);
   hipLaunchKernelGGL(cg1::k_subgroup_row, dim3(np), dim3(64), 0, ctx->stream, (const uint32_t*)(D + L.rs), np, D + L.in_g1);
-  hipLaunchKernelGGL(cg1whisk::k_whisk_status, dim3(std::min<uint32_t>((np + 255u) / 256u, 64u)), dim3(256), 0, ctx->stream, (const uint8_t*)(D + L.st_dec),
-                     (const uint8_t*)(D + L.in_g1), np, (uint32_t*)(D + L.wst));
+  if (out_status)
+    hipLaunchKernelGGL(cg1whisk::k_whisk_status_provers, dim3(Pn), dim3(64), 0, ctx->stream, (const uint8_t*)(D + L.st_dec), (const uint8_t*)(D + L.in_g1), (uint32_t)ell,
+                       (uint32_t*)(D + L.pst));
+  else
+    hipLaunchKernelGGL(cg1whisk::k_whisk_status, dim3(std::min<uint32_t>((np + 255u) / 256u, 64u)), dim3(256), 0, ctx->stream, (const uint8_t*)(D + L.st_dec),
+                       (const uint8_t*)(D + L.in_g1), np, (uint32_t*)(D + L.wst));
   {
     cg1whisk::PermuteMulArgs a;
     a.ell = (uint32_t)ell; a.n_out = np;
     a.rs96 = (const uint32_t*)(D + L.rs); a.perm = (const uint32_t*)(D + L.perm); a.k = (const uint32_t*)(D + L.k); a.status = (const uint32_t*)(D + L.wst);
+    a.prover_status = out_status ? (const uint32_t*)(D + L.pst) : nullptr;
     a.tu96 = (uint32_t*)(D + L.tu); a.post48 = (uint32_t*)(D + L.post);
     hipLaunchKernelGGL(cg1whisk::k_whisk_permute_mul, dim3(np), dim3(64), 0, ctx->stream, a);
   }
@@ -90,7 +99,7 @@ int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t 
   if (const int rc = chain_download(ctx, t, L)) return shuffle_refuse(ctx, rc);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipGetLastError());
-  for (int pass = 0; pass < 2; ++pass)                      // the decoder's refusals first, then the subgroup test's, each in tracker order
+  for (int pass = 0; pass < 2 && !out_status; ++pass)       // the decoder's refusals first, then the subgroup test's, each in tracker order
     for (size_t p = 0; p < P; ++p)
       for (size_t i = 0; i < ell; ++i)
         for (int half = 0; half < 2; ++half) {
@@ -102,6 +111,65 @@ int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t 
   if (const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + L.st_msm)[0])) return rc;
   memcpy(out_rs_affine96, H + L.rs, pts * 96); memcpy(out_tu_affine96, H + L.tu, pts * 96);
   memcpy(out_post96, H + L.post, pts * 48); memcpy(out_m48, H + L.m48, P * 48);
+  for (size_t p = 0; out_status && p < P; ++p) {
+    const uint32_t w = reinterpret_cast<const uint32_t*>(H + L.pst)[p];
+    out_status[p] = (int32_t)(w >> 16); out_bad_at[p] = w & 0xffffu;
+    if (!w) continue;                                       // (k_whisk_permute_mul wrote nothing for it: the block holds an earlier call's bytes there)
+    memset(out_rs_affine96 + p * 2 * ell * 96, 0, 2 * ell * 96); memset(out_tu_affine96 + p * 2 * ell * 96, 0, 2 * ell * 96);
+    memset(out_post96 + p * 2 * ell * 48, 0, 2 * ell * 48); memset(out_m48 + p * 48, 0, 48);
+  }
+  return CG1_OK;
+}
+
+// the chain's refusal text under the entry's name
+void whisk_chain_text(cg1_ctx* ctx, const char* who) {
+  static const char* const chain = "cg1_shuffle_prove_device";
+  const size_t cl = strlen(chain);
+  if (strncmp(ctx->err, chain, cl) == 0) {
+    const std::string tail(ctx->err + cl);
+    snprintf(ctx->err, sizeof ctx->err, "%s%s", who, tail.c_str());
+  }
+}
+
+// ---- the seeded draws
+void whisk_wipe(void* p, size_t n) {                        // a memset the optimiser may not drop
+  memset(p, 0, n);
+  __asm__ __volatile__("" : : "r"(p) : "memory");
+}
+struct WipedBytes {                                         // host staging of secrets: zeroed on every exit path
+  std::vector<uint8_t> v;
+  ~WipedBytes() { if (!v.empty()) whisk_wipe(v.data(), v.size()); }
+};
+struct DrawBlock { size_t swaps, perm, scalars, total; };   // ctx->d_whisk_draws; the host staging holds [perm, total)
+DrawBlock whisk_draw_block(size_t ell, size_t P) {
+  auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
+  DrawBlock B;
+  B.swaps = 0; B.perm = up(P * (ell - 1) * 4); B.scalars = B.perm + up(P * ell * 4);
+  B.total = B.scalars + cg1whisk_host::draw_columns(ell, P).total * 32;
+  return B;
+}
+// k_whisk_draws and k_whisk_fisher_yates on the context's stream, ONE copy down (perm | scalars -> stage), the device buffer zeroed, one
+// wait.  The arguments have been checked (cg1whisk_host::check_draws).
+int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, uint64_t first_index, WipedBytes& stage) {
+  const DrawBlock B = whisk_draw_block(ell, P);
+  HIPCHK(hipSetDevice(ctx->device));
+  if (const int rc = cg1::grow_bufs(ctx, ctx->cap_whisk_draws, B.total, B.total, {cg1::dev_buf(ctx->d_whisk_draws, B.total)})) return rc;
+  uint8_t* D = (uint8_t*)ctx->d_whisk_draws;
+  stage.v.resize(B.total - B.perm);
+  cg1whisk::DrawArgs a;
+  memcpy(a.seed.w, seed32, 32);
+  a.ell = (uint32_t)ell; a.n_provers = (uint32_t)P; a.first_index = (uint32_t)first_index;      // (first_index = 2^32 only with P = 0)
+  a.swaps = (uint32_t*)(D + B.swaps); a.scalars = (uint32_t*)(D + B.scalars);
+  const uint32_t lanes = (uint32_t)P * cg1whisk_host::draw_count((uint32_t)ell);
+  hipLaunchKernelGGL(cg1whisk::k_whisk_draws, dim3((lanes + cg1merlin::LANES - 1) / cg1merlin::LANES), dim3(cg1merlin::LANES), 0, ctx->stream, a);
+  hipLaunchKernelGGL(cg1whisk::k_whisk_fisher_yates, dim3((uint32_t)P), dim3(64), 0, ctx->stream, (const uint32_t*)(D + B.swaps), (uint32_t)ell, (uint32_t*)(D + B.perm));
+  whisk_wipe(&a, sizeof a);
+  hipError_t e = hipMemcpyAsync(stage.v.data(), D + B.perm, B.total - B.perm, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t e2 = hipMemsetAsync(D, 0, B.total, ctx->stream);        // the draws do not outlive the call on the device, whatever the copy said
+  const hipError_t e3 = hipStreamSynchronize(ctx->stream);
+  e = e != hipSuccess ? e : e2 != hipSuccess ? e2 : e3;
+  HIPCHK(e);
+  HIPCHK(hipGetLastError());
   return CG1_OK;
 }
 }  // namespace
@@ -129,7 +197,6 @@ int cg1_whisk_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
                                    const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* blinders32, const uint8_t* vec_r32, uint8_t* out_post96,
                                    uint8_t* out_proofs) {
   static const char* const who = "cg1_whisk_shuffle_prove_device";
-  static const char* const chain = "cg1_shuffle_prove_device";
   if (!ctx) return CG1_ERR_HIP;
   if (n_provers == 0) return CG1_OK;
   const bool pointers_ok = g_index && h_index && u_index && gt_index && gu_index && gth_affine96 && trackers96 && perm && k32 && vec_m_blinders32 && vec_a_blinders32 &&
@@ -144,11 +211,7 @@ int cg1_whisk_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   proofs.resize(P * pb);
   if (const int rc = cg1_shuffle_prove_device(ctx, t, ell, P, g_index, h_index, u_index, gt_index, gu_index, gth_affine96, rs.data(), tu.data(), m48.data(), perm, k32,
                                               vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32, blinders32, vec_r32, 1, proofs.data(), nullptr)) {
-    const size_t cl = strlen(chain);                        // the chain's text under this entry's name
-    if (strncmp(ctx->err, chain, cl) == 0) {
-      const std::string tail(ctx->err + cl);
-      snprintf(ctx->err, sizeof ctx->err, "%s%s", who, tail.c_str());
-    }
+    whisk_chain_text(ctx, who);
     return rc;
   }
   memcpy(out_post96, post.data(), pts * 48);
@@ -156,6 +219,97 @@ int cg1_whisk_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
     memcpy(out_proofs + p * (48 + pb), &m48[48 * p], 48);
     memcpy(out_proofs + p * (48 + pb) + 48, &proofs[p * pb], pb);
   }
+  return CG1_OK;
+}
+
+int cg1_whisk_shuffle_draws_device(cg1_ctx* ctx, size_t ell, size_t n_provers, const uint8_t* seed32, uint64_t first_index, uint32_t* out_perm, uint8_t* out_scalars32) {
+  static const char* const who = "cg1_whisk_shuffle_draws_device";
+  if (!ctx) return CG1_ERR_HIP;
+  if (!seed32 || !out_perm || !out_scalars32) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
+  if (const int rc = cg1whisk_host::check_draws(ctx->err, sizeof ctx->err, who, ell, n_provers, first_index)) return rc;
+  if (n_provers == 0) return CG1_OK;
+  WipedBytes stage;
+  if (const int rc = whisk_draws_run(ctx, ell, n_provers, seed32, first_index, stage)) return rc;
+  const DrawBlock B = whisk_draw_block(ell, n_provers);
+  memcpy(out_perm, stage.v.data(), n_provers * ell * 4);
+  memcpy(out_scalars32, stage.v.data() + (B.scalars - B.perm), B.total - B.scalars);
+  return CG1_OK;
+}
+
+int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
+                                   const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* trackers96, const uint8_t* seed32,
+                                   uint64_t first_index, uint8_t* out_post96, uint8_t* out_proofs, int32_t* out_status, uint32_t* out_bad_at) {
+  static const char* const who = "cg1_whisk_shuffle_prove_seeded";
+  constexpr size_t NB = cg1whisk_host::N_BLINDERS;
+  if (!ctx) return CG1_ERR_HIP;
+  if (n_provers == 0) return CG1_OK;
+  const bool pointers_ok = g_index && h_index && u_index && gt_index && gu_index && gth_affine96 && trackers96 && seed32 && out_post96 && out_proofs && out_status && out_bad_at;
+  if (!t || t->device != ctx->device || !pointers_ok) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
+  const size_t P = n_provers, n = ell + NB;
+  if (const int rc = cg1whisk_host::check_shape(ctx->err, sizeof ctx->err, who, ell)) return rc;
+  if (P > CG1_SAME_MSM_MAX_PROVERS || P * 2 * n > CG1_LIGHT_MAX_BASES) {
+    snprintf(ctx->err, sizeof ctx->err, "%s: more than %d provers, or more than %d bases T | U, in one call", who, CG1_SAME_MSM_MAX_PROVERS, CG1_LIGHT_MAX_BASES);
+    return CG1_ERR_ARG; }
+  if (const int rc = cg1whisk_host::check_draws(ctx->err, sizeof ctx->err, who, ell, P, first_index)) return rc;
+  if (const int rc = chain_check_indices(ctx, who, t, {{g_index, P * ell}, {h_index, P * NB}, {u_index, P}, {gt_index, P}, {gu_index, P}})) return rc;
+  t->chain_used = 0;
+  // ---- 1. the draws: on the device, one copy down
+  WipedBytes stage;
+  if (const int rc = whisk_draws_run(ctx, ell, P, seed32, first_index, stage)) return rc;
+  const DrawBlock B = whisk_draw_block(ell, P);
+  const cg1whisk_host::DrawColumns C = cg1whisk_host::draw_columns(ell, P);
+  uint32_t* perm = reinterpret_cast<uint32_t*>(stage.v.data());
+  uint8_t* sc = stage.v.data() + (B.scalars - B.perm);
+  // ---- 2. the front, a status per prover
+  const size_t pts = P * 2 * ell, pb = cg1_shuffle_prover_proof_bytes(ell);
+  std::vector<uint8_t> rs(pts * 96), tu(pts * 96), post(pts * 48), m48(P * 48), proofs;
+  std::vector<int32_t> st(P);
+  std::vector<uint32_t> at(P);
+  // the table's staging block holds k, the permutations and, after the chain, every blinder: both copies are zeroed before any return
+  auto wipe_block = [&]() -> hipError_t {
+    const size_t used = std::min(t->chain_used, t->cap_chain);             // what this call's layouts reached
+    if (!used) return hipSuccess;
+    memset(t->h_chain, 0, used);
+    const hipError_t e = hipMemsetAsync(t->d_chain, 0, used, ctx->stream), e2 = hipStreamSynchronize(ctx->stream);
+    return e != hipSuccess ? e : e2;
+  };
+  if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, perm, sc + 32 * C.k, sc + 32 * C.mbl, rs.data(), tu.data(), post.data(), m48.data(),
+                                 st.data(), at.data())) { (void)wipe_block(); return rc; }
+  // ---- 3. the provers it did not refuse, moved to the front of every array, through the chain
+  std::vector<size_t> keep;
+  for (size_t p = 0; p < P; ++p) if (!st[p]) keep.push_back(p);
+  const size_t Q = keep.size();
+  std::vector<uint32_t> gi, hi, ui, gti, gui;
+  if (Q && Q < P) {
+    auto rows = [&](uint8_t* base, size_t row) { for (size_t q = 0; q < Q; ++q) memmove(base + q * row, base + keep[q] * row, row); };       // keep[q] >= q
+    rows(reinterpret_cast<uint8_t*>(perm), ell * 4);
+    rows(sc + 32 * C.k, 32); rows(sc + 32 * C.mbl, 32 * NB); rows(sc + 32 * C.abl, 64); rows(sc + 32 * C.cbl, 32 * NB); rows(sc + 32 * C.ipa_r, 32 * n);
+    rows(sc + 32 * C.z_head, 32 * (n - 2)); rows(sc + 32 * C.bl, 32 * 5); rows(sc + 32 * C.vec_r, 32 * n);
+    rows(rs.data(), 2 * ell * 96); rows(tu.data(), 2 * ell * 96); rows(m48.data(), 48);
+    auto pick = [&](std::vector<uint32_t>& dst, const uint32_t* src, size_t row) { dst.resize(Q * row); for (size_t q = 0; q < Q; ++q) memcpy(&dst[q * row], src + keep[q] * row, row * 4); };
+    pick(gi, g_index, ell); pick(hi, h_index, NB); pick(ui, u_index, 1); pick(gti, gt_index, 1); pick(gui, gu_index, 1);
+    g_index = gi.data(); h_index = hi.data(); u_index = ui.data(); gt_index = gti.data(); gu_index = gui.data();
+  }
+  int rc = CG1_OK;
+  if (Q) {
+    proofs.resize(Q * pb);
+    rc = cg1_shuffle_prove_device(ctx, t, ell, Q, g_index, h_index, u_index, gt_index, gu_index, gth_affine96, rs.data(), tu.data(), m48.data(), perm, sc + 32 * C.k,
+                                  sc + 32 * C.mbl, sc + 32 * C.abl, sc + 32 * C.cbl, sc + 32 * C.ipa_r, sc + 32 * C.z_head, sc + 32 * C.bl, sc + 32 * C.vec_r, 1, proofs.data(),
+                                  nullptr);
+    if (rc) whisk_chain_text(ctx, who);                     // (its "prover" counts the provers the front let through)
+  }
+  // ---- 4. secret hygiene (the draws' own device buffer and host staging: whisk_draws_run, WipedBytes), then the caller's buffers
+  const hipError_t wiped = wipe_block();
+  if (rc) return rc;
+  HIPCHK(wiped);
+  memset(out_post96, 0, pts * 48); memset(out_proofs, 0, P * (48 + pb));
+  for (size_t q = 0; q < Q; ++q) {                          // M || proof: the wire form cg1_shuffle_proof_bytes counts
+    const size_t p = keep[q];
+    memcpy(out_post96 + p * 2 * ell * 48, &post[p * 2 * ell * 48], 2 * ell * 48);
+    memcpy(out_proofs + p * (48 + pb), &m48[48 * q], 48);
+    memcpy(out_proofs + p * (48 + pb) + 48, &proofs[q * pb], pb);
+  }
+  memcpy(out_status, st.data(), P * 4); memcpy(out_bad_at, at.data(), P * 4);
   return CG1_OK;
 }
 }  // extern "C"

@@ -3,10 +3,16 @@
 // vec_U = perm(k vec_S), re-encode -- for every prover of a call at once.  The decoding and the subgroup test are the existing
 // k_batch_decompress_row (kernels_batch.h) and k_subgroup_row (fp_row.h); the kernels here are
 //     k_whisk_status        the call's status word: set when any of the call's points did not decode or lies outside G1
+//     k_whisk_status_provers  the same per prover, with the first offending point: the seeded entry refuses shuffle by shuffle
 //     k_whisk_permute_mul   out (p, h, i) = k_p * point perm[p][i] of half h of prover p, finished on the device: affine96 and the
 //                           48-byte encoding, scattered into the tracker layout T_i | U_i
-// Part of the single translation unit csrc/msm_gpu.hip (after kernels_fixed.h: row_inv, and kernels_generator.h: compress_words).
+// and, for the seeded entry (cg1_whisk_shuffle_prove_seeded), the draws of every shuffle made on the device:
+//     k_whisk_draws         one lane per (shuffle, draw): one SHAKE256 permutation -> a Fisher-Yates swap index or a scalar mod r
+//     k_whisk_fisher_yates  the swaps of a shuffle applied in order -> its permutation
+// Part of the single translation unit csrc/msm_gpu.hip (after kernels_fixed.h: row_inv, kernels_generator.h: compress_words, and
+// kernels_opening.h: Seed32 and the sponge layout of blinder_from_seed).
 #pragma once
+#include "whisk_shuffle_host.h"
 
 namespace cg1whisk {
 using namespace cg1;
@@ -22,12 +28,35 @@ __global__ void __launch_bounds__(256) k_whisk_status(const uint8_t* __restrict_
   if (bad) atomicOr(status, ST_REFUSED);
 }
 
+// status[p] = 0 for a clean prover, else code << 16 | (tracker 2 + half) of its FIRST offending point: a point the decoder refused
+// (ST_NO_DECODE) before one outside G1 (ST_NOT_G1), each in tracker order -- the order whisk_front reports them in.  One block per prover.
+constexpr uint32_t ST_NO_DECODE = 2u, ST_NOT_G1 = 3u;     // CG1_WHISK_SHUFFLE_NO_DECODE, CG1_WHISK_SHUFFLE_NOT_G1
+__global__ void __launch_bounds__(64) k_whisk_status_provers(const uint8_t* __restrict__ decode_status, const uint8_t* __restrict__ in_g1, uint32_t ell,
+                                                             uint32_t* __restrict__ status) {
+  constexpr uint32_t NONE = 0xffffffffu;
+  __shared__ uint32_t first[2];
+  const uint32_t p = blockIdx.x, two = 2u * ell;
+  if (threadIdx.x < 2u) first[threadIdx.x] = NONE;
+  __syncthreads();
+  uint32_t dec = NONE, g1 = NONE;
+  for (uint32_t q = threadIdx.x; q < two; q += 64u) {      // q = tracker 2 + half, ascending within a lane
+    const size_t at = (size_t)p * two + (size_t)(q & 1u) * ell + (q >> 1);
+    if (dec == NONE && decode_status[at] != 0u) dec = q;
+    if (g1 == NONE && in_g1[at] == 0u) g1 = q;
+  }
+  if (dec != NONE) atomicMin(&first[0], dec);
+  if (g1 != NONE) atomicMin(&first[1], g1);
+  __syncthreads();
+  if (threadIdx.x == 0u) status[p] = first[0] != NONE ? (ST_NO_DECODE << 16 | first[0]) : first[1] != NONE ? (ST_NOT_G1 << 16 | first[1]) : 0u;
+}
+
 struct PermuteMulArgs {
   uint32_t ell, n_out;                       // n_out = P 2 ell
   const uint32_t* rs96;                      // [P][2][ell] affine96, standard form, zeros = the identity: vec_R | vec_S as decoded
   const uint32_t* perm;                      // [P][ell]
   const uint32_t* k;                         // [P] 8 words, little-endian, below r
   const uint32_t* status;                    // k_whisk_status's word
+  const uint32_t* prover_status;             // nullable: k_whisk_status_provers' words; a prover whose word is set writes nothing
   uint32_t* tu96;                            // [P][2][ell] affine96: vec_T | vec_U
   uint32_t* post48;                          // [P][ell][2] 12 words each: T_i | U_i
 };
@@ -40,6 +69,7 @@ __global__ void __launch_bounds__(64) k_whisk_permute_mul(PermuteMulArgs a) {
   if (o >= a.n_out || a.status[0] != 0u) return;           // (uniform) a refused call writes nothing
   const uint32_t ell = a.ell, two = 2u * ell;
   const uint32_t p = o / two, h = (o - p * two) / ell, i = o - p * two - h * ell;
+  if (a.prover_status && a.prover_status[p] != 0u) return; // (uniform)
   uint32_t j = a.perm[(size_t)p * ell + i];
   j = j < ell ? j : ell - 1u;                              // the host has refused perm[i] >= ell; clamp all the same
   const RowK k = row_constants();
@@ -95,6 +125,66 @@ __global__ void __launch_bounds__(64) k_whisk_permute_mul(PermuteMulArgs a) {
   compress_words(w, acc.inf != 0u, c);
   uint32_t* d48 = a.post48 + 12ull * (((size_t)p * ell + i) * 2u + h);
   for (int t = 0; t < 12; ++t) d48[t] = c[t];
+}
+
+// ---- the seeded draws (the format: whisk_shuffle_host.h)
+struct DrawArgs {
+  cg1open::Seed32 seed;
+  uint32_t ell, n_provers, first_index;      // first_index + n_provers <= 2^32: a shuffle's global index fits a word
+  uint32_t* swaps;                           // [P][ell - 1]: j of the Fisher-Yates step i = ell - 1 - d, below i + 1
+  uint32_t* scalars;                         // cg1whisk_host::DrawColumns, 8 words per scalar, canonical
+};
+
+// One lane per (shuffle, draw); the sponge of a lane sits in LDS at blinder_from_seed's stride.  D = ell + 3 n + 13 is no multiple of 64:
+// the lanes of a wave belong to different shuffles and take either branch at the end.
+__global__ void __launch_bounds__(cg1merlin::LANES) k_whisk_draws(DrawArgs a) {
+  constexpr int L = cg1merlin::LANES;
+  __shared__ uint32_t sponge[50 * L];
+  const uint32_t D = cg1whisk_host::draw_count(a.ell);
+  const uint32_t t = blockIdx.x * (uint32_t)L + threadIdx.x;               // P D <= 4096 * 3085
+  if (t >= a.n_provers * D) return;
+  const uint32_t p = t / D, d = t - p * D;
+  uint8_t seedb[32], msg[64];
+  for (int k = 0; k < 32; ++k) seedb[k] = (uint8_t)(a.seed.w[k >> 2] >> (8 * (k & 3)));
+  cg1whisk_host::draw_message(seedb, a.first_index + p, d, msg);
+  uint32_t* w = sponge + threadIdx.x;
+  for (int k = 0; k < 50; ++k) w[k * L] = 0;
+  for (int k = 0; k < 16; ++k)
+    w[k * L] = (uint32_t)msg[4 * k] | ((uint32_t)msg[4 * k + 1] << 8) | ((uint32_t)msg[4 * k + 2] << 16) | ((uint32_t)msg[4 * k + 3] << 24);
+  w[33 * L] = 0x80000000u;                                                 // last pad bit: byte 135 of the rate
+  cg1merlin::keccak_words<false>(w);
+  uint32_t o[16];
+  for (int k = 0; k < 16; ++k) o[k] = w[k * L];
+  if (d + 1u < a.ell) {
+    const uint64_t lo = (uint64_t)o[0] | ((uint64_t)o[1] << 32), hi = (uint64_t)o[2] | ((uint64_t)o[3] << 32);
+    a.swaps[(size_t)p * (a.ell - 1u) + d] = cg1whisk_host::draw_mod_u128(lo, hi, a.ell - d);
+  } else {
+    uint32_t v[8];
+    cg1fr::fr_to_le32(cg1fr::fr_from_le64_wide(reinterpret_cast<const uint8_t*>(o)), reinterpret_cast<uint8_t*>(v));
+    uint32_t* dst = a.scalars + 8u * cg1whisk_host::draw_slot(a.ell, a.n_provers, p, d - (a.ell - 1u));
+    for (int k = 0; k < 8; ++k) dst[k] = v[k];
+  }
+}
+
+// perm = list(range(ell)); for d = 0 .. ell - 2: i = ell - 1 - d, swap perm[i], perm[swaps[d]].  One block per shuffle: the row and its
+// swaps come into LDS, ONE lane applies the swaps in order (each depends on the one before), all lanes write the row out.
+__global__ void __launch_bounds__(64) k_whisk_fisher_yates(const uint32_t* __restrict__ swaps, uint32_t ell, uint32_t* __restrict__ perm) {
+  __shared__ uint32_t pm[CG1_SAME_MSM_MAX_N], sw[CG1_SAME_MSM_MAX_N];
+  const uint32_t p = blockIdx.x;
+  if (ell > (uint32_t)CG1_SAME_MSM_MAX_N) return;          // (uniform; the host has refused it)
+  for (uint32_t i = threadIdx.x; i < ell; i += 64u) {
+    pm[i] = i;
+    if (i + 1u < ell) sw[i] = swaps[(size_t)p * (ell - 1u) + i];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0u)
+    for (uint32_t d = 0; d + 1u < ell; ++d) {
+      const uint32_t i = ell - 1u - d, j = sw[d] <= i ? sw[d] : i;         // k_whisk_draws reduces below i + 1; clamp all the same
+      const uint32_t x = pm[i];
+      pm[i] = pm[j]; pm[j] = x;
+    }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < ell; i += 64u) perm[(size_t)p * ell + i] = pm[i];
 }
 
 }  // namespace cg1whisk

@@ -878,4 +878,32 @@ int cg1_whisk_shuffle_front_emulate(size_t ell, const uint8_t* trackers96, const
   return CG1_OK;
 }
 
+// The host twin of cg1_whisk_shuffle_draws_device (capi_whisk_shuffle.h): the same format (whisk_shuffle_host.h) over the host Keccak, the
+// same refusals; no context, so a refusal carries no text.
+int cg1_whisk_shuffle_draws(size_t ell, size_t n_provers, const uint8_t* seed32, uint64_t first_index, uint32_t* out_perm, uint8_t* out_scalars32) {
+  if (!seed32 || !out_perm || !out_scalars32) return CG1_ERR_ARG;
+  if (const int rc = cg1whisk_host::check_draws(nullptr, 0, "cg1_whisk_shuffle_draws", ell, n_provers, first_index)) return rc;
+  const uint32_t L = (uint32_t)ell, P = (uint32_t)n_provers, D = cg1whisk_host::draw_count(L);
+  for (uint32_t p = 0; p < P; ++p) {
+    uint32_t* perm = out_perm + (size_t)p * L;
+    for (uint32_t i = 0; i < L; ++i) perm[i] = i;
+    for (uint32_t d = 0; d < D; ++d) {
+      alignas(8) uint8_t st[200] = {0};
+      cg1whisk_host::draw_message(seed32, (uint32_t)(first_index + p), d, st);
+      st[135] ^= 0x80;
+      cg1_keccak_f1600(st);
+      if (d + 1 < L) {
+        uint64_t lo, hi;
+        memcpy(&lo, st, 8); memcpy(&hi, st + 8, 8);
+        const uint32_t i = L - 1 - d, j = cg1whisk_host::draw_mod_u128(lo, hi, i + 1);
+        std::swap(perm[i], perm[j]);
+      } else {
+        cg1fr::fr_to_le32(cg1fr::fr_from_le64_wide(st), out_scalars32 + 32 * cg1whisk_host::draw_slot(L, P, p, d - (L - 1)));
+      }
+      memset(st, 0, sizeof st);
+    }
+  }
+  return CG1_OK;
+}
+
 }  // extern "C"

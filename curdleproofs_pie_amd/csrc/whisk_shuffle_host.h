@@ -1,5 +1,6 @@
 // The refusals cg1_whisk_shuffle_front (capi_whisk_shuffle.h, on the device) and cg1_whisk_shuffle_front_emulate (lazy_host.cpp, its host
-// twin for the CPU tests) share: one set of checks and one set of texts, so that the two cannot drift apart.  Host only.
+// twin for the CPU tests) share: one set of checks and one set of texts, so that the two cannot drift apart.  Host only, but for the few
+// functions marked CG1WHISK_HD: the format of the seeded draws, which the device kernels (kernels_whisk_shuffle.h) and the host twin share.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -53,6 +54,71 @@ inline int refuse_point(char* err, size_t err_len, const char* who, size_t prove
                    : "lies outside the prime-order subgroup G1 (k folds into the scalars only for points of order r)";
   snprintf(err, err_len, "%s: prover %zu: tracker %zu: %s %s", who, prover, index, half ? "k_r_G" : "r_G", what);
   return rc;
+}
+
+// ---- the seeded draws (cg1_whisk_shuffle_draws_device: k_whisk_draws, k_whisk_fisher_yates; cg1_whisk_shuffle_draws: lazy_host.cpp).
+// Draw d of shuffle `index` is SHAKE256("whisk_shuffle_draw" || seed32 || le64(index) || le32(d)).digest(64): 62 bytes in, one permutation.
+// d < ell - 1 are the Fisher-Yates swaps; scalar number s = d - (ell - 1) runs through k, vec_m_blinders (4), vec_a_blinders (2),
+// vec_c_blinders (4), ipa_r (n), ipa_z_head (n - 2), r_t r_u r_a r_b r_k, vec_r (n), and lands in the COLUMN layout the chain takes:
+// every column holds its P rows one after the other, the columns in that order.
+#if defined(__HIPCC__)
+#define CG1WHISK_HD __host__ __device__ inline
+#else
+#define CG1WHISK_HD inline
+#endif
+constexpr size_t DRAW_DOMAIN_LEN = 18;
+constexpr char DRAW_DOMAIN[] = "whisk_shuffle_draw";
+static_assert(sizeof DRAW_DOMAIN == DRAW_DOMAIN_LEN + 1, "");
+
+CG1WHISK_HD uint32_t draw_scalars(uint32_t ell) { return 3u * (ell + (uint32_t)N_BLINDERS) + 14u; }        // per shuffle
+CG1WHISK_HD uint32_t draw_count(uint32_t ell) { return ell - 1u + draw_scalars(ell); }                    // D = ell + 3 n + 13
+
+// where the columns begin, in scalars, for P provers: k | vec_m_blinders | vec_a_blinders | vec_c_blinders | ipa_r | ipa_z_head | blinders | vec_r
+struct DrawColumns { size_t k, mbl, abl, cbl, ipa_r, z_head, bl, vec_r, total; };
+inline DrawColumns draw_columns(size_t ell, size_t P) {
+  const size_t n = ell + N_BLINDERS;
+  DrawColumns c;
+  c.k = 0; c.mbl = P; c.abl = 5 * P; c.cbl = 7 * P; c.ipa_r = 11 * P; c.z_head = (11 + n) * P; c.bl = (9 + 2 * n) * P; c.vec_r = (14 + 2 * n) * P;
+  c.total = (14 + 3 * n) * P;
+  return c;
+}
+// the slot (in scalars) of scalar number s of prover p
+CG1WHISK_HD size_t draw_slot(uint32_t ell, uint32_t P, uint32_t p, uint32_t s) {
+  const size_t n = ell + (uint32_t)N_BLINDERS, Pz = P, pz = p;
+  if (s < 1u) return pz;
+  if (s < 5u) return Pz + 4 * pz + (s - 1u);
+  if (s < 7u) return 5 * Pz + 2 * pz + (s - 5u);
+  if (s < 11u) return 7 * Pz + 4 * pz + (s - 7u);
+  if (s < 11u + n) return 11 * Pz + n * pz + (s - 11u);
+  if (s < 9u + 2 * n) return (11 + n) * Pz + (n - 2) * pz + (s - 11u - n);
+  if (s < 14u + 2 * n) return (9 + 2 * n) * Pz + 5 * pz + (s - 9u - 2 * n);
+  return (14 + 2 * n) * Pz + n * pz + (s - 14u - 2 * n);
+}
+// (hi 2^64 + lo) mod m for 2 <= m <= 2^16: the swap index of a Fisher-Yates step from the first 16 bytes of its block
+CG1WHISK_HD uint32_t draw_mod_u128(uint64_t lo, uint64_t hi, uint32_t m) {
+  const uint64_t two64 = (~(uint64_t)0 % m + 1u) % m;
+  return (uint32_t)(((hi % m) * two64 + lo % m) % m);
+}
+// the 64 message bytes of a draw's one rate block (the SHAKE domain byte included; the last pad bit, byte 135, is the caller's)
+CG1WHISK_HD void draw_message(const uint8_t* seed32, uint32_t index, uint32_t d, uint8_t msg[64]) {
+  for (int i = 0; i < 64; ++i) msg[i] = 0;
+  for (size_t i = 0; i < DRAW_DOMAIN_LEN; ++i) msg[i] = (uint8_t)DRAW_DOMAIN[i];
+  for (int i = 0; i < 32; ++i) msg[18 + i] = seed32[i];
+  for (int i = 0; i < 4; ++i) { msg[50 + i] = (uint8_t)(index >> (8 * i)); msg[58 + i] = (uint8_t)(d >> (8 * i)); }      // le64(index), index < 2^32
+  msg[62] = 0x1Fu;
+}
+
+// the refusals both draw entries share, after their pointer checks; nothing has been written when one is made.  The text (err: nullable)
+// never holds the seed.
+inline int check_draws(char* err, size_t err_len, const char* who, size_t ell, size_t P, uint64_t first_index) {
+  if (!shape_ok(ell)) { if (err) snprintf(err, err_len, "%s: ell + %zu must be a power of two in 8 .. %d", who, N_BLINDERS, CG1_SAME_MSM_MAX_N); return CG1_ERR_ARG; }
+  if (P > CG1_WHISK_SHUFFLE_DRAWS_MAX_PROVERS) {
+    if (err) snprintf(err, err_len, "%s: more than %d shuffles in one call", who, CG1_WHISK_SHUFFLE_DRAWS_MAX_PROVERS);
+    return CG1_ERR_ARG; }
+  if (first_index > ((uint64_t)1 << 32) || first_index + P > ((uint64_t)1 << 32)) {
+    if (err) snprintf(err, err_len, "%s: first_index + n_provers exceeds 2^32: a shuffle's index is below 2^32", who);
+    return CG1_ERR_ARG; }
+  return CG1_OK;
 }
 
 // M's scalar row: perm[i] as a 32-byte little-endian scalar, then the four blinders

@@ -13,10 +13,21 @@ bytes and M || proof out, no G1Point object on the way.
 One difference from the reference: a tracker point outside the prime-order subgroup G1 is refused (NativeError).  The reference decodes
 trackers unchecked (util.py:35-36) and would go on; the device prover folds k into the scalars of its same-scalar block, which is exact
 only for points of order r, so the call certifies every tracker point first.
+
+generate() draws from Python's `random`, as the reference does: that is what the byte-for-byte tests need, and nothing to prove with.
+To prove, use the seeded face: tracker bytes and a 32-byte seed in, every draw made on the device (cg1_whisk_shuffle_prove_seeded), a
+status per shuffle out -- one malformed tracker costs its own list its proof and no other.
+
+    post96, proofs, status = prover.generate_packed(trackers96)          # flat bytes; the seed: 32 fresh bytes from the OS, kept nowhere
+    out = prover.generate_seeded(lists)                                   # [(post_trackers, proof) or None, ...]
+
+shuffle_draws_from_seed is the definition of what a seed draws.
 """
 from __future__ import annotations
 
+import hashlib
 import random
+import secrets
 from typing import List, Optional, Sequence, Tuple
 
 from . import _native as N
@@ -24,6 +35,36 @@ from .opening_prover import _scalar32, _tracker_bytes
 from .shuffle_verifier import FR_MODULUS
 
 N_BLINDERS = 4                                                          # curdleproofs.py:24
+DRAW_DOMAIN = b"whisk_shuffle_draw"
+REJECT_NAMES = {0: "proved", N.WHISK_SHUFFLE_NO_DECODE: "a tracker point does not decode", N.WHISK_SHUFFLE_NOT_G1: "a tracker point outside G1"}
+HALF_NAMES = ("r_G", "k_r_G")
+
+
+def shuffle_draws_from_seed(seed: bytes, index: int, ell: int) -> tuple:
+    """What shuffle number `index` of `seed` draws -> (permutation, k, vec_m_blinders, draws), the last four fields of a prove_many item:
+    prove_many([(pre, *shuffle_draws_from_seed(seed, i, ell))]) is the definition of item i of generate_packed(.., seed).  Draw number d is
+    block(d) = SHAKE256(b"whisk_shuffle_draw" || seed || le64(index) || le32(d)).digest(64); d = 0 .. ell - 2 are the Fisher-Yates steps
+    i = ell - 1 - d, j = le128(block[:16]) mod (i + 1), swap perm[i], perm[j]; then one draw each for k, vec_m_blinders (4), vec_a_blinders (2),
+    vec_c_blinders (4), ipa_r (n), ipa_z_head (n - 2), r_t, r_u, r_a, r_b, r_k and vec_r (n), n = ell + 4: le512(block) mod r, as 32-byte
+    strings."""
+    if len(seed) != 32:
+        raise ValueError("seed: 32 bytes")
+    if not 0 <= index < 1 << 32:
+        raise ValueError("index: 0 .. 2^32 - 1")
+    n = ell + N_BLINDERS
+    head = DRAW_DOMAIN + bytes(seed) + index.to_bytes(8, "little")
+    block = lambda d: hashlib.shake_256(head + d.to_bytes(4, "little")).digest(64)
+    perm = list(range(ell))
+    for d in range(ell - 1):
+        i = ell - 1 - d
+        j = int.from_bytes(block(d)[:16], "little") % (i + 1)
+        perm[i], perm[j] = perm[j], perm[i]
+    count = iter(range(ell - 1, ell + 3 * n + 13))
+    take = lambda m: [(int.from_bytes(block(next(count)), "little") % FR_MODULUS).to_bytes(32, "little") for _ in range(m)]
+    k, mbl = take(1)[0], take(N_BLINDERS)
+    abl, cbl, ipa_r, z_head = take(N_BLINDERS - 2), take(N_BLINDERS), take(n), take(n - 2)
+    r_t, r_u, r_a, r_b, r_k = take(5)
+    return perm, k, mbl, (abl, cbl, ipa_r, z_head, r_t, r_u, r_a, r_b, r_k, take(n))
 
 
 def _draw_scalars(randint, m: int) -> List[bytes]:
@@ -59,6 +100,8 @@ class ShuffleBatchProver:
                 list(crs.vec_G) + list(crs.vec_H) + [crs.H, crs.G_t, crs.G_u])
         self.table = table
         self._fixed = None                                   # the table indices and G_t | G_u | H, looked up at the first call
+        self.last_status: List[int] = []                     # of the last seeded call, per shuffle: a key of REJECT_NAMES
+        self.last_refusals: List[Optional[Tuple[int, str]]] = []        # ... and (tracker index, "r_G" | "k_r_G") where the status is not 0
 
     def close(self) -> None:
         if self._owns and self.table is not None:
@@ -144,6 +187,70 @@ class ShuffleBatchProver:
                 for p in range(P):
                     rec = post[96 * ell * p: 96 * ell * (p + 1)]
                     out.append(([(rec[96 * i: 96 * i + 48], rec[96 * i + 48: 96 * i + 96]) for i in range(ell)], proofs[wb * p: wb * (p + 1)]))
+        return out
+
+    def generate_packed(self, trackers96: bytes, seed: Optional[bytes] = None, first_index: int = 0) -> Tuple[bytes, bytes, List[int]]:
+        """Shuffles proved from tracker bytes and a seed, flat buffers in and out, every draw made on the device.  trackers96: ell records
+        r_G48 | k_r_G48 per shuffle.  -> (post96: ell records T48 | U48 per shuffle; proofs: cg1_whisk_shuffle_proof_bytes(ell) bytes M || proof
+        per shuffle; status per shuffle, REJECT_NAMES).  Shuffle p draws what shuffle_draws_from_seed(seed, first_index + p, ell) gives, so its
+        output depends on neither its neighbours nor on how the batch is cut into native calls.  A refused shuffle (status != 0: one of its
+        tracker points does not decode or lies outside G1; `last_refusals` names the first) gets zero bytes in both outputs and leaves the
+        others alone.  seed=None draws 32 fresh bytes from the OS and keeps them nowhere.  A seed that is reused, or known to anyone but the
+        prover, reveals every k and permutation it proved: pass one only in tests.  Never touches `random`.
+        ValueError: a length, before anything runs.  NativeError: a refusal of the whole native call; nothing has been produced then."""
+        ell = self.ell
+        trackers96 = bytes(trackers96)
+        if len(trackers96) % (96 * ell):
+            raise ValueError(f"trackers96: a multiple of 96 * ell = {96 * ell} bytes")
+        count = len(trackers96) // (96 * ell)
+        if seed is None:
+            seed = secrets.token_bytes(32)
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        if isinstance(first_index, bool) or not isinstance(first_index, int) or first_index < 0 or first_index + count > 1 << 32:
+            raise ValueError("first_index: an int with first_index + the number of shuffles <= 2^32")
+        self.last_status, self.last_refusals = [], []
+        if not count:
+            return b"", b"", []
+        if self.table is None:
+            raise N.NativeError("the prover is closed")
+        step = min(N.SAME_MSM_MAX_PROVERS, N.LIGHT_MAX_BASES // (2 * (ell + N_BLINDERS)))
+        posts, proofs, status, refusals = [], [], [], []
+        table = self.table
+        with table._ctx_lock():
+            if table._KIND != "fixed-base":
+                raise TypeError("the device pipeline of a shuffle proof runs over a FixedBaseTable")
+            gi, hi, ui, gti, gui, gth = self._crs_args()
+            for lo in range(0, count, step):
+                P = min(step, count - lo)
+                post, out, st, at = table._ctx.whisk_shuffle_prove_seeded(table._tab, ell, P, gi * P, hi * P, [ui] * P, [gti] * P, [gui] * P, gth,
+                                                                          trackers96[96 * ell * lo: 96 * ell * (lo + P)], seed, first_index + lo)
+                posts.append(post); proofs.append(out); status += st
+                refusals += [(a >> 1, HALF_NAMES[a & 1]) if s else None for s, a in zip(st, at)]
+        self.last_status, self.last_refusals = status, refusals
+        return b"".join(posts), b"".join(proofs), list(status)
+
+    def generate_seeded(self, pre_tracker_lists: Sequence, seed: Optional[bytes] = None, first_index: int = 0) -> List[Optional[Tuple[List[Tuple[bytes, bytes]], bytes]]]:
+        """generate_packed over lists of ell WhiskTracker-like objects (r_G, k_r_G) or byte pairs: -> per list (post_trackers, proof) as
+        prove_many returns them, or None where the list was refused (`last_status`, `last_refusals`).  No input is mutated."""
+        ell = self.ell
+        recs = []
+        for pre in pre_tracker_lists:
+            pre = list(pre)
+            if len(pre) != ell:
+                raise ValueError(f"pre_trackers has ell = {ell} entries")
+            for t in pre:
+                r, kr = _tracker_bytes(t)
+                if len(r) != 48 or len(kr) != 48:
+                    raise ValueError("a tracker is two 48-byte encodings (r_G, k_r_G)")
+                recs.append(r + kr)
+        post, proofs, status = self.generate_packed(b"".join(recs), seed, first_index)
+        wb = len(proofs) // max(1, len(status))
+        out = []
+        for p, st in enumerate(status):
+            rec = post[96 * ell * p: 96 * ell * (p + 1)]
+            out.append(None if st else ([(rec[96 * i: 96 * i + 48], rec[96 * i + 48: 96 * i + 96]) for i in range(ell)], proofs[wb * p: wb * (p + 1)]))
         return out
 
     def generate(self, pre_tracker_lists: Sequence, rng: Optional[random.Random] = None) -> List[Tuple[List[Tuple[bytes, bytes]], bytes]]:

@@ -942,6 +942,37 @@ int cg1_whisk_shuffle_front_emulate(size_t ell, const uint8_t* trackers96, const
                                     const uint8_t* gh_affine96 /* nullable */, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96, uint8_t* out_post96,
                                     uint8_t* out_m_scalars32, uint8_t* out_m48 /* with gh_affine96 */, char* out_err256 /* nullable */);
 
+/* ---- Whisk shuffles proved from a SEED: the permutation, k and all 3 n + 14 blinders of every shuffle (n = ell + 4) are drawn on the
+ * device.  For shuffle number index (global: first_index + position in the call, below 2^32) and draw number d,
+ *   block(index, d) = SHAKE256("whisk_shuffle_draw" || seed32 || le64(index) || le32(d)).digest(64)      (62 bytes in: one permutation)
+ *   d = 0 .. ell - 2        Fisher-Yates on perm = 0 .. ell - 1, in order of d: i = ell - 1 - d, j = le128(block[:16]) mod (i + 1), swap perm[i], perm[j]
+ *   then, one draw each     k, vec_m_blinders (4), vec_a_blinders (2), vec_c_blinders (4), ipa_r (n), ipa_z_head (n - 2), r_t r_u r_a r_b r_k,
+ *                           vec_r (n): le512(block) mod r.  A zero is not special-cased: the chain refuses what it refuses.
+ * so a shuffle's output depends on (seed, index) alone, not on its neighbours or on how a batch is cut into calls.  A seed that is reused,
+ * or known to anyone but the prover, reveals every k and permutation it proved.
+ * cg1_whisk_shuffle_draws_device   k_whisk_draws + k_whisk_fisher_yates (csrc/kernels_whisk_shuffle.h) alone.  out_perm: n_provers x ell;
+ *   out_scalars32: (3 n + 14) n_provers scalars in the COLUMN layout cg1_whisk_shuffle_prove_device takes -- k | vec_m_blinders |
+ *   vec_a_blinders | vec_c_blinders | ipa_r | ipa_z_head | r_t .. r_k | vec_r, every column its n_provers rows one after the other.
+ *   CG1_ERR_ARG, nothing written: a null pointer, ell + 4 not a power of two in 8 .. CG1_SAME_MSM_MAX_N, n_provers above
+ *   CG1_WHISK_SHUFFLE_DRAWS_MAX_PROVERS, first_index + n_provers > 2^32.  The device buffer of the draws is zeroed before the call returns.
+ * cg1_whisk_shuffle_draws          the host twin over the host Keccak: same format, same refusals (without a text: it has no context).
+ * cg1_whisk_shuffle_prove_seeded   (1) those draws on the context's stream and one copy of them down; (2) cg1_whisk_shuffle_front with a
+ *   status PER PROVER: out_status[p] = 0, CG1_WHISK_SHUFFLE_NO_DECODE or CG1_WHISK_SHUFFLE_NOT_G1, out_bad_at[p] = tracker 2 + half (0 = r_G,
+ *   1 = k_r_G) of the prover's first such point -- points the decoder refuses before points outside G1, each in tracker order; (3) the
+ *   provers with status 0 through cg1_shuffle_prove_device (all refused: CG1_OK without it).  A refused prover gets zero bytes in
+ *   out_post96 and out_proofs and leaves the others as they would be without it.  Every other refusal is the whole call's, as
+ *   cg1_whisk_shuffle_prove_device makes it, and leaves all four outputs untouched; a text of the chain counts the provers that reached it.
+ *   Before returning, the device buffer of the draws and the table's staging block (both copies) are zeroed and the host staging of the
+ *   draws is wiped; neither the seed nor a draw appears in an error text. */
+#define CG1_WHISK_SHUFFLE_DRAWS_MAX_PROVERS 4096
+#define CG1_WHISK_SHUFFLE_NO_DECODE 2   /* a tracker point is not a compressed encoding of a curve point */
+#define CG1_WHISK_SHUFFLE_NOT_G1    3   /* a tracker point lies outside the prime-order subgroup */
+int cg1_whisk_shuffle_draws_device(cg1_ctx* ctx, size_t ell, size_t n_provers, const uint8_t* seed32, uint64_t first_index, uint32_t* out_perm, uint8_t* out_scalars32);
+int cg1_whisk_shuffle_draws(size_t ell, size_t n_provers, const uint8_t* seed32, uint64_t first_index, uint32_t* out_perm, uint8_t* out_scalars32);
+int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
+                                   const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* trackers96, const uint8_t* seed32,
+                                   uint64_t first_index, uint8_t* out_post96, uint8_t* out_proofs, int32_t* out_status /* n_provers */, uint32_t* out_bad_at /* n_provers */);
+
 /* The tracker scan: which trackers does a set of Whisk secrets open?  For n_trackers trackers (r_G48 | k_r_G48, cg1_opening_prove's layout)
  * and n_ks secrets (scalar32), bit (i, j) = [ k_j * point_projective_from_bytes(r_G_i) == point_projective_from_bytes(k_r_G_i) ]
  * (util.py:35-36: unchecked decoding, a point outside G1 is legal and multiplied exactly; the relation opening.py proves).
