@@ -258,6 +258,14 @@ cg1_generator_mul_device = _proto("cg1_generator_mul_device", c_int, c_void_p, c
 cg1_tracker_match_device = _proto("cg1_tracker_match_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_tracker_match = _proto("cg1_tracker_match", c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_tracker_match_last_ms = _proto("cg1_tracker_match_last_ms", c_int, c_void_p, c_void_p)
+# exact relations in bulk (csrc/kernels_exact.h): sum of (+-) k P == identity on all of E(Fp); index check, host twin, device launch, and
+# the opening proofs' challenges on the worker pool
+cg1_exact_relations_check = _proto("cg1_exact_relations_check", c_int, c_void_p, c_size_t, c_size_t, c_size_t)
+cg1_exact_relations = _proto("cg1_exact_relations", c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int)
+cg1_exact_relations_device = _proto("cg1_exact_relations_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p)
+cg1_exact_gather_device = _proto("cg1_exact_gather_device", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t)
+cg1_opening_challenges = _proto("cg1_opening_challenges", c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int)
+EXACT_TERMS, EXACT_NEG, EXACT_ONE, EXACT_NONE = 4, 0x80000000, 0x7FFFFFFF, 0xFFFFFFFF      # CG1_EXACT_* of include/curdle_g1.h
 # resident tables of fixed bases (csrc/kernels_fixed.h)
 cg1_fixed_create = _proto("cg1_fixed_create", c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_int))
 cg1_fixed_destroy = _proto("cg1_fixed_destroy", None, c_void_p)
@@ -363,6 +371,7 @@ EXPORTED_SYMBOLS = [
     "cg1_whisk_shuffle_proof_bytes", "cg1_whisk_shuffle_front", "cg1_whisk_shuffle_prove_device", "cg1_whisk_shuffle_front_emulate",
     "cg1_whisk_shuffle_draws_device", "cg1_whisk_shuffle_draws", "cg1_whisk_shuffle_prove_seeded",
     "cg1_tracker_match_device", "cg1_tracker_match", "cg1_tracker_match_last_ms",
+    "cg1_exact_relations_check", "cg1_exact_relations", "cg1_exact_relations_device", "cg1_exact_gather_device", "cg1_opening_challenges",
 ]
 
 

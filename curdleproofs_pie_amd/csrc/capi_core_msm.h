@@ -186,6 +186,7 @@ void cg1_ctx_destroy(cg1_ctx* ctx) {
   cg1::release_bufs(ctx->cap_prover, {cg1::dev_buf(ctx->d_prover)});
   cg1::release_bufs(ctx->cap_whisk_draws, {cg1::dev_buf(ctx->d_whisk_draws)});
   cg1::release_bufs(ctx->cap_tscan_tab, {cg1::dev_buf(ctx->d_tscan_tab)});
+  for (int i = 0; i < 2; ++i) cg1::release_bufs(ctx->cap_exact[i], {cg1::host_buf(ctx->h_exact[i]), cg1::dev_buf(ctx->d_exact[i])});
   cg1::release_bufs(ctx->cap_small_partial, {cg1::dev_buf(ctx->d_small_partial)});
   cg1::release_bufs(ctx->cap_small_pts, {cg1::dev_buf(ctx->d_small_pts), cg1::dev_buf(ctx->d_small_flags)});
   cg1::release_bufs(ctx->cap_stage_pts, {cg1::dev_buf(ctx->d_stage_pts)});
@@ -199,6 +200,7 @@ void cg1_ctx_destroy(cg1_ctx* ctx) {
   for (int i = 0; i < 2; ++i) if (ctx->tm_ev[i]) (void)hipEventDestroy(ctx->tm_ev[i]);
   if (ctx->copy_stream.load()) (void)hipStreamDestroy(ctx->copy_stream.load());
   if (ctx->side_ev) (void)hipEventDestroy(ctx->side_ev);
+  for (int i = 0; i < 2; ++i) if (ctx->exact_ev[i]) (void)hipEventDestroy(ctx->exact_ev[i]);
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
   delete ctx;
 }

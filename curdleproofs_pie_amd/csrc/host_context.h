@@ -121,6 +121,10 @@ struct Ctx {
   int decompress_waves = 3;             // "decompress_waves": waves per SIMD k_batch_decompress<false> is compiled for (2: table in registers, 3: half of it in scratch)
   void* d_opening = nullptr; size_t cap_opening = 0;              // cg1_opening_prepare_device's scratch (940 B per proof)
   void* d_tscan_tab = nullptr; size_t cap_tscan_tab = 0;          // cg1_tracker_match_device's tile of light-table records (public points only)
+  // cg1_exact_relations_device's term records and cg1_exact_gather_device's indices: two page-locked staging blocks with their device copies,
+  // used in turn, each with the event recorded behind its last upload (a call waits only for the upload made two calls before it)
+  uint8_t *h_exact[2] = {nullptr, nullptr}, *d_exact[2] = {nullptr, nullptr}; size_t cap_exact[2] = {0, 0};
+  hipEvent_t exact_ev[2] = {nullptr, nullptr}; int exact_turn = 0;
   int tscan_ladder_max_ks = CG1_TRACKER_MATCH_LADDER_MAX_KS;      // "tracker_scan_ladder_max_ks": up to this many secrets a scan runs one ladder per pair (0: always the tables)
   int tscan_timing = 0; float tscan_ms[2] = {0.f, 0.f};           // "tracker_scan_timing": wait between the phases of a scan and keep build / match wall ms
   void* d_prover = nullptr; size_t cap_prover = 0;                // cg1_opening_prove_device's scratch (1 252 B per proof)

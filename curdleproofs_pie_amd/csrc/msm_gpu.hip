@@ -68,6 +68,7 @@ int pick_window(size_t n);
 #include "light_digits.h"
 #include "kernels_light.h"
 #include "kernels_tracker_scan.h"
+#include "kernels_exact.h"         // k_exact_relations: signed sums of at most four k P == identity, exact on all of E(Fp), a wave per relation
 }  // namespace cg1
 #include "kernels_rows.h"
 #include "kernels_merlin.h"
@@ -100,4 +101,5 @@ int pick_window(size_t n);
 #include "capi_same_scalar.h"      // the same-scalar block proved on the device: cg1_same_scalar_prove_device
 #include "capi_shuffle.h"          // a whole shuffle proof proved on the device: cg1_shuffle_prove_device
 #include "capi_whisk_shuffle.h"    // GenerateWhiskShuffleProof from tracker bytes: cg1_whisk_shuffle_front, cg1_whisk_shuffle_prove_device
+#include "capi_exact.h"           // exact relations in bulk: cg1_exact_relations_device (host twin: csrc/shuffle_verify.cpp)
 #include "capi_tracker_scan.h"    // which trackers a set of secrets opens: cg1_tracker_match_device and its host twin cg1_tracker_match

@@ -1165,6 +1165,95 @@ int cg1_opening_weights_from_seed(const uint8_t seed32[32], size_t first, size_t
   return CG1_OK;
 }
 
+// One exact relation on the host: sum of (+-) k P over its terms == identity, with the scalars as 256-bit integers (jac_mul does not
+// reduce) and complete additions -- the one copy of this arithmetic: cg1_shuffle_exact_same_scalar, cg1_opening_exact_status and the
+// flat-array entry cg1_exact_relations (the twin of the device's k_exact_relations) all come here.
+extern "C++" {
+namespace {
+struct ExactOperand { const jac* P; const uint8_t* k32 /* nullptr: the scalar one */; bool neg; };
+bool exact_sum_is_identity(const ExactOperand* terms, size_t n) {
+  jac acc = cg1h::jac_identity();
+  for (size_t j = 0; j < n; ++j) {
+    const ExactOperand& t = terms[j];
+    const jac v = t.k32 ? cg1h::jac_mul(*t.P, t.k32) : *t.P;
+    acc = cg1h::jac_add(acc, t.neg ? cg1h::jac_neg(v) : v);
+  }
+  return cg1h::jac_is_identity(acc);
+}
+bool exact_sum_is_identity(std::initializer_list<ExactOperand> terms) { return exact_sum_is_identity(terms.begin(), terms.size()); }
+
+// the challenge of an opening proof (opening.py:60-70): the transcript over the encodings as they came, infinities canonical
+void opening_challenge(const uint8_t* tracker96, const uint8_t* k_commitment48, const uint8_t* proof128, uint8_t c32[32]) {
+  const uint8_t *rG = tracker96, *krG = tracker96 + 48, *kG = k_commitment48, *A = proof128, *B = proof128 + 48;
+  uint8_t G48[48], own[5 * 48];
+  cg1h::g1_compress(cg1h::jac_generator(), G48);
+  memcpy(own, kG, 48); memcpy(own + 48, krG, 48); memcpy(own + 96, rG, 48); memcpy(own + 144, A, 48); memcpy(own + 192, B, 48);
+  canonicalize_infinities(own, 5);
+  Transcript tr("whisk_opening_proof");
+  const uint8_t* order[6] = {own, G48, own + 48, own + 96, own + 144, own + 192};
+  for (const uint8_t* p : order) tr.point("tracker_opening_proof", p);
+  fr_to_le32(tr.challenge("tracker_opening_proof_challenge"), c32);
+}
+
+// items 0 .. n-1 over the worker pool (n_threads <= 0: the whole pool and the caller)
+void exact_spread(size_t n, int n_threads, const std::function<void(size_t)>& one) {
+  std::atomic<size_t> next{0};
+  std::function<void()> work = [&]() { for (;;) { const size_t i = next.fetch_add(1); if (i >= n) return; one(i); } };
+  Pool& pool = Pool::get();
+  size_t nt = n_threads > 0 ? (size_t)n_threads : pool.size() + 1;
+  nt = std::min(nt, n);
+  if (nt <= 1) work(); else pool.run(work, nt);
+}
+}  // namespace
+}  // extern "C++"
+
+int cg1_exact_relations_check(const uint32_t* terms, size_t n_relations, size_t n_points, size_t n_scalars) {
+  if ((n_relations && !terms) || n_points >= CG1_EXACT_NONE || n_scalars >= CG1_EXACT_ONE || n_relations > 0xffffffffull / CG1_EXACT_TERMS) return CG1_ERR_ARG;
+  for (size_t t = 0; t < n_relations * CG1_EXACT_TERMS; ++t) {
+    const uint32_t p = terms[2 * t], k = terms[2 * t + 1] & ~CG1_EXACT_NEG;
+    if (p == CG1_EXACT_NONE) continue;
+    if (p >= n_points || (k != CG1_EXACT_ONE && k >= n_scalars)) return CG1_ERR_ARG;
+  }
+  return CG1_OK;
+}
+
+int cg1_exact_relations(const uint8_t* points96, size_t n_points, const uint8_t* scalars32, size_t n_scalars, const uint32_t* terms,
+                        size_t n_relations, uint8_t* ok, int n_threads) {
+  if ((n_points && !points96) || (n_scalars && !scalars32) || (n_relations && !ok)) return CG1_ERR_ARG;
+  if (const int rc = cg1_exact_relations_check(terms, n_relations, n_points, n_scalars)) return rc;
+  // decode every point once (a relation names a point by index, and relations share points)
+  std::vector<jac> P(n_points);
+  std::atomic<int> bad{0};
+  exact_spread(n_points, n_threads, [&](size_t i) {
+    const uint8_t* b = points96 + 96 * i;
+    bool any = false;
+    for (int t = 0; t < 96; ++t) any = any || b[t];
+    cg1h::fe x, y;
+    if (!any) P[i] = cg1h::jac_identity();
+    else if (!cg1h::fe_from_le48(b, x) || !cg1h::fe_from_le48(b + 48, y)) bad.store(1);
+    else P[i] = cg1h::jac_from_affine(x, y);
+  });
+  if (bad.load()) return CG1_ERR_ENCODING;
+  exact_spread(n_relations, n_threads, [&](size_t i) {
+    ExactOperand ops[CG1_EXACT_TERMS];
+    size_t cnt = 0;
+    for (size_t j = 0; j < CG1_EXACT_TERMS; ++j) {
+      const uint32_t p = terms[2 * (i * CG1_EXACT_TERMS + j)], k = terms[2 * (i * CG1_EXACT_TERMS + j) + 1], ki = k & ~CG1_EXACT_NEG;
+      if (p == CG1_EXACT_NONE) continue;
+      ops[cnt++] = ExactOperand{&P[p], ki == CG1_EXACT_ONE ? nullptr : scalars32 + 32 * (size_t)ki, (k & CG1_EXACT_NEG) != 0};
+    }
+    ok[i] = exact_sum_is_identity(ops, cnt) ? 1 : 0;
+  });
+  return CG1_OK;
+}
+
+int cg1_opening_challenges(const uint8_t* trackers96, const uint8_t* k_commitments48, const uint8_t* proofs128, size_t n, uint8_t* out_c32,
+                           int n_threads) {
+  if (n && (!trackers96 || !k_commitments48 || !proofs128 || !out_c32)) return CG1_ERR_ARG;
+  exact_spread(n, n_threads, [&](size_t i) { opening_challenge(trackers96 + 96 * i, k_commitments48 + 48 * i, proofs128 + 128 * i, out_c32 + 32 * i); });
+  return CG1_OK;
+}
+
 // The equalities the reference asserts directly, evaluated EXACTLY (no random weights) with host group arithmetic, for
 // proofs that carry a point outside G1: random weights are only sound inside the prime-order subgroup (E(Fp) has points of
 // order 3, 11, ...), and the reference's own verdict on such a proof is the exact one.
@@ -1191,12 +1280,11 @@ int cg1_shuffle_exact_same_scalar(const cg1_shuffle_crs* crs_, const uint8_t* in
     return CG1_OK;
   uint8_t a32[32], zk32[32], zt32[32], zu32[32];
   fr_to_le32(alpha, a32); fr_to_le32(z_k, zk32); fr_to_le32(z_t, zt32); fr_to_le32(z_u, zu32);
-  using cg1h::jac_add; using cg1h::jac_mul; using cg1h::jac_eq;
   // GroupCommitment.new(G, H, T, r) = (G r, T + H r)  (commitment.py:22-30); expected == cm + cm' alpha (same_scalar.py:101-108)
-  const bool e1 = jac_eq(jac_mul(Gt, zt32), jac_add(A1, jac_mul(T1, a32)));
-  const bool e2 = jac_eq(jac_add(jac_mul(R, zk32), jac_mul(H, zt32)), jac_add(A2, jac_mul(T2, a32)));
-  const bool e3 = jac_eq(jac_mul(Gu, zu32), jac_add(B1, jac_mul(U1, a32)));
-  const bool e4 = jac_eq(jac_add(jac_mul(S, zk32), jac_mul(H, zu32)), jac_add(B2, jac_mul(U2, a32)));
+  const bool e1 = exact_sum_is_identity({{&Gt, zt32, false}, {&A1, nullptr, true}, {&T1, a32, true}});
+  const bool e2 = exact_sum_is_identity({{&R, zk32, false}, {&H, zt32, false}, {&A2, nullptr, true}, {&T2, a32, true}});
+  const bool e3 = exact_sum_is_identity({{&Gu, zu32, false}, {&B1, nullptr, true}, {&U1, a32, true}});
+  const bool e4 = exact_sum_is_identity({{&S, zk32, false}, {&H, zu32, false}, {&B2, nullptr, true}, {&U2, a32, true}});
   *ok = (e1 && e2 && e3 && e4) ? 1 : 0;
   return CG1_OK;
 }
@@ -1225,19 +1313,12 @@ int cg1_opening_exact_status(const uint8_t* tracker96, const uint8_t* k_commitme
     *status = CG1_SHUFFLE_BAD_POINT;
     return CG1_OK;
   }
-  uint8_t G48[48], own[5 * 48];
-  cg1h::g1_compress(cg1h::jac_generator(), G48);
-  memcpy(own, kG, 48); memcpy(own + 48, krG, 48); memcpy(own + 96, rG, 48); memcpy(own + 144, A, 48); memcpy(own + 192, B, 48);
-  canonicalize_infinities(own, 5);
-  Transcript tr("whisk_opening_proof");
-  const uint8_t* order[6] = {own, G48, own + 48, own + 96, own + 144, own + 192};
-  for (const uint8_t* p : order) tr.point("tracker_opening_proof", p);
-  const fr c = tr.challenge("tracker_opening_proof_challenge");
   uint8_t c32[32], s32[32];
-  fr_to_le32(c, c32); fr_to_le32(s_, s32);
-  using cg1h::jac_add; using cg1h::jac_mul; using cg1h::jac_eq;
-  const bool e1 = jac_eq(jac_add(jac_mul(cg1h::jac_generator(), s32), jac_mul(jkG, c32)), jA);      // opening.py:73
-  const bool e2 = jac_eq(jac_add(jac_mul(jrG, s32), jac_mul(jkrG, c32)), jB);                       // opening.py:74
+  opening_challenge(tracker96, k_commitment48, proof128, c32);
+  fr_to_le32(s_, s32);
+  const jac jG = cg1h::jac_generator();
+  const bool e1 = exact_sum_is_identity({{&jG, s32, false}, {&jkG, c32, false}, {&jA, nullptr, true}});       // opening.py:73
+  const bool e2 = exact_sum_is_identity({{&jrG, s32, false}, {&jkrG, c32, false}, {&jB, nullptr, true}});     // opening.py:74
   *ok = (e1 && e2) ? 1 : 0;
   *status = *ok ? 0 : 6;
   return CG1_OK;

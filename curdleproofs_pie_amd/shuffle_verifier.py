@@ -161,10 +161,20 @@ class Prepared:
 class ShuffleBatchVerifier:
     SPLIT = 2048                            # verify_packed cuts calls of more than 2 * SPLIT proofs into pieces of this many
     FE_FIRST_MAX = 8                        # host front-end: batches up to this size run it BESIDE the GPU's decoding (it decodes its own four points)
+    EXACT_DEVICE_MIN = 1                    # (exact_device=None) flagged live proofs of a batch from which they are decided in one device pass
+                                            # (_decide_flagged_device).  profiles/r19_exact_device_timing.txt, 1 024 proofs at ell = 124: the pass never
+                                            # loses -- 1 flagged 30.3 ms against 30.7 one by one (spread 0.3), 4: 30.8 against 36.9, 64: 34.4 against 156,
+                                            # all 1 024: 39.7 ms against 2.07 s
 
     def __init__(self, crs, ctx: Optional["N.Context"] = None, threads: int = 0, chunk: int = 256, device_rows: bool = True,
                  blocking_sync: Optional[bool] = None, device_front_end: Optional[bool] = None, fe_lanes: Optional[int] = None, fe_cus: int = 0, fe_prio: int = 0,
-                 pipelines: Optional[int] = None, max_pinned_bytes: Optional[int] = None, coalesce: Optional[int] = None):
+                 pipelines: Optional[int] = None, max_pinned_bytes: Optional[int] = None, coalesce: Optional[int] = None,
+                 exact_device: Optional[bool] = None):
+        # exact_device: how the live proofs that carry a point outside G1 in the same-scalar equalities are decided.  False: one by one
+        # (_decide_flagged: the path there always was); True: all of a batch in one device pass (_decide_flagged_device) from one such proof
+        # on; None: the device pass from EXACT_DEVICE_MIN on.  The device pass reads the row-input blocks on the device, so with
+        # device_rows=False every setting takes the per-proof path.
+        self.exact_device = exact_device
         # max_pinned_bytes: budget for the page-locked staging of the batch slots of ONE pipeline (None = no limit).  A stream keeps
         # 3 + fe_lanes + 1 slots rotating so that packing, decoding, front-end launches and the MSM of different batches overlap; under a
         # budget the rotation shrinks towards the minimum of 3 (fewer batches in flight: throughput cost in profiles/r05_verify_footprint.txt).
@@ -254,6 +264,7 @@ class ShuffleBatchVerifier:
         ell, lg = self.crs.ell, self.crs.lg
         offs = [4 * ell + 2 + j for j in range(6)] + [4 * ell + 12 + 4 * lg + j for j in range(4)]
         self._exact_offsets = (ctypes.c_uint32 * N_EXACT_POINTS)(*offs)
+        assert self._rowin_scalars == ell + 28 + 4 * lg      # csrc/kernels_rows.h RowIn: _decide_flagged_device indexes its slots
 
     # ---------------------------------------------------------------- lifetime
     def close(self) -> None:
@@ -288,6 +299,8 @@ class ShuffleBatchVerifier:
             if b is not None:
                 for k in ("wire", "pts", "pstat", "sgflags", "sc", "rowin", "hstat", "csrows", "dstat"):
                     b[k].free()
+                for x in (b.get("exact") or {}).values():
+                    x.free()
                 for h in b["host"].values():
                     if isinstance(h, N.PinnedBuffer):          # (the staging dict also caches plain ctypes buffers)
                         h.free()
@@ -677,6 +690,67 @@ class ShuffleBatchVerifier:
         N.cg1_add(tmp, own, shared)
         return bool(N.cg1_is_identity(tmp.raw))
 
+    def _decide_flagged_device(self, tk: dict, flagged: List[int]):
+        """MSM lane: the live proofs `flagged` of the batch (each carries a point outside G1 in the same-scalar argument) decided together,
+        as _decide_flagged decides one: -> ([accepted per proof], native calls made).
+          * the 4 f same-scalar equalities EXACTLY, in one launch of k_exact_relations: term lists straight over the slot's decoded points
+            (the CRS points lie behind them at n L) and its row-input blocks (alpha at head slot 6, z_k z_t z_u at fields() + 2 .. 4);
+            index arithmetic from `Layout` / `RowIn`, no point or scalar is copied;
+          * the weighted statement of those proofs with w1..w4 (rho[8..11]) ZERO: their row-input blocks compacted with the four slots
+            cleared and their own points compacted (k_exact_gather), one cg1_shuffle_rows_device call over the subset, and P_i over the own
+            points, Q_i over the CRS points from two msm_batched_device calls, as the independent fallback does.
+        A proof is accepted iff its four relations hold and P_i + Q_i is the identity.  The buffers belong to the slot and are allocated once,
+        at the slot's capacity; the number of native calls that launch, copy or wait does not depend on f (the f sums P_i + Q_i of the blobs
+        the two MSM calls return are host arithmetic, as in the independent fallback)."""
+        import numpy as np
+
+        crs, ctx = self.crs, self.ctx_msm
+        L, C, K, ell, lg = crs.points_per_proof, crs.ncrs, self._rowin_scalars, crs.ell, crs.lg
+        b, n, f = tk["slot"], tk["n"], len(flagged)
+        x = b.get("exact")
+        if x is None:
+            cap = b["cap"]
+            x = b["exact"] = {"ok": ctx.alloc(4 * cap), "rowin": ctx.alloc(cap * K * 32), "pts": ctx.alloc(cap * L * 96), "rep": ctx.alloc(cap * C * 96),
+                              "sc": ctx.alloc((cap * L + C) * 32), "csrows": ctx.alloc(cap * C * 32), "dstat": ctx.alloc(4 * cap),
+                              "hstat": ctx.alloc(4 * cap), "pstat": ctx.alloc(cap * L)}
+            x["hstat"].upload(bytes(4 * cap)); x["pstat"].upload(bytes(cap * L))      # live proofs, decodable points: never written again
+        calls = 0
+        idx = np.asarray(flagged, dtype=np.uint64)
+        own, cb, sb = idx * L + 4 * ell, n * L, idx * K
+        fields = ell + 10 + 4 * lg
+        al, zk, zt, zu = sb + 6, sb + fields + 2, sb + fields + 3, sb + fields + 4
+        T1, T2, U1, U2, R, S = (own + j for j in range(2, 8))
+        A1, A2, B1, B2 = (own + 12 + 4 * lg + j for j in range(4))
+        H, Gt, Gu = (np.full(f, cb + ell + 4 + j, dtype=np.uint64) for j in range(3))
+        neg, one_neg = N.EXACT_NEG, N.EXACT_ONE | N.EXACT_NEG
+        none, zero = np.full(f, N.EXACT_NONE, dtype=np.uint64), np.zeros(f, dtype=np.uint64)
+        minus_one = np.full(f, one_neg, dtype=np.uint64)
+        terms = np.stack([Gt, zt, A1, minus_one, T1, al | neg, none, zero,                  # G_t z_t - cm_A.T_1 - alpha T_1
+                          R, zk, H, zt, A2, minus_one, T2, al | neg,                        # R z_k + H z_t - cm_A.T_2 - alpha T_2
+                          Gu, zu, B1, minus_one, U1, al | neg, none, zero,                  # G_u z_u - cm_B.T_1 - alpha U_1
+                          S, zk, H, zu, B2, minus_one, U2, al | neg], axis=1).astype("<u4")  # S z_k + H z_u - cm_B.T_2 - alpha U_2
+        ctx.check(N.cg1_exact_relations_device(ctx.handle, b["pts"].ptr, n * L + C, b["rowin"].ptr, n * K, terms.tobytes(), 4 * f, x["ok"].ptr))
+        i32 = idx.astype("<u4").tobytes()
+        ctx.check(N.cg1_exact_gather_device(ctx.handle, b["rowin"].ptr, n, K * 32, i32, f, x["rowin"].ptr, K * 32, K * 32, (fields + 6 + 8) * 32, 4 * 32))
+        ctx.check(N.cg1_exact_gather_device(ctx.handle, b["pts"].ptr, n, L * 96, i32, f, x["pts"].ptr, L * 96, L * 96, 0, 0))
+        ctx.check(N.cg1_exact_gather_device(ctx.handle, b["pts"].ptr + n * L * 96, 1, 0, bytes(4 * f), f, x["rep"].ptr, C * 96, C * 96, 0, 0))
+        ctx.check(N.cg1_shuffle_rows_device(ctx.handle, ell, lg, f, x["rowin"].ptr, x["hstat"].ptr, x["pstat"].ptr, x["sc"].ptr, x["csrows"].ptr,
+                                            x["dstat"].ptr))
+        ctx.check(N.cg1_stream_sync(ctx.handle))
+        p_own = ctx.msm_batched_device(x["pts"], x["sc"], [j * L for j in range(f + 1)])
+        p_crs = ctx.msm_batched_device(x["rep"], x["csrows"], [j * C for j in range(f + 1)])
+        ok, dstat = x["ok"].download(4 * f), np.frombuffer(x["dstat"].download(4 * f), dtype="<i4")
+        calls += 10
+        tmp = ctypes.create_string_buffer(N.POINT_BYTES)
+        out = []
+        for j in range(f):
+            good = ok[4 * j: 4 * j + 4] == b"\x01\x01\x01\x01" and dstat[j] == 0
+            if good:
+                N.cg1_add(tmp, p_own[j], p_crs[j])
+                good = bool(N.cg1_is_identity(tmp.raw))
+            out.append(good)
+        return out, calls
+
     def _fe_lane(self, k: int, n: int):
         """Front-end lane k: its own context (stream), device front-end handle and aux staging, created on first use."""
         pair = self._fe[k]
@@ -746,7 +820,7 @@ class ShuffleBatchVerifier:
             self._release_lanes()                             # (lanes a single batch may have built on this verifier itself)
             dev = self.ctx.device
             self._kids = [ShuffleBatchVerifier(self.crs, N.Context(dev), threads=self.threads, chunk=self.chunk, device_rows=self.device_rows,
-                                               blocking_sync=self.blocking_sync, device_front_end=True, fe_lanes=self.fe_lanes, fe_prio=self.fe_prio, pipelines=1,
+                                               blocking_sync=self.blocking_sync, device_front_end=True, fe_lanes=self.fe_lanes, fe_prio=self.fe_prio, pipelines=1, exact_device=self.exact_device,
                                                max_pinned_bytes=self.max_pinned_bytes, coalesce=0)      # (the stream is coalesced once, by this verifier: a child
                                                                                                        # waiting for a second batch to merge would starve its siblings' order)
                           for _ in range(self.pipelines)]
@@ -906,15 +980,24 @@ class ShuffleBatchVerifier:
                 # (None in honest traffic.  The flags were brought back by the decompression lane: tk["sgflags"].)
                 tk["flags_done"].wait()
                 flags = tk["sgflags"]
-                n_exact = 0
+                n_exact, exact_path, exact_calls = 0, None, 0
                 if flags is not None and any(flags):
                     was_live = set(live)
-                    for i in range(n):
-                        if i in was_live and any(flags[i * N_EXACT_POINTS: (i + 1) * N_EXACT_POINTS]):
-                            n_exact += 1
+                    flagged = [i for i in range(n) if i in was_live and any(flags[i * N_EXACT_POINTS: (i + 1) * N_EXACT_POINTS])]
+                    n_exact = len(flagged)
+                    on_device = bool(flagged) and tk["device_rows"] and (self.exact_device if self.exact_device is not None
+                                                                          else n_exact >= self.EXACT_DEVICE_MIN)
+                    if on_device:
+                        exact_path = "device"
+                        verdicts, exact_calls = self._decide_flagged_device(tk, flagged)
+                        for i, good in zip(flagged, verdicts):
+                            status[i] = 0 if good else REJECT_EQUATION
+                    elif flagged:
+                        exact_path, exact_calls = "host", n_exact      # one decision per proof, each a dozen native calls of its own
+                        for i in flagged:
                             status[i] = 0 if self._decide_flagged(tk, i) else REJECT_EQUATION
                 tk["status"] = status
-                tk["stats"] = {"merged_msm_s": t1 - t0, "exact_checks": n_exact, "independent_s": time.perf_counter() - t1, "merged_ok": merged_ok,
+                tk["stats"] = {"merged_msm_s": t1 - t0, "exact_checks": n_exact, "exact_path": exact_path, "exact_native_calls": exact_calls, "independent_s": time.perf_counter() - t1, "merged_ok": merged_ok,
                                "front_end_s": tk.get("front_end_s", 0.0), "decompress_s": tk.get("decompress_s", 0.0), "n": n, "points": n * L + C, "pipelined": len(tk["bounds"]) > 1}
             except BaseException as e:
                 tk["error"] = e
@@ -1067,7 +1150,7 @@ class ShuffleBatchVerifier:
             if host_ms < 12.5 + 0.03 * n:
                 if self._host_twin is None:
                     self._host_twin = ShuffleBatchVerifier(self.crs, self._ctx if not getattr(self, "_own_ctx", False) else None, threads=self.threads,
-                                                           chunk=self.chunk, device_rows=self.device_rows, blocking_sync=self.blocking_sync, device_front_end=False)
+                                                           chunk=self.chunk, device_rows=self.device_rows, blocking_sync=self.blocking_sync, device_front_end=False, exact_device=self.exact_device)
                 tw = self._host_twin
                 out = tw.verify_packed(instances, proofs, n, mode=mode, rng=rng, weights=weights, pre_status=pre_status)
                 self.last_status, self.last_stats = tw.last_status, tw.last_stats
@@ -1126,9 +1209,19 @@ class OpeningBatchVerifier:
     SMALL_EXACT = 4                         # up to this many proofs are checked one by one on the host (cg1_opening_exact_status: ~0.4 ms each;
                                             # the GPU path is ~2.4 ms of dependent launches whatever the batch: IsValidWhiskOpeningProof is a batch of one)
 
-    def __init__(self, ctx: Optional["N.Context"] = None, device_front_end: bool = True):
+    EXACT_DEVICE_MIN = 16                   # (exact_device=None) from this many proofs that carry a point outside G1 on, they are decided in ONE device pass
+                                            # (_decide_outside_device) instead of one cg1_opening_exact each.  profiles/r19_exact_device_timing.txt, 65 536
+                                            # proofs per batch: 1 flagged 15.9 ms on the host against 16.7, 16 flagged 21.0 against 16.9 (the smallest measured
+                                            # count at which the pass wins by more than the spread), 256: 100 against 17.2, all 65 536: 21.6 s against 0.107
+
+    def __init__(self, ctx: Optional["N.Context"] = None, device_front_end: bool = True, exact_device: Optional[bool] = None):
         self._ctx = ctx
         self.device_front_end = bool(device_front_end)
+        # exact_device: how the proofs that carry a point outside G1 are decided (batches above SMALL_EXACT).  False: one by one on the host
+        # (cg1_opening_exact); True: all of them in one pass on the device (_decide_outside_device); None: the device from EXACT_DEVICE_MIN on.
+        self.exact_device = exact_device
+        self.last_exact_path: Optional[str] = None      # "host" / "device": how the last batch's flagged proofs were decided; None: it had none
+        self._xdev = None                     # (capacity, d_wire, d_pts, d_stat, d_sc, d_ok) of the device pass, kept between calls
         g = ctypes.create_string_buffer(N.POINT_BYTES)
         N.cg1_generator(g)
         aff = ctypes.create_string_buffer(96)
@@ -1211,6 +1304,45 @@ class OpeningBatchVerifier:
             self._dev = (cap, ctx.alloc(96 * (5 * cap + 1)), ctx.alloc(32 * (5 * cap + 1)))
         return self._dev[1], self._dev[2]
 
+    def _decide_outside_device(self, idx, trackers, kcs, pfs) -> List[bool]:
+        """The proofs idx of the batch -- each carries a point outside G1 and nothing else is wrong with it -- decided EXACTLY in one pass:
+        their challenges in one pooled host call (cg1_opening_challenges), their five points decoded again WITHOUT the subgroup test in one
+        launch (the checked decoder's output for a flagged point is not relied on), then the 2 f relations s G + c k_G - A and
+        s r_G + c k_r_G - B (opening.py:73-74) in one launch of k_exact_relations.  The number of native calls and waits does not depend on f."""
+        import numpy as np
+
+        ctx, f = self.ctx, len(idx)
+        if self._xdev is None or self._xdev[0] < f:
+            cap = max(f, 256, 2 * (self._xdev[0] if self._xdev else 0))
+            if self._xdev is not None:
+                for b in self._xdev[1:]:
+                    b.free()
+                self._xdev = None
+            self._xdev = (cap, ctx.alloc(240 * cap), ctx.alloc(96 * (5 * cap + 1)), ctx.alloc(5 * cap), ctx.alloc(64 * cap), ctx.alloc(2 * cap))
+            self._xdev[2].upload(self._g96)                  # point 0: the generator, once per allocation
+        _, d_wire, d_pts, d_stat, d_sc, d_ok = self._xdev
+        rows = np.asarray(idx, dtype=np.int64)
+        trk = np.frombuffer(trackers, dtype=np.uint8).reshape(-1, 96)[rows]
+        kc = np.frombuffer(kcs, dtype=np.uint8).reshape(-1, 48)[rows]
+        pf = np.frombuffer(pfs, dtype=np.uint8).reshape(-1, 128)[rows]
+        c32 = np.empty((f, 32), dtype=np.uint8)
+        ctx.check(N.cg1_opening_challenges(trk.ctypes.data, kc.ctypes.data, pf.ctypes.data, f, c32.ctypes.data, 0))
+        # points: the generator, then r_G k_r_G k_G A B of proof j at 1 + 5 j ..; scalars 2 j, 2 j + 1: s, c
+        d_wire.upload(np.concatenate([trk, kc, pf[:, :96]], axis=1).tobytes())
+        ctx.check(N.cg1_batch_decompress_device(ctx.handle, d_wire.ptr, d_pts.ptr + 96, d_stat.ptr, 5 * f, 0))
+        d_sc.upload(np.concatenate([pf[:, 96:], c32], axis=1).tobytes())
+        j = np.arange(f, dtype=np.uint32)
+        p, k = 1 + 5 * j, 2 * j
+        g, zero = np.zeros(f, dtype=np.uint32), np.zeros(f, dtype=np.uint32)
+        minus_one, none = np.full(f, N.EXACT_ONE | N.EXACT_NEG, dtype=np.uint32), np.full(f, N.EXACT_NONE, dtype=np.uint32)
+        terms = np.stack([g, k, p + 2, k + 1, p + 3, minus_one, none, zero,                  # s G + c k_G - A
+                          p, k, p + 1, k + 1, p + 4, minus_one, none, zero], axis=1).astype("<u4")      # s r_G + c k_r_G - B
+        ctx.check(N.cg1_exact_relations_device(ctx.handle, d_pts.ptr, 5 * f + 1, d_sc.ptr, 2 * f, terms.tobytes(), 2 * f, d_ok.ptr))
+        ctx.check(N.cg1_stream_sync(ctx.handle))
+        ok = np.frombuffer(d_ok.download(2 * f), dtype=np.uint8).reshape(f, 2)
+        undecoded = np.frombuffer(d_stat.download(5 * f), dtype=np.uint8).reshape(f, 5)
+        return ((ok == 1).all(axis=1) & (undecoded == 0).all(axis=1)).tolist()
+
     def verify_many(self, items, rng=None, _seed: Optional[bytes] = None) -> List[bool]:
         """One verdict per (tracker, k_commitment, proof).  The batch weights come from 32 fresh bytes of the OS per call; `_seed` replaces
         them for TESTS that compare two front-ends on the same weights -- a seed that is reused or known to the prover makes every weight
@@ -1227,7 +1359,7 @@ class OpeningBatchVerifier:
 
     def _verify(self, n, trackers, kcs, pfs, pre, rng, seed=None) -> List[bool]:
         if n == 0:
-            self.last_status = []
+            self.last_status, self.last_exact_path = [], None
             return []
         if n <= self.SMALL_EXACT:
             # the reference's own two equalities (opening.py:73-74), asserted exactly, proof by proof: no weights, no GPU round trips
@@ -1238,7 +1370,7 @@ class OpeningBatchVerifier:
                 if rc:
                     raise N.NativeError(f"cg1_opening_exact_status failed ({rc})")
                 status.append((pre[i] if pre else 0) or int(st.value))
-            self.last_status = status
+            self.last_status, self.last_exact_path = status, None
             return [s == 0 for s in status]
         ctx = self.ctx
         if seed is None:
@@ -1293,8 +1425,14 @@ class OpeningBatchVerifier:
                     if not N.cg1_is_identity(tmp.raw):
                         status[i] = REJECT_EQUATION
         ok = ctypes.c_int(0)
-        for i in outside:
-            if status[i] == 2:                       # rejected only for the subgroup flag: the exact equalities decide
+        flagged = [i for i in outside if status[i] == 2]      # rejected only for the subgroup flag: the exact equalities decide
+        on_device = bool(flagged) and (self.exact_device if self.exact_device is not None else len(flagged) >= self.EXACT_DEVICE_MIN)
+        self.last_exact_path = None if not flagged else "device" if on_device else "host"
+        if on_device:
+            for i, good in zip(flagged, self._decide_outside_device(flagged, trackers, kcs, pfs)):
+                status[i] = 0 if good else REJECT_EQUATION
+        else:
+            for i in flagged:
                 ctx.check(N.cg1_opening_exact(trackers[96 * i: 96 * i + 96], kcs[48 * i: 48 * i + 48], pfs[128 * i: 128 * i + 128], ctypes.byref(ok)))
                 status[i] = 0 if ok.value else REJECT_EQUATION
         self.last_status = status

@@ -511,6 +511,44 @@ int cg1_opening_exact(const uint8_t* tracker96 /* r_G | k_r_G */, const uint8_t*
  * OpeningBatchVerifier uses for a handful of proofs -- IsValidWhiskOpeningProof itself (whisk_interface.py:147-169) is a batch of ONE: five
  * single decompressions and four scalar multiplications on the host (~0.4 ms) against ~2.4 ms of dependent GPU launches. */
 int cg1_opening_exact_status(const uint8_t* tracker96, const uint8_t* k_commitment48, const uint8_t* proof128, int* status);
+/* Exact relations in bulk: ok[i] = 1 iff sum_j (+-) k_j * P_j over the (at most CG1_EXACT_TERMS) terms of relation i is the identity --
+ * what the two entries above evaluate for one proof, for any number of relations over flat arrays:
+ *   points96     n_points affine96 records (x | y, 48-byte little-endian standard form; all-zero = the identity); ANY point of the curve,
+ *                inside G1 or not -- nothing is folded, split or reduced, a scalar is its 256-bit integer
+ *   scalars32    n_scalars 32-byte little-endian scalars (n_scalars < CG1_EXACT_ONE)
+ *   terms        n_relations x CG1_EXACT_TERMS records of two uint32: { point index, or CG1_EXACT_NONE for "no term" ; scalar index, or
+ *                CG1_EXACT_ONE for the scalar one (no ladder is paid for it), with CG1_EXACT_NEG set for a minus sign }.  HOST memory in
+ *                both entries: every index is checked before anything runs (cg1_exact_relations_check; CG1_ERR_ARG, nothing written).
+ * cg1_exact_relations_device: d_points96, d_scalars32 and d_ok are DEVICE memory.  The records are host memory here too -- not a device
+ * array -- BECAUSE every index is checked on the host before the launch; they travel through one of two page-locked blocks the context
+ * keeps and uses in turn, then ONE launch (k_exact_relations: a wave per relation, the terms of a relation share one ladder's
+ * doublings) on the context's stream.  It allocates nothing once the kept blocks have grown and waits for no kernel and not for its own
+ * upload: the caller synchronises the stream before reading d_ok (a staging block is reused only after the upload it carried two calls
+ * earlier has left it -- the only wait inside, and none when fewer than three calls are in flight).  The device entry ASSUMES what
+ * cg1_batch_decompress_device produces: canonical coordinates (< p) of points on the curve; it cannot refuse a coordinate >= p as the
+ * host twin does (the kernel would compute with the unreduced value), and neither entry tests the curve equation.
+ * cg1_exact_relations: the host twin over host arrays on the worker pool (n_threads <= 0: all of it); a coordinate >= p: CG1_ERR_ENCODING.
+ * cg1_exact_gather_device: dst block j (at j * dst_stride_bytes) = src block idx[j] (at idx[j] * src_stride_bytes; a stride of 0 repeats one
+ * block), block_bytes each, with the bytes [clear_off, clear_off + clear_bytes) of every copied block zeroed -- the flagged subset of a batch
+ * compacted on the device (row-input blocks with the same-scalar weights cleared, own points, CRS points repeated) for the weighted pass over
+ * it.  Device memory in and out, idx in host memory and checked against n_src_blocks there (CG1_ERR_ARG; also for sizes that are no
+ * multiple of 4 or a block longer than a stride); one launch on the context's stream through the same staging, no wait for it.
+ * cg1_opening_challenges: the transcript half of cg1_opening_exact_status for n proofs on the worker pool: out_c32[i] = the challenge c of
+ * proof i (trackers96 n x (r_G | k_r_G), k_commitments48, proofs128 as cg1_opening_exact takes them; the encodings are absorbed as they
+ * are, decodable or not). */
+#define CG1_EXACT_TERMS 4
+#define CG1_EXACT_NEG   0x80000000u
+#define CG1_EXACT_ONE   0x7fffffffu
+#define CG1_EXACT_NONE  0xffffffffu
+int cg1_exact_relations_check(const uint32_t* terms, size_t n_relations, size_t n_points, size_t n_scalars);
+int cg1_exact_relations(const uint8_t* points96, size_t n_points, const uint8_t* scalars32, size_t n_scalars, const uint32_t* terms,
+                        size_t n_relations, uint8_t* ok, int n_threads);
+int cg1_exact_relations_device(cg1_ctx* ctx, const void* d_points96, size_t n_points, const void* d_scalars32, size_t n_scalars,
+                               const uint32_t* terms, size_t n_relations, void* d_ok);
+int cg1_exact_gather_device(cg1_ctx* ctx, const void* d_src, size_t n_src_blocks, size_t src_stride_bytes, const uint32_t* idx, size_t n_idx,
+                            void* d_dst, size_t dst_stride_bytes, size_t block_bytes, size_t clear_off, size_t clear_bytes);
+int cg1_opening_challenges(const uint8_t* trackers96, const uint8_t* k_commitments48, const uint8_t* proofs128, size_t n, uint8_t* out_c32,
+                           int n_threads);
 /* just the gather step: every proof's own points (instance, then the proof's points in wire order) */
 int cg1_shuffle_gather_points(const cg1_shuffle_crs* crs, size_t n_proofs, const uint8_t* instances, const uint8_t* proofs,
                               uint8_t* out_points48);
