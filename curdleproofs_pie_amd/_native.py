@@ -340,6 +340,11 @@ cg1_whisk_shuffle_draws = _proto("cg1_whisk_shuffle_draws", c_int, c_size_t, c_s
 cg1_whisk_shuffle_prove_seeded = _proto("cg1_whisk_shuffle_prove_seeded", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p)
 WHISK_SHUFFLE_DRAWS_MAX_PROVERS, WHISK_SHUFFLE_NO_DECODE, WHISK_SHUFFLE_NOT_G1 = 4096, 2, 3      # CG1_WHISK_SHUFFLE_* of include/curdle_g1.h
+# a chain of shuffles over a device-resident tracker set (csrc/kernels_tracker_set.h, csrc/capi_tracker_set.h; cg1_chain_expand: csrc/shuffle_verify.cpp)
+cg1_chain_expand = _proto("cg1_chain_expand", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, POINTER(c_size_t))
+cg1_batch_decompress_strided_enqueue = _proto("cg1_batch_decompress_strided_enqueue", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t)
+cg1_chain_gather_enqueue = _proto("cg1_chain_gather_enqueue", c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t)
+cg1_chain_scatter_enqueue = _proto("cg1_chain_scatter_enqueue", c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t)
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -372,6 +377,7 @@ EXPORTED_SYMBOLS = [
     "cg1_whisk_shuffle_draws_device", "cg1_whisk_shuffle_draws", "cg1_whisk_shuffle_prove_seeded",
     "cg1_tracker_match_device", "cg1_tracker_match", "cg1_tracker_match_last_ms",
     "cg1_exact_relations_check", "cg1_exact_relations", "cg1_exact_relations_device", "cg1_exact_gather_device", "cg1_opening_challenges",
+    "cg1_chain_expand", "cg1_batch_decompress_strided_enqueue", "cg1_chain_gather_enqueue", "cg1_chain_scatter_enqueue",
 ]
 
 

@@ -267,11 +267,9 @@ __device__ __forceinline__ fp fp_sqrt_chain(const fp& a) {
 // register footprint of the subgroup test's scalar multiplication (256 VGPRs + spills, 1 wave/SIMD when it did).
 // WAVES (per SIMD) is a template parameter too: at 3 the compiler keeps half of the chain's table in scratch (168 VGPRs, 224 bytes, 45
 // scratch loads per point against 148 862 multiplies) and a third wave shares the multiplier; 2 = the table in registers (214 VGPRs).
-template <bool CHECK, int WAVES>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) k_batch_decompress(const uint8_t* __restrict__ in48, uint32_t* __restrict__ out_raw,
-                                                          uint8_t* __restrict__ status, uint32_t n) {
-  uint32_t i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= n) return;
+// The per-point body is one inlined function of the point's index, so that the strided form below decodes exactly as this kernel does.
+template <bool CHECK>
+__device__ __forceinline__ void decompress_point(const uint8_t* __restrict__ in48, uint32_t* __restrict__ out_raw, uint8_t* __restrict__ status, uint32_t i) {
   const uint8_t* b = in48 + 48ull * i;
   uint32_t* dst = out_raw + 24ull * i;
   for (int k = 0; k < 24; ++k) dst[k] = 0;
@@ -310,6 +308,25 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WAVES,
   }
   for (int k = 0; k < 12; ++k) { dst[k] = w[k]; dst[12 + k] = yw[k]; }
   status[i] = CG1_OK;
+}
+template <bool CHECK, int WAVES>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) k_batch_decompress(const uint8_t* __restrict__ in48, uint32_t* __restrict__ out_raw,
+                                                          uint8_t* __restrict__ status, uint32_t n) {
+  uint32_t i = blockIdx.x * 128 + threadIdx.x;
+  if (i >= n) return;
+  decompress_point<CHECK>(in48, out_raw, status, i);
+}
+
+// The unchecked decoding through an index map: thread t decodes point (t / take) * stride + skip + t % take, for t < n_groups * take.  The
+// points [0, skip) and [skip + take, stride) of every group are neither read nor written, in any of the three arrays: in a chain of shuffles
+// (shuffle_chain.py) the first 2 ell points of a proof are the pre trackers, which were decoded before as an earlier block's posts or as
+// entries of the resident tracker set, and k_chain_gather copies them in behind this launch.
+template <int WAVES>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) k_batch_decompress_strided(const uint8_t* __restrict__ in48, uint32_t* __restrict__ out_raw,
+                                                          uint8_t* __restrict__ status, uint32_t n_groups, uint32_t stride, uint32_t skip, uint32_t take) {
+  const uint32_t t = blockIdx.x * 128 + threadIdx.x, g = t / take;
+  if (g >= n_groups) return;
+  decompress_point<false>(in48, out_raw, status, g * stride + skip + (t - g * take));
 }
 
 // The same decoding for a few hundred points at a time (the 585 single from_compressed_bytes_unchecked of one verification, decoded in

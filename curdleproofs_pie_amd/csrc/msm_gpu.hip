@@ -69,6 +69,7 @@ int pick_window(size_t n);
 #include "kernels_light.h"
 #include "kernels_tracker_scan.h"
 #include "kernels_exact.h"         // k_exact_relations: signed sums of at most four k P == identity, exact on all of E(Fp), a wave per relation
+#include "kernels_tracker_set.h"   // k_chain_gather / k_chain_scatter: decoded records between a batch's points and the resident tracker set
 }  // namespace cg1
 #include "kernels_rows.h"
 #include "kernels_merlin.h"
@@ -102,4 +103,5 @@ int pick_window(size_t n);
 #include "capi_shuffle.h"          // a whole shuffle proof proved on the device: cg1_shuffle_prove_device
 #include "capi_whisk_shuffle.h"    // GenerateWhiskShuffleProof from tracker bytes: cg1_whisk_shuffle_front, cg1_whisk_shuffle_prove_device
 #include "capi_exact.h"           // exact relations in bulk: cg1_exact_relations_device (host twin: csrc/shuffle_verify.cpp)
+#include "capi_tracker_set.h"     // a chain of shuffles over a resident tracker set: strided decoding, cg1_chain_gather_enqueue / _scatter_enqueue
 #include "capi_tracker_scan.h"    // which trackers a set of secrets opens: cg1_tracker_match_device and its host twin cg1_tracker_match

@@ -1346,6 +1346,60 @@ int cg1_shuffle_gather_points(const cg1_shuffle_crs* crs_, size_t n_proofs, cons
   return CG1_OK;
 }
 
+// A chain of shuffles over one tracker set (shuffle_chain.py): block j reads pre_j = [set[i] for i in indices_j] BEFORE any of its own
+// writes, then writes set[indices_j[t]] = post_j[t] for t = 0 .. ell - 1 in order (indices inside a block may repeat: the last write wins).
+//   set96          n_slots x (r_G | k_r_G), updated in place to the state after the last block
+//   out_instances  n_blocks x (vec_R | vec_S | vec_T | vec_U) encodings, what cg1_shuffle_gather_points reads (NULL: not wanted)
+//   out_plan       n_blocks x 2 ell entries, one per pre position (vec_R, then vec_S): where its decoded record already is.  >= 0: a point
+//                  of this batch, block b's T (or U) position t at b * stride_points + 2 ell + t (3 ell + t); < 0: ~(set point index), the
+//                  set's points being r_G at 2 s and k_r_G at 2 s + 1 as they were BEFORE the call (NULL: not wanted)
+//   out_writers    (slot, writer) per slot the blocks wrote, slots ascending, writer = b * ell + t of its last write; room for
+//                  min(n_slots, n_blocks * ell) pairs (NULL: not wanted); *out_n_writers = their number
+// An index >= n_slots refuses the call before anything is written.
+int cg1_chain_expand(uint8_t* set96, size_t n_slots, const uint32_t* indices, const uint8_t* posts96, size_t n_blocks, size_t ell, size_t stride_points,
+                     uint8_t* out_instances, int32_t* out_plan, uint32_t* out_writers, size_t* out_n_writers) {
+  if (ell == 0 || stride_points < 4 * ell || (n_slots && !set96) || (n_blocks && (!indices || !posts96)) || n_slots >= (1ull << 30) ||
+      n_blocks >= (1ull << 31) / stride_points || (out_writers && !out_n_writers))
+    return CG1_ERR_ARG;
+  for (size_t k = 0; k < n_blocks * ell; ++k)
+    if (indices[k] >= n_slots) return CG1_ERR_ARG;
+  std::vector<int32_t> last(n_slots, -1);                    // the writer of a slot's current value, -1: still the set's own
+  for (size_t b = 0; b < n_blocks; ++b) {
+    const uint32_t* idx = indices + b * ell;
+    const uint8_t* post = posts96 + b * ell * 96;
+    for (size_t t = 0; t < ell; ++t) {                       // every read, before the block's first write
+      const size_t s = idx[t];
+      if (out_instances) {
+        uint8_t* o = out_instances + b * 4 * ell * 48;
+        memcpy(o + t * 48, set96 + s * 96, 48);
+        memcpy(o + (ell + t) * 48, set96 + s * 96 + 48, 48);
+        memcpy(o + (2 * ell + t) * 48, post + t * 96, 48);
+        memcpy(o + (3 * ell + t) * 48, post + t * 96 + 48, 48);
+      }
+      if (out_plan) {
+        const int32_t w = last[s];
+        const int32_t at = w < 0 ? 0 : (int32_t)((size_t)w / ell * stride_points + 2 * ell + (size_t)w % ell);
+        out_plan[b * 2 * ell + t] = w < 0 ? ~(int32_t)(2 * s) : at;
+        out_plan[b * 2 * ell + ell + t] = w < 0 ? ~(int32_t)(2 * s + 1) : at + (int32_t)ell;
+      }
+    }
+    for (size_t t = 0; t < ell; ++t) {
+      memcpy(set96 + (size_t)idx[t] * 96, post + t * 96, 96);
+      last[idx[t]] = (int32_t)(b * ell + t);
+    }
+  }
+  if (out_n_writers) {
+    size_t m = 0;
+    for (size_t s = 0; s < n_slots; ++s)
+      if (last[s] >= 0) {
+        if (out_writers) { out_writers[2 * m] = (uint32_t)s; out_writers[2 * m + 1] = (uint32_t)last[s]; }
+        ++m;
+      }
+    *out_n_writers = m;
+  }
+  return CG1_OK;
+}
+
 // What the device front-end needs besides the points (csrc/kernels_frontend.h): per proof the seven Fr fields of the wire proof in
 // wire order (r_p c_final d_final z_k z_t z_u x_final) followed by the proof's 12 weights, 19 x 32 bytes.
 int cg1_shuffle_gather_aux(const cg1_shuffle_crs* crs_, size_t n_proofs, const uint8_t* proofs, const uint8_t* weights, uint8_t* out_aux) {

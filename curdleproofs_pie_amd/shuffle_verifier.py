@@ -502,12 +502,34 @@ class ShuffleBatchVerifier:
             ctx.check(N.cg1_shuffle_gather_points(crs.handle, cnt, ia, pa, b["host"]["wire"].ptr + a * L * 48))
         ctx.check(N.cg1_h2d_async(ctx.handle, b["wire"].ptr + lo * L * 48, wire, (hi - lo) * L * 48))
 
-    def _decompress_launch(self, b: dict, lo: int, hi: int) -> None:
-        """GPU thread: once the sub-batch's copy has landed, launch its decompression (points stay on the device for the MSM)."""
+    def _decompress_launch(self, b: dict, lo: int, hi: int, chain: Optional[dict] = None) -> None:
+        """GPU thread: once the sub-batch's copy has landed, launch its decompression (points stay on the device for the MSM).
+        chain (shuffle_chain.py): the pre trackers -- the first 2 ell points of every proof -- are not decoded again: the strided launch
+        leaves them out and the gather behind it, on the same stream, copies their records from where they were decoded before."""
         ctx, L = self.ctx, self.crs.points_per_proof
         ctx.check(N.cg1_copy_fence(ctx.handle))
-        ctx.check(N.cg1_batch_decompress_enqueue(ctx.handle, b["wire"].ptr + lo * L * 48, b["pts"].ptr + lo * L * 96,
-                                                 b["pstat"].ptr + lo * L, (hi - lo) * L, 0))
+        if chain is None:
+            ctx.check(N.cg1_batch_decompress_enqueue(ctx.handle, b["wire"].ptr + lo * L * 48, b["pts"].ptr + lo * L * 96,
+                                                     b["pstat"].ptr + lo * L, (hi - lo) * L, 0))
+            return
+        pre = 2 * self.crs.ell
+        ctx.check(N.cg1_batch_decompress_strided_enqueue(ctx.handle, b["wire"].ptr + lo * L * 48, b["pts"].ptr + lo * L * 96, b["pstat"].ptr + lo * L,
+                                                         hi - lo, L, pre, L - pre))
+        chain["decoded_points"] += (hi - lo) * (L - pre)
+
+    def _chain_gather(self, b: dict, n: int, lo: int, hi: int, chain: dict) -> None:
+        """GPU thread, directly behind the sub-batch's decoding: every pre position of the proofs [lo, hi) <- its source's decoded record
+        and status byte (an earlier proof's post position in this slot, or an entry of the resident set)."""
+        ctx, L, pre, ts = self.ctx, self.crs.points_per_proof, 2 * self.crs.ell, chain["set"]
+        ctx.check(N.cg1_chain_gather_enqueue(ctx.handle, b["pts"].ptr, b["pstat"].ptr, n * L, ts.d_pts.ptr, ts.d_pstat.ptr, 2 * ts.n_slots,
+                                             ctypes.addressof(chain["plan"]) + lo * pre * 4, lo, hi - lo, L, pre))
+        chain["gathered_points"] += (hi - lo) * pre
+
+    def _chain_scatter(self, b: dict, n: int, chain: dict) -> None:
+        """GPU thread, behind the batch's last sub-batch: the final post of every slot the batch wrote -> the resident set."""
+        ctx, ts = self.ctx, chain["set"]
+        ctx.check(N.cg1_chain_scatter_enqueue(ctx.handle, b["pts"].ptr, b["pstat"].ptr, n * self.crs.points_per_proof, ts.d_pts.ptr, ts.d_pstat.ptr,
+                                              2 * ts.n_slots, chain["pairs"], chain["n_pairs"]))
 
     def _decompress_collect(self, b: dict, lo: int, hi: int) -> None:
         """GPU thread: wait for the kernel, bring back the per-point verdicts and the 8-point window the front-end wants."""
@@ -530,11 +552,12 @@ class ShuffleBatchVerifier:
         L, C = crs.points_per_proof, crs.ncrs
         assert n >= 1 and len(instances) == n * 4 * crs.ell * 48 and len(proofs) == n * crs.proof_bytes
         weights = batch[4] if len(batch) > 4 else None       # None: drawn on the GPU thread while the first kernel runs
+        chain = batch[5] if len(batch) > 5 else None         # a chain plan (shuffle_chain.py): pre trackers are gathered, not decoded
         assert weights is None or len(weights) == n * N_WEIGHTS * 32
         b = self._slot(n)
         tk = {"slot": b, "n": n, "instances": instances, "proofs": proofs, "weights": weights, "mode": mode,
               "pre_status": batch[3] if len(batch) > 3 else None, "chunks": queue.Queue(), "done": threading.Event(),
-              "error": None, "t0": time.perf_counter(), "flags_done": threading.Event(), "sgflags": None}
+              "error": None, "t0": time.perf_counter(), "flags_done": threading.Event(), "sgflags": None, "chain": chain}
         step = max(self.chunk, (n + 1) // 2) if (prefetched and self.prefetch_big) else self.chunk
         tk["bounds"] = [(lo, min(lo + step, n)) for lo in range(0, n, step)]
         b["busy"] = tk["done"]
@@ -553,7 +576,11 @@ class ShuffleBatchVerifier:
                 bounds = tk["bounds"]
                 self._stage_in(b, instances, proofs, *bounds[0])
                 for i, (lo, hi) in enumerate(bounds):              # copy of sub-batch i+1 overlaps the kernel of sub-batch i
-                    self._decompress_launch(b, lo, hi)
+                    self._decompress_launch(b, lo, hi, chain)
+                    if chain is not None:
+                        self._chain_gather(b, n, lo, hi, chain)
+                        if i + 1 == len(bounds):
+                            self._chain_scatter(b, n, chain)
                     if tk["weights"] is None:
                         tk["weights"] = self.draw_weights(n, rng)
                     if i + 1 < len(bounds):
@@ -999,6 +1026,8 @@ class ShuffleBatchVerifier:
                 tk["status"] = status
                 tk["stats"] = {"merged_msm_s": t1 - t0, "exact_checks": n_exact, "exact_path": exact_path, "exact_native_calls": exact_calls, "independent_s": time.perf_counter() - t1, "merged_ok": merged_ok,
                                "front_end_s": tk.get("front_end_s", 0.0), "decompress_s": tk.get("decompress_s", 0.0), "n": n, "points": n * L + C, "pipelined": len(tk["bounds"]) > 1}
+                if tk["chain"] is not None:
+                    tk["stats"].update(decoded_points=tk["chain"]["decoded_points"], gathered_points=tk["chain"]["gathered_points"])
             except BaseException as e:
                 tk["error"] = e
             finally:
@@ -1020,7 +1049,8 @@ class ShuffleBatchVerifier:
     def verify_stream(self, batches, mode: str = "merged", rng=None):
         """Verify a sequence of batches, three stages overlapped across batches: while the host front-end works on batch k,
         the GPU finishes the MSM of batch k-1 and already decompresses batch k+1.
-        `batches` yields (instances, proofs, n[, pre_status[, weights]]); yields one status list (0 = valid) per batch."""
+        `batches` yields (instances, proofs, n[, pre_status[, weights[, chain plan]]]); yields one status list (0 = valid) per batch.
+        (The chain plan is shuffle_chain.ShuffleChainVerifier's: the batch's pre trackers are gathered from where they were decoded before.)"""
         if self.device_front_end:
             if self._host_twin is not None:            # (its lanes would keep hardware queues the pipelines need)
                 self._host_twin.close()

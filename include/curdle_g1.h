@@ -552,6 +552,33 @@ int cg1_opening_challenges(const uint8_t* trackers96, const uint8_t* k_commitmen
 /* just the gather step: every proof's own points (instance, then the proof's points in wire order) */
 int cg1_shuffle_gather_points(const cg1_shuffle_crs* crs, size_t n_proofs, const uint8_t* instances, const uint8_t* proofs,
                               uint8_t* out_points48);
+/* A chain of shuffles over one tracker set that stays on the device in decoded form (shuffle_chain.py).  Block j of a batch reads
+ * pre_j = [set[i] for i in indices_j] before any of its own writes, then writes set[indices_j[t]] = post_j[t], t = 0 .. ell - 1 in order
+ * (indices of a block may repeat: reads first, the last write wins).
+ * cg1_chain_expand (host): set96 = n_slots x (r_G | k_r_G), updated IN PLACE to the state after the last block; indices n_blocks x ell;
+ * posts96 n_blocks x ell x (r_G | k_r_G).  out_instances: the n_blocks x 4 ell x 48 bytes cg1_shuffle_gather_points reads (vec_R | vec_S |
+ * vec_T | vec_U).  out_plan: one entry per pre position (n_blocks x 2 ell: vec_R, then vec_S) saying where its decoded record already is --
+ * >= 0: a point of the batch's own array, the T (U) position t of the earlier block b at b * stride_points + 2 ell + t (3 ell + t);
+ * < 0: ~(set point index), the set holding r_G of slot s at point 2 s and k_r_G at 2 s + 1, as the set was before the call.
+ * out_writers: (slot, writer) for every slot the blocks wrote, slots ascending, writer = b * ell + t of the slot's last write (room for
+ * min(n_slots, n_blocks * ell) pairs), *out_n_writers their number.  Each output may be NULL.  An index >= n_slots: CG1_ERR_ARG, and nothing
+ * is written, set96 included.
+ * cg1_batch_decompress_strided_enqueue: cg1_batch_decompress_enqueue (unchecked) through an index map -- of every group of `stride` points
+ * the points [skip, skip + take) are decoded; the other positions of the three arrays are neither read nor written.
+ * cg1_chain_gather_enqueue: for the groups [first_group, first_group + n_groups) of d_pts96 / d_pstat (n_points records of 96 bytes / status
+ * bytes), point p < take of group g <- the record plan[(g - first_group) * take + p] names (as out_plan above).  A source >= 0 must lie in
+ * an earlier group, at a position >= take: a decoded position, never a gathered one.
+ * cg1_chain_scatter_enqueue: set point pairs[2 j] <- point pairs[2 j + 1] of d_pts96 / d_pstat; the set points of a call are distinct.
+ * The three device entries check every index on the host (CG1_ERR_ARG, nothing launched), carry `plan` / `pairs` (host memory) through the
+ * context's kept staging, launch on the context's stream and wait for nothing; record arrays are 16-byte aligned. */
+int cg1_chain_expand(uint8_t* set96, size_t n_slots, const uint32_t* indices, const uint8_t* posts96, size_t n_blocks, size_t ell, size_t stride_points,
+                     uint8_t* out_instances, int32_t* out_plan, uint32_t* out_writers, size_t* out_n_writers);
+int cg1_batch_decompress_strided_enqueue(cg1_ctx* ctx, const void* d_in48, void* d_out_affine96, void* d_status, size_t n_groups, size_t stride,
+                                         size_t skip, size_t take);
+int cg1_chain_gather_enqueue(cg1_ctx* ctx, void* d_pts96, void* d_pstat, size_t n_points, const void* d_set_pts96, const void* d_set_pstat, size_t n_set_points,
+                             const int32_t* plan, size_t first_group, size_t n_groups, size_t stride, size_t take);
+int cg1_chain_scatter_enqueue(cg1_ctx* ctx, const void* d_pts96, const void* d_pstat, size_t n_points, void* d_set_pts96, void* d_set_pstat, size_t n_set_points,
+                              const uint32_t* pairs, size_t n_pairs);
 /* fold cg1_batch_decompress_device's per-point status bytes (n_proofs x points_per_proof) into status[]: a proof
  * with an undecodable point becomes CG1_SHUFFLE_BAD_POINT and its scalars are zeroed (BufReader.read_g1, util.py:143-147) */
 int cg1_shuffle_apply_point_status(int32_t* status, const uint8_t* point_status, size_t n_proofs, size_t points_per_proof,
