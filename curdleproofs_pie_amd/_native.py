@@ -345,6 +345,14 @@ cg1_chain_expand = _proto("cg1_chain_expand", c_int, c_void_p, c_size_t, c_void_
 cg1_batch_decompress_strided_enqueue = _proto("cg1_batch_decompress_strided_enqueue", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t)
 cg1_chain_gather_enqueue = _proto("cg1_chain_gather_enqueue", c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_size_t)
 cg1_chain_scatter_enqueue = _proto("cg1_chain_scatter_enqueue", c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t)
+# a chain of shuffles PROVED over the resident set (csrc/chain_lineage.h, csrc/kernels_chain_prove.h, csrc/capi_chain_prove.h; cg1_chain_lineage: csrc/shuffle_verify.cpp)
+cg1_chain_lineage = _proto("cg1_chain_lineage", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           POINTER(c_size_t))
+cg1_chain_evolve_device = _proto("cg1_chain_evolve_device", c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, POINTER(c_size_t), c_void_p)
+cg1_chain_prove_seeded = _proto("cg1_chain_prove_seeded", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_size_t),
+                                c_void_p)
 cg1_shuffle_gather_points = _proto("cg1_shuffle_gather_points", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_shuffle_apply_point_status = _proto("cg1_shuffle_apply_point_status", c_int, _buf, _u8p, c_size_t, c_size_t, _buf, _buf, c_size_t)
 cg1_shuffle_sum_crs_scalars = _proto("cg1_shuffle_sum_crs_scalars", c_int, _buf, _buf, c_size_t, c_size_t, _buf)
@@ -378,6 +386,7 @@ EXPORTED_SYMBOLS = [
     "cg1_tracker_match_device", "cg1_tracker_match", "cg1_tracker_match_last_ms",
     "cg1_exact_relations_check", "cg1_exact_relations", "cg1_exact_relations_device", "cg1_exact_gather_device", "cg1_opening_challenges",
     "cg1_chain_expand", "cg1_batch_decompress_strided_enqueue", "cg1_chain_gather_enqueue", "cg1_chain_scatter_enqueue",
+    "cg1_chain_lineage", "cg1_chain_evolve_device", "cg1_chain_prove_seeded",
 ]
 
 

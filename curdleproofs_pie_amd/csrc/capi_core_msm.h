@@ -185,6 +185,7 @@ void cg1_ctx_destroy(cg1_ctx* ctx) {
   cg1::release_bufs(ctx->cap_opening, {cg1::dev_buf(ctx->d_opening)});
   cg1::release_bufs(ctx->cap_prover, {cg1::dev_buf(ctx->d_prover)});
   cg1::release_bufs(ctx->cap_whisk_draws, {cg1::dev_buf(ctx->d_whisk_draws)});
+  cg1::release_bufs(ctx->cap_chain_prove, {cg1::dev_buf(ctx->d_chain_prove)});
   cg1::release_bufs(ctx->cap_tscan_tab, {cg1::dev_buf(ctx->d_tscan_tab)});
   for (int i = 0; i < 2; ++i) cg1::release_bufs(ctx->cap_exact[i], {cg1::host_buf(ctx->h_exact[i]), cg1::dev_buf(ctx->d_exact[i])});
   cg1::release_bufs(ctx->cap_small_partial, {cg1::dev_buf(ctx->d_small_partial)});

@@ -31,6 +31,37 @@ WhiskLayout whisk_layout(size_t ell, size_t P) {
   return L;
 }
 
+// M = sum perm[i] G_i + sum vec_m_blinders[b] H_b of every prover as ONE k_table_msm launch over the CRS table, for whisk_front and the chain
+// prover (capi_chain_prove.h): the fields of the caller's layout it uses, the host rows, the launch.
+struct WhiskMFields { size_t tb, sc, offs, m48, st_msm; };
+TableShape whisk_m_shape(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t P, int& rc) {
+  const uint32_t Pn = (uint32_t)P, nn = (uint32_t)(ell + cg1whisk_host::N_BLINDERS);
+  const TableShape shape = table_pick_shape<FixedKind>(ctx, Pn, nn);
+  const size_t S = (nn + shape.slice - 1) / shape.slice, need = S > 1 ? (size_t)Pn * S : 0;
+  rc = cg1::grow_device(ctx, t->d_partial, t->cap_partial, need, need);
+  return shape;
+}
+void whisk_m_rows(uint8_t* H, const WhiskMFields& F, size_t ell, size_t P, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* perm,
+                  const uint8_t* vec_m_blinders32) {
+  constexpr size_t NB = cg1whisk_host::N_BLINDERS;
+  const size_t n = ell + NB;
+  uint32_t* tb = reinterpret_cast<uint32_t*>(H + F.tb);
+  uint32_t* offs = reinterpret_cast<uint32_t*>(H + F.offs);
+  for (size_t p = 0; p < P; ++p) {
+    memcpy(tb + p * n, g_index + p * ell, ell * 4); memcpy(tb + p * n + ell, h_index + p * NB, NB * 4);
+    cg1whisk_host::m_scalar_row(ell, perm + p * ell, vec_m_blinders32 + 32 * NB * p, H + F.sc + 32 * n * p);
+    offs[p] = (uint32_t)(p * n);
+  }
+  offs[P] = (uint32_t)(P * n);
+}
+int whisk_m_enqueue(cg1_ctx* ctx, cg1_fixed* t, uint8_t* D, const WhiskMFields& F, size_t ell, size_t P, const TableShape& shape) {
+  const uint32_t Pn = (uint32_t)P, nn = (uint32_t)(ell + cg1whisk_host::N_BLINDERS);
+  if (const int rc = table_enqueue<FixedKind>(ctx, t, (const uint32_t*)(D + F.tb), (const uint32_t*)(D + F.sc), (const uint32_t*)(D + F.offs), Pn, Pn * nn, nn, shape, false,
+                                              nullptr, D + F.m48)) return shuffle_refuse(ctx, rc);
+  HIPCHK(hipMemcpyAsync(D + F.st_msm, t->d_status, 16, hipMemcpyDeviceToDevice, ctx->stream));
+  return CG1_OK;
+}
+
 // The front on the context's stream.  The outputs are host buffers of the caller's or of the whole call's; nothing is written into them
 // before every refusal has been ruled out.  out_status / out_bad_at (both or neither): a tracker point that does not decode or lies
 // outside G1 then refuses ITS prover only -- code and tracker 2 + half of its first such point; its four outputs are zeros -- and the call
@@ -51,33 +82,25 @@ int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t 
   const WhiskLayout L = whisk_layout(ell, P);
   uint8_t* H; uint8_t* D;
   if (const int rc = chain_reserve(ctx, t, L.total, H, D)) return rc;
-  const uint32_t Pn = (uint32_t)P, nn = (uint32_t)n, np = (uint32_t)pts;
-  const TableShape shape = table_pick_shape<FixedKind>(ctx, Pn, nn);
-  {
-    const size_t S = (nn + shape.slice - 1) / shape.slice, need = S > 1 ? (size_t)Pn * S : 0;
-    if (const int rc = cg1::grow_device(ctx, t->d_partial, t->cap_partial, need, need)) return rc;
-  }
-  uint32_t* tb = reinterpret_cast<uint32_t*>(H + L.tb);
-  uint32_t* offs = reinterpret_cast<uint32_t*>(H + L.offs);
+  const uint32_t Pn = (uint32_t)P, np = (uint32_t)pts;
+  int shape_rc = CG1_OK;
+  const TableShape shape = whisk_m_shape(ctx, t, ell, P, shape_rc);
+  if (shape_rc) return shape_rc;
+  const WhiskMFields MF{L.tb, L.sc, L.offs, L.m48, L.st_msm};
   for (size_t p = 0; p < P; ++p) {
     uint8_t* enc = H + L.enc + p * 2 * ell * 48;            // r_G | k_r_G records -> vec_R | vec_S
     for (size_t i = 0; i < ell; ++i) {
       memcpy(enc + 48 * i, trackers96 + 96 * (p * ell + i), 48);
       memcpy(enc + 48 * (ell + i), trackers96 + 96 * (p * ell + i) + 48, 48);
     }
-    memcpy(tb + p * n, g_index + p * ell, ell * 4); memcpy(tb + p * n + ell, h_index + p * NB, NB * 4);
-    cg1whisk_host::m_scalar_row(ell, perm + p * ell, vec_m_blinders32 + 32 * NB * p, H + L.sc + 32 * n * p);
-    offs[p] = (uint32_t)(p * n);
   }
-  offs[P] = (uint32_t)(P * n);
+  whisk_m_rows(H, MF, ell, P, g_index, h_index, perm, vec_m_blinders32);
   memcpy(H + L.perm, perm, P * ell * 4); memcpy(H + L.k, k32, P * 32);
   memset(H + L.wst, 0, 16);
   if (const int rc = chain_upload(ctx, t, L)) return rc;
 
   // ---- M for every prover as one launch over the CRS table; it depends on no tracker and runs ahead of the scalar multiplications
-  if (const int rc = table_enqueue<FixedKind>(ctx, t, (const uint32_t*)(D + L.tb), (const uint32_t*)(D + L.sc), (const uint32_t*)(D + L.offs), Pn, Pn * nn, nn, shape, false,
-                                              nullptr, D + L.m48)) return shuffle_refuse(ctx, rc);
-  HIPCHK(hipMemcpyAsync(D + L.st_msm, t->d_status, 16, hipMemcpyDeviceToDevice, ctx->stream));
+  if (const int rc = whisk_m_enqueue(ctx, t, D, MF, ell, P, shape)) return rc;
   // ---- decode, certify, the call's status word, then the multiplications
   hipLaunchKernelGGL(cg1::k_batch_decompress_row, dim3((np + 3u) / 4u), dim3(64), 0, ctx->stream, (const uint8_t*)(D + L.enc), (uint32_t*)(D + L.rs), D + L.st_dec, np);
   hipLaunchKernelGGL(cg1::k_subgroup_row, dim3(np), dim3(64), 0, ctx->stream, (const uint32_t*)(D + L.rs), np, D + L.in_g1);
@@ -172,6 +195,15 @@ int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, u
   HIPCHK(hipGetLastError());
   return CG1_OK;
 }
+// the table's staging block holds k, the permutations and, after the chain, every blinder: both copies are zeroed before any return of a
+// seeded entry (which set t->chain_used = 0 when it began)
+hipError_t whisk_wipe_block(cg1_ctx* ctx, cg1_fixed* t) {
+  const size_t used = std::min(t->chain_used, t->cap_chain);               // what this call's layouts reached
+  if (!used) return hipSuccess;
+  memset(t->h_chain, 0, used);
+  const hipError_t e = hipMemsetAsync(t->d_chain, 0, used, ctx->stream), e2 = hipStreamSynchronize(ctx->stream);
+  return e != hipSuccess ? e : e2;
+}
 }  // namespace
 
 extern "C" {
@@ -265,14 +297,7 @@ int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   std::vector<uint8_t> rs(pts * 96), tu(pts * 96), post(pts * 48), m48(P * 48), proofs;
   std::vector<int32_t> st(P);
   std::vector<uint32_t> at(P);
-  // the table's staging block holds k, the permutations and, after the chain, every blinder: both copies are zeroed before any return
-  auto wipe_block = [&]() -> hipError_t {
-    const size_t used = std::min(t->chain_used, t->cap_chain);             // what this call's layouts reached
-    if (!used) return hipSuccess;
-    memset(t->h_chain, 0, used);
-    const hipError_t e = hipMemsetAsync(t->d_chain, 0, used, ctx->stream), e2 = hipStreamSynchronize(ctx->stream);
-    return e != hipSuccess ? e : e2;
-  };
+  auto wipe_block = [&]() -> hipError_t { return whisk_wipe_block(ctx, t); };
   if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, perm, sc + 32 * C.k, sc + 32 * C.mbl, rs.data(), tu.data(), post.data(), m48.data(),
                                  st.data(), at.data())) { (void)wipe_block(); return rc; }
   // ---- 3. the provers it did not refuse, moved to the front of every array, through the chain

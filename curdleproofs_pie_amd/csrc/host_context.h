@@ -129,6 +129,7 @@ struct Ctx {
   int tscan_timing = 0; float tscan_ms[2] = {0.f, 0.f};           // "tracker_scan_timing": wait between the phases of a scan and keep build / match wall ms
   void* d_prover = nullptr; size_t cap_prover = 0;                // cg1_opening_prove_device's scratch (1 252 B per proof)
   void* d_whisk_draws = nullptr; size_t cap_whisk_draws = 0;      // the seeded draws of Whisk shuffles (capi_whisk_shuffle.h): swaps | perm | scalars; zeroed before every return
+  void* d_chain_prove = nullptr; size_t cap_chain_prove = 0;      // the tracker stage of a proved chain (capi_chain_prove.h): certification, origins, composites (zeroed before every return), records
   PreparedPoint* d_gen_tab = nullptr;   // k_generator_mul's table of G (GEN_ENTRIES records), built at the first use (cg1_generator_mul_device)
   int fixed_slice = 0;                  // "fixed_slice": terms per workgroup of k_table_msm (1 .. 128; 0 = by the size of the call).  A/B switch
   int fixed_waves = 0;                  // "fixed_waves": waves per workgroup of k_table_msm (4, 8, 16; 0 = by the size of the call).  A/B switch

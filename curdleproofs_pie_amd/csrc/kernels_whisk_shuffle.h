@@ -61,17 +61,16 @@ struct PermuteMulArgs {
   uint32_t* post48;                          // [P][ell][2] 12 words each: T_i | U_i
 };
 
-// One WAVE per output point, as k_batch_mul_row: k belongs to the prover and so to the wave, the window digit is wave-uniform, and the
-// table of 15 multiples stays in registers (a point is four VGPRs in row form).  The output is finished here -- one row_inv of ZZ ZZZ --
-// because nothing on the host wants the XYZZ form: the chain behind takes affine96, the caller takes the encoding.
-__global__ void __launch_bounds__(64) k_whisk_permute_mul(PermuteMulArgs a) {
-  const uint32_t o = blockIdx.x;
-  if (o >= a.n_out || a.status[0] != 0u) return;           // (uniform) a refused call writes nothing
-  const uint32_t ell = a.ell, two = 2u * ell;
-  const uint32_t p = o / two, h = (o - p * two) / ell, i = o - p * two - h * ell;
-  if (a.prover_status && a.prover_status[p] != 0u) return; // (uniform)
-  uint32_t j = a.perm[(size_t)p * ell + i];
-  j = j < ell ? j : ell - 1u;                              // the host has refused perm[i] >= ell; clamp all the same
+// One WAVE per output point, as k_batch_mul_row: the scalar belongs to the wave, the window digit is wave-uniform, and the table of 15
+// multiples stays in registers (a point is four VGPRs in row form).  The output is finished here -- one row_inv of ZZ ZZZ -- because
+// nothing on the host wants the XYZZ form: the chain behind takes affine96, the caller takes the encoding.
+// whisk_mul_finish: the wave's body, shared by k_whisk_permute_mul and k_chain_lineage_mul (kernels_chain_prove.h): scalar8 (8 words,
+// little-endian, below r, wave-uniform) times the affine96 record at src96 (standard form, zeros = the identity) -> affine96 at d96 and
+// the 48-byte encoding at d48 (ENC_ALWAYS; ENC_IF_NAMED: only where d48 is not null); lane 0 writes.  Registers, scratch and LDS of
+// k_whisk_permute_mul are what they were with the body written out in the kernel: 188 VGPRs, 972 B scratch, no LDS.
+constexpr int ENC_ALWAYS = 1, ENC_IF_NAMED = 2;
+template <int ENC>
+__device__ __forceinline__ void whisk_mul_finish(const uint32_t* src96, const uint32_t* scalar8, uint32_t* d96, uint32_t* d48) {
   const RowK k = row_constants();
   const uint32_t l = k.lane16;
   uint32_t r2 = 0;
@@ -79,7 +78,7 @@ __global__ void __launch_bounds__(64) k_whisk_permute_mul(PermuteMulArgs a) {
   for (int t = 0; t < NL; ++t) r2 = l == (uint32_t)t ? fp_r2().l[t] : r2;
   xyzz_row P1;
   {
-    const uint32_t* w = a.rs96 + 24ull * ((size_t)p * two + (size_t)h * ell + j);
+    const uint32_t* w = src96;
     uint32_t wd[24], any = 0;
     for (int t = 0; t < 24; ++t) { wd[t] = w[t]; any |= wd[t]; }
     P1.X = row_mul(row_from_fp(fp_from_words(wd), l), r2, k);
@@ -87,7 +86,7 @@ __global__ void __launch_bounds__(64) k_whisk_permute_mul(PermuteMulArgs a) {
     P1.ZZ = k.one; P1.ZZZ = k.one; P1.inf = any ? 0u : 1u;
   }
   uint32_t s[8];
-  for (int t = 0; t < 8; ++t) s[t] = a.k[8ull * p + t];
+  for (int t = 0; t < 8; ++t) s[t] = scalar8[t];
   xyzz_row acc; acc.X = acc.Y = acc.ZZ = acc.ZZZ = 0; acc.inf = 1;
   if (!P1.inf) {
     xyzz_row T[15];                                                          // T[d - 1] = d P1
@@ -119,12 +118,24 @@ __global__ void __launch_bounds__(64) k_whisk_permute_mul(PermuteMulArgs a) {
   uint32_t w[24];
   for (int t = 0; t < 24; ++t) w[t] = 0;
   if (!acc.inf) { fp_to_words(xf, w); fp_to_words(yf, w + 12); }
-  uint32_t* d96 = a.tu96 + 24ull * o;
   for (int t = 0; t < 24; ++t) d96[t] = w[t];
-  uint32_t c[12];
-  compress_words(w, acc.inf != 0u, c);
-  uint32_t* d48 = a.post48 + 12ull * (((size_t)p * ell + i) * 2u + h);
-  for (int t = 0; t < 12; ++t) d48[t] = c[t];
+  if (ENC == ENC_ALWAYS || d48) {
+    uint32_t c[12];
+    compress_words(w, acc.inf != 0u, c);
+    for (int t = 0; t < 12; ++t) d48[t] = c[t];
+  }
+}
+
+__global__ void __launch_bounds__(64) k_whisk_permute_mul(PermuteMulArgs a) {
+  const uint32_t o = blockIdx.x;
+  if (o >= a.n_out || a.status[0] != 0u) return;           // (uniform) a refused call writes nothing
+  const uint32_t ell = a.ell, two = 2u * ell;
+  const uint32_t p = o / two, h = (o - p * two) / ell, i = o - p * two - h * ell;
+  if (a.prover_status && a.prover_status[p] != 0u) return; // (uniform)
+  uint32_t j = a.perm[(size_t)p * ell + i];
+  j = j < ell ? j : ell - 1u;                              // the host has refused perm[i] >= ell; clamp all the same
+  whisk_mul_finish<ENC_ALWAYS>(a.rs96 + 24ull * ((size_t)p * two + (size_t)h * ell + j), a.k + 8ull * p, a.tu96 + 24ull * o,
+                         a.post48 + 12ull * (((size_t)p * ell + i) * 2u + h));
 }
 
 // ---- the seeded draws (the format: whisk_shuffle_host.h)

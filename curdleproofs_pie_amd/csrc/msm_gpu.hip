@@ -83,6 +83,7 @@ int pick_window(size_t n);
 #include "kernels_same_scalar.h"   // k_sscalar_step: the same-scalar block's two phases around its one MSM launch
 #include "kernels_shuffle.h"       // k_shuffle_begin: the terms of a whole shuffle proof that depend on no later challenge than vec_a
 #include "kernels_whisk_shuffle.h" // k_whisk_permute_mul: the post-shuffle trackers of a Whisk shuffle, k vec_R | k vec_S through the permutation
+#include "kernels_chain_prove.h"   // k_chain_lineage_mul: every pre and post tracker of a proved chain from (origin slot, composite scalar), one launch
 #include "host_context.h"          // Ctx: streams, helper threads, scratch buffers
 #include "host_chains.h"           // planner + launch chains: regime A, k_msm_small, regime B
 #include "capi_core_msm.h"         // cg1_* : host operators, context, memory, parameters, MSM entry points
@@ -104,4 +105,5 @@ int pick_window(size_t n);
 #include "capi_whisk_shuffle.h"    // GenerateWhiskShuffleProof from tracker bytes: cg1_whisk_shuffle_front, cg1_whisk_shuffle_prove_device
 #include "capi_exact.h"           // exact relations in bulk: cg1_exact_relations_device (host twin: csrc/shuffle_verify.cpp)
 #include "capi_tracker_set.h"     // a chain of shuffles over a resident tracker set: strided decoding, cg1_chain_gather_enqueue / _scatter_enqueue
+#include "capi_chain_prove.h"     // a chain of shuffles PROVED over the resident set: cg1_chain_evolve_device, cg1_chain_prove_seeded (host lineage: chain_lineage.h)
 #include "capi_tracker_scan.h"    // which trackers a set of secrets opens: cg1_tracker_match_device and its host twin cg1_tracker_match

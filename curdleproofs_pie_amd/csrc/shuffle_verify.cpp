@@ -37,6 +37,7 @@
 
 #include "../../include/curdle_g1.h"
 #include "fr.h"
+#include "chain_lineage.h"
 #include "host_g1.h"
 #include "merlin_group.h"
 #include "pool.h"
@@ -1398,6 +1399,15 @@ int cg1_chain_expand(uint8_t* set96, size_t n_slots, const uint32_t* indices, co
     *out_n_writers = m;
   }
   return CG1_OK;
+}
+
+// The lineage of a chain of shuffles PROVED over a tracker set (chain_lineage.h): statuses, (origin slot, composite scalar) of every pre
+// and post position, and the last writers -- no point arithmetic.  Every refusal is made before anything is written.
+int cg1_chain_lineage(size_t n_slots, const uint8_t* point_status, const uint32_t* indices, const uint32_t* perm, const uint8_t* k32, size_t n_blocks, size_t ell,
+                      int32_t* out_status, uint32_t* out_bad_at, uint32_t* out_origin, uint8_t* out_scalar32, uint32_t* out_writers, size_t* out_n_writers) {
+  if (!point_status || (n_blocks && (!indices || !perm || !k32)) || (out_writers && !out_n_writers)) return CG1_ERR_ARG;
+  if (const int rc = cg1chain::lineage_check(nullptr, 0, "cg1_chain_lineage", n_slots, indices, perm, k32, n_blocks, ell)) return rc;
+  return cg1chain::lineage(n_slots, point_status, indices, perm, k32, n_blocks, ell, out_status, out_bad_at, out_origin, out_scalar32, out_writers, out_n_writers);
 }
 
 // What the device front-end needs besides the points (csrc/kernels_frontend.h): per proof the seven Fr fields of the wire proof in

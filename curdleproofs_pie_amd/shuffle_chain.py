@@ -8,6 +8,8 @@ moments earlier as somebody's posts.  Here they are decoded once:
 
     TrackerSet            the N trackers as host bytes (authoritative) and as 2 N decoded records + status bytes on the device
     ShuffleChainVerifier  blocks as (indices, post trackers, proof) against a TrackerSet
+    ShuffleChainProver    the other direction: ell slot indices per block and a seed in, such blocks out (its docstring; TrackerSet.evolve
+                          is its tracker stage alone)
 
 Semantics, block by block: block j reads pre_j = [set[i] for i in indices_j] BEFORE any of its own writes, then writes
 set[indices_j[t]] = post_j[t] for t = 0 .. ell - 1 in order (indices of a block may repeat: the last write wins).  Its status is exactly
@@ -37,6 +39,9 @@ from typing import List, Optional
 
 from . import _native as N
 from .shuffle_verifier import REJECT_LENGTH, ShuffleBatchVerifier, _tracker_bytes
+
+
+_FR_MODULUS = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 
 
 def _packed_trackers(trackers) -> bytes:
@@ -114,6 +119,90 @@ class TrackerSet:
             ctx.check(N.cg1_stream_sync(ctx.handle))
         finally:
             d_w.free(); d_p.free(); d_s.free()
+
+    def _check_open(self) -> None:
+        if self.d_pts is None or not self.ctx.handle:
+            raise ValueError("the tracker set is closed")
+
+    def _indices(self, indices, ell: int):
+        """n x ell slot indices (ints, or uint32 little-endian bytes) -> (uint32 array, n); ValueError for an index outside the set or a count
+        that is no multiple of ell"""
+        import numpy as np
+
+        if isinstance(indices, (bytes, bytearray, memoryview)):
+            wide = np.frombuffer(bytes(indices), dtype="<u4").astype(np.int64)
+        else:
+            wide = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if len(wide) % ell:
+            raise ValueError(f"{len(wide)} slot indices: not a multiple of ell = {ell}")
+        if len(wide) and (wide.min() < 0 or wide.max() >= self.n_slots):
+            raise ValueError(f"a slot index outside the set of {self.n_slots}")
+        return np.ascontiguousarray(wide.astype("<u4")), len(wide) // ell
+
+    def _apply_writers(self, writers, post96: bytes) -> None:
+        """host bytes of every slot written <- the T | U record of its last writer (b ell + t names record b ell + t of post96)"""
+        for slot, w in writers:
+            ctypes.memmove(ctypes.addressof(self._host) + 96 * int(slot), post96[96 * int(w): 96 * int(w) + 96], 96)
+
+    def _restore(self, before: bytes) -> None:
+        """back to `before`, decoded afresh: what a failed call leaves (ShuffleChainVerifier.verify_blocks_packed's except branch)"""
+        ctypes.memmove(self._host, before, len(before))
+        try:
+            self.ctx.check(N.cg1_stream_sync(self.ctx.handle))
+            self._load()
+        except Exception:
+            pass
+
+    def evolve(self, indices, perms, ks):
+        """The tracker stage of a chain alone (cg1_chain_evolve_device), permutations and scalars the caller's: block j reads
+        pre_j = [set[i] for i in indices_j] before any of its own writes and writes set[indices_j[t]] = ks[j] * pre_j[perms[j][t]], t in
+        order.  indices: n lists of ell slots (ell: the length of perms[0]); perms: n permutations of 0 .. ell - 1; ks: n scalars (ints or
+        32-byte little-endian strings, below r).  -> (post96, status): ell records T48 | U48 per block and a status per block, 0 or
+        WHISK_SHUFFLE_NO_DECODE / WHISK_SHUFFLE_NOT_G1 for a block that read such a point -- it writes nothing, its records are zeros.
+        The set is advanced, host bytes and device records.  `last_evolve_stats`: {"stage_ms", "certified_slots", "bad_at"}.  How a client
+        that trusts a chain follows its trackers without verifying.  ValueError: a shape, an index, a permutation, k >= r -- before anything
+        runs.  NativeError: the set is as it was before the call."""
+        import numpy as np
+
+        self._check_open()
+        perms = [list(p) for p in perms]
+        n = len(perms)
+        ell = len(perms[0]) if n else 1
+        if ell == 0 or any(len(p) != ell for p in perms):
+            raise ValueError("perms: n permutations of one length ell >= 1")
+        if any(sorted(p) != list(range(ell)) for p in perms):
+            raise ValueError("perms: every row a permutation of 0 .. ell - 1")
+        idx, n_idx = self._indices([i for block in indices for i in block] if not isinstance(indices, (bytes, bytearray, memoryview)) else indices, ell)
+        ks = list(ks)
+        if n_idx != n or len(ks) != n:
+            raise ValueError("evolve: n x ell indices, n permutations and n scalars")
+        k32 = bytearray()
+        for k in ks:
+            v = int.from_bytes(bytes(k), "little") if isinstance(k, (bytes, bytearray, memoryview)) else int(k)
+            if not 0 <= v < _FR_MODULUS:
+                raise ValueError("a scalar outside 0 .. r - 1")
+            k32 += v.to_bytes(32, "little")
+        if n == 0:
+            self.last_evolve_stats = {"stage_ms": 0.0, "certified_slots": 0, "bad_at": []}
+            return b"", []
+        pm = np.ascontiguousarray(np.asarray(perms, dtype="<u4").reshape(-1))
+        kbuf = (ctypes.c_char * len(k32)).from_buffer(k32)
+        post = ctypes.create_string_buffer(96 * ell * n)
+        st, at = (ctypes.c_int32 * n)(), (ctypes.c_uint32 * n)()
+        writers = np.empty((min(self.n_slots, n * ell), 2), dtype="<u4")
+        nw, stats = ctypes.c_size_t(0), (ctypes.c_float * 2)()
+        before = self.packed()
+        try:
+            self.ctx.check(N.cg1_chain_evolve_device(self.ctx.handle, self.d_pts.ptr, self.d_pstat.ptr, self.n_slots, idx.ctypes.data, pm.ctypes.data, kbuf, n, ell, post,
+                                                     st, at, writers.ctypes.data, ctypes.byref(nw), stats))
+            self._apply_writers(writers[: nw.value], post.raw)
+        except BaseException:
+            self._restore(before)
+            raise
+        finally:
+            ctypes.memset(kbuf, 0, len(k32))
+        self.last_evolve_stats = {"stage_ms": float(stats[0]), "certified_slots": int(stats[1]), "bad_at": list(at)}
+        return post.raw[: 96 * ell * n], list(st)
 
     def _free(self) -> None:
         for b in (self.d_wire, self.d_pts, self.d_pstat):
@@ -261,3 +350,124 @@ class ShuffleChainVerifier:
 
 def _addr_of(b: bytes) -> int:
     return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p).value
+
+
+class ShuffleChainProver:
+    """A chain of Whisk shuffles PROVED over a TrackerSet: `ell` slot indices per block and a seed in, blocks ready for
+    ShuffleChainVerifier.verify_blocks out, the set advanced on host and device.
+
+    prove_blocks(index_lists, seed=None, first_index=0)          -> [(indices, post_trackers, proof_bytes) or None where refused, ...]
+    prove_blocks_packed(indices, n, seed=None, first_index=0)    -> (post96, proofs, status): n x ell x (T48 | U48), n x (M || proof), a list
+    Both leave `last_status`, `last_refusals` ((tracker index, "r_G" | "k_r_G") or None per block, as ShuffleBatchProver's) and `last_stats`.
+
+    Block j, for j = 0 .. n - 1 in order, reads pre_j = [set[i] for i in indices_j] before any of its own writes.  Its outputs ARE item 0 of
+    ShuffleBatchProver.generate_packed(pre_j as 96 ell bytes, seed, first_index=first_index + j): the same post bytes, the same M || proof
+    bytes, the same status.  If the status is 0 it writes set[indices_j[t]] = post_j[t] for t = 0 .. ell - 1 in order (indices may repeat:
+    the last write wins) -- ShuffleChainVerifier's semantics.  A block whose pre trackers hold a point that does not decode gets status 2,
+    one with a pre point outside G1 status 3; a refused block gets zero bytes in both outputs (None on the list face), and it WRITES
+    NOTHING: later blocks are proved as if it were not there, but under their own index first_index + j.  So the output does not depend on
+    how a call is cut: prove_blocks(all) == prove_blocks(head) followed by prove_blocks(tail, first_index=first_index + len(head)).
+
+    seed=None draws secrets.token_bytes(32); the warning of ShuffleBatchProver.generate_packed about seeds holds here word for word.
+    ValueError (an index outside the set, a wrong count of indices, a closed prover or set) before anything runs, the set as it was.
+    NativeError: host bytes and device records are as they were before the call.
+
+    How (cg1_chain_prove_seeded, csrc/capi_chain_prove.h): the draws of all blocks first; the distinct slots the call reads are certified in
+    G1; a host pass (csrc/chain_lineage.h) names for every pre and post position its origin slot and the product of the k's on the way;
+    ONE launch (k_chain_lineage_mul) makes every tracker of every block; the proofs, independent now, run through the whole-shuffle chain
+    in groups of 64.  Calls of more than MAX_BLOCKS blocks go as further native calls; the cut invariance makes that free.  The device work
+    runs on the TABLE's context, which must sit on the set's device; one caller at a time."""
+
+    MAX_BLOCKS = N.WHISK_SHUFFLE_DRAWS_MAX_PROVERS
+
+    def __init__(self, crs, tracker_set: TrackerSet, table=None):
+        from .shuffle_prover import ShuffleBatchProver
+
+        self.set = tracker_set
+        self._prover = ShuffleBatchProver(crs, table=table)
+        self.crs, self.ell = crs, self._prover.ell
+        self.last_status: List[int] = []
+        self.last_refusals: list = []
+        self.last_stats: dict = {}
+
+    def close(self) -> None:
+        """Release the table when this prover made it.  The tracker set stays the caller's.  Idempotent."""
+        self._prover.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def prove_blocks(self, index_lists, seed: Optional[bytes] = None, first_index: int = 0):
+        ell = self.ell
+        index_lists = [[int(i) for i in block] for block in index_lists]
+        for block in index_lists:
+            if len(block) != ell:
+                raise ValueError(f"a block names {len(block)} slots, not {ell}")
+        post, proofs, status = self.prove_blocks_packed([i for block in index_lists for i in block], len(index_lists), seed, first_index)
+        wb = len(proofs) // max(1, len(status))
+        out = []
+        for j, st in enumerate(status):
+            rec = post[96 * ell * j: 96 * ell * (j + 1)]
+            out.append(None if st else (index_lists[j], [(rec[96 * i: 96 * i + 48], rec[96 * i + 48: 96 * i + 96]) for i in range(ell)], proofs[wb * j: wb * (j + 1)]))
+        return out
+
+    def prove_blocks_packed(self, indices, n: int, seed: Optional[bytes] = None, first_index: int = 0):
+        import secrets
+
+        import numpy as np
+
+        from .shuffle_prover import HALF_NAMES
+
+        ts, ell, table = self.set, self.ell, self._prover.table
+        if table is None:
+            raise ValueError("the prover is closed")
+        ts._check_open()
+        idx, n_idx = ts._indices(indices, ell)
+        if n_idx != n:
+            raise ValueError(f"prove_blocks_packed: expected n x ell = {n * ell} indices")
+        if seed is None:
+            seed = secrets.token_bytes(32)
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        if isinstance(first_index, bool) or not isinstance(first_index, int) or first_index < 0 or first_index + n > 1 << 32:
+            raise ValueError("first_index: an int with first_index + the number of blocks <= 2^32")
+        self.last_status, self.last_refusals = [], []
+        self.last_stats = {"stage_ms": 0.0, "certified_slots": 0, "chain_ms": 0.0, "call_ms": 0.0, "native_calls": 0}
+        if n == 0:
+            return b"", b"", []
+        wb = int(N.cg1_whisk_shuffle_proof_bytes(ell))
+        posts, proofs, status, refusals = [], [], [], []
+        stats = dict(self.last_stats)
+        before = ts.packed()
+        try:
+            with table._ctx_lock():
+                if table._KIND != "fixed-base":
+                    raise TypeError("the device pipeline of a shuffle proof runs over a FixedBaseTable")
+                cx = table._ctx
+                if int(N.cg1_ctx_device(cx.handle)) != int(N.cg1_ctx_device(ts.ctx.handle)):
+                    raise ValueError("the table and the tracker set sit on different devices")
+                gi, hi, ui, gti, gui, gth = self._prover._crs_args()
+                g_arr, h_arr = (ctypes.c_uint32 * ell)(*gi), (ctypes.c_uint32 * 4)(*hi)
+                ts.ctx.check(N.cg1_stream_sync(ts.ctx.handle))                # whatever the set's own stream still holds, before another stream touches it
+                for lo in range(0, n, self.MAX_BLOCKS):
+                    m = min(self.MAX_BLOCKS, n - lo)
+                    post, out = ctypes.create_string_buffer(96 * ell * m), ctypes.create_string_buffer(wb * m)
+                    st, at = (ctypes.c_int32 * m)(), (ctypes.c_uint32 * m)()
+                    writers = np.empty((min(ts.n_slots, m * ell), 2), dtype="<u4")
+                    nw, fl = ctypes.c_size_t(0), (ctypes.c_float * 4)()
+                    cx.check(N.cg1_chain_prove_seeded(cx.handle, table._tab.handle, ell, m, g_arr, h_arr, ui, gti, gui, gth, ts.d_pts.ptr, ts.d_pstat.ptr, ts.n_slots,
+                                                      idx[lo * ell:].ctypes.data, seed, first_index + lo, post, out, st, at, writers.ctypes.data, ctypes.byref(nw), fl))
+                    ts._apply_writers(writers[: nw.value], post.raw)
+                    posts.append(post.raw[: 96 * ell * m]); proofs.append(out.raw[: wb * m]); status += list(st)
+                    refusals += [(a >> 1, HALF_NAMES[a & 1]) if s else None for s, a in zip(st, at)]
+                    stats["stage_ms"] += float(fl[0]); stats["certified_slots"] += int(fl[1]); stats["chain_ms"] += float(fl[2]); stats["call_ms"] += float(fl[3])
+                    stats["native_calls"] += 1
+        except BaseException:
+            ts._restore(before)
+            raise
+        self.last_status, self.last_refusals, self.last_stats = status, refusals, stats
+        return b"".join(posts), b"".join(proofs), list(status)

@@ -1038,6 +1038,38 @@ int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, siz
                                    const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* trackers96, const uint8_t* seed32,
                                    uint64_t first_index, uint8_t* out_post96, uint8_t* out_proofs, int32_t* out_status /* n_provers */, uint32_t* out_bad_at /* n_provers */);
 
+/* ---- A chain of Whisk shuffles PROVED over the resident tracker set (the set: cg1_chain_expand above; shuffle_chain.py).  Block j, in order,
+ * reads pre_j = [set[i] for i in indices_j] before any of its own writes and, unless refused, writes set[indices_j[t]] = k_j * pre_j[perm_j[t]],
+ * t = 0 .. ell - 1 in order (a repeated index: the last write wins).  A block is refused -- it writes nothing, its outputs are zeros, later
+ * blocks read what was there -- when a pre point does not decode (CG1_WHISK_SHUFFLE_NO_DECODE) or lies outside G1 (CG1_WHISK_SHUFFLE_NOT_G1);
+ * out_bad_at is tracker 2 + half of the first such point in cg1_whisk_shuffle_prove_seeded's order.
+ * cg1_chain_lineage (host, no point arithmetic): point_status = 2 n_slots bytes (r_G of slot s at 2 s, k_r_G at 2 s + 1; 0, _NO_DECODE or
+ *   _NOT_G1; only slots read at first touch are looked at).  The current value of a slot is composite * (the tracker its ORIGIN slot held
+ *   before the call).  out_origin: [n_blocks][2][ell] origin slots, pre position t at [b][0][t], post position t at [b][1][t] (0xffffffff in
+ *   a refused block); out_scalar32: the composites (products of the k's, mod r) in the same layout, canonical (zeros in a refused block);
+ *   out_writers / out_n_writers as cg1_chain_expand's.  Every output may be NULL.  Refused before anything is written: CG1_ERR_ARG for
+ *   ell = 0, an index >= n_slots, a perm row that is no permutation of 0 .. ell - 1, another point_status value; CG1_ERR_ENCODING for k >= r.
+ * cg1_chain_evolve_device: the tracker stage on the context's stream -- the distinct slots read are certified (k_subgroup_row over their
+ *   records, the first wait), the lineage, ONE k_chain_lineage_mul launch (csrc/kernels_chain_prove.h) for every pre and post point, the last
+ *   writers' records scattered into the set with zero status bytes, the second wait.  out_post96: n_blocks x ell x (T48 | U48).
+ *   out_stats (NULL or 2 floats): the stage's milliseconds between two events, the number of slots certified.  cg1_chain_lineage's refusals,
+ *   with a text, before anything runs.  The composites' device field is zeroed and their host staging wiped before it returns.
+ * cg1_chain_prove_seeded: block j's draws are those of shuffle first_index + j of cg1_whisk_shuffle_prove_seeded, and its post bytes, M || proof
+ *   and status are what that entry gives for pre_j: the draws of all blocks (kept in wiped host staging), the tracker stage, then the surviving
+ *   blocks through cg1_shuffle_prove_device in groups of CG1_SAME_MSM_MAX_PROVERS.  g_index (ell), h_index (4), u / gt / gu_index: the CRS in the
+ *   table, once.  n_blocks <= CG1_WHISK_SHUFFLE_DRAWS_MAX_PROVERS.  out_stats (NULL or 4 floats): also the wall milliseconds inside
+ *   cg1_shuffle_prove_device and of the whole call.  Secret hygiene as cg1_whisk_shuffle_prove_seeded's.
+ * Neither device entry restores the set's records when it fails after the scatter: the caller, who holds the bytes, decodes them afresh. */
+int cg1_chain_lineage(size_t n_slots, const uint8_t* point_status, const uint32_t* indices, const uint32_t* perm, const uint8_t* k32, size_t n_blocks, size_t ell,
+                      int32_t* out_status, uint32_t* out_bad_at, uint32_t* out_origin, uint8_t* out_scalar32, uint32_t* out_writers, size_t* out_n_writers);
+int cg1_chain_evolve_device(cg1_ctx* ctx, void* d_set_pts96, void* d_set_pstat, size_t n_slots, const uint32_t* indices, const uint32_t* perm, const uint8_t* k32,
+                            size_t n_blocks, size_t ell, uint8_t* out_post96, int32_t* out_status, uint32_t* out_bad_at, uint32_t* out_writers, size_t* out_n_writers,
+                            float* out_stats);
+int cg1_chain_prove_seeded(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_blocks, const uint32_t* g_index, const uint32_t* h_index, uint32_t u_index, uint32_t gt_index,
+                           uint32_t gu_index, const uint8_t* gth_affine96, void* d_set_pts96, void* d_set_pstat, size_t n_slots, const uint32_t* indices,
+                           const uint8_t* seed32, uint64_t first_index, uint8_t* out_post96, uint8_t* out_proofs, int32_t* out_status, uint32_t* out_bad_at,
+                           uint32_t* out_writers, size_t* out_n_writers, float* out_stats);
+
 /* The tracker scan: which trackers does a set of Whisk secrets open?  For n_trackers trackers (r_G48 | k_r_G48, cg1_opening_prove's layout)
  * and n_ks secrets (scalar32), bit (i, j) = [ k_j * point_projective_from_bytes(r_G_i) == point_projective_from_bytes(k_r_G_i) ]
  * (util.py:35-36: unchecked decoding, a point outside G1 is legal and multiplied exactly; the relation opening.py proves).
