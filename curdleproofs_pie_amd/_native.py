@@ -19,6 +19,24 @@ PHASE_NAMES = ("prepare", "sort_count", "sort_scatter", "chunks", "accumulate", 
 
 OK, ERR_ARG, ERR_HIP, ERR_ENCODING, ERR_NOT_ON_CURVE, ERR_NOT_IN_SUBGROUP, ERR_COMM = range(7)
 
+# cg1_get_last_tail's bit fields (csrc/host_context.h: TAIL_*), as names
+TAIL_FOLD = (None, "k_bucket_fold_quad", "k_bucket_fold")
+TAIL_ROWCOL = (None, "k_rowcol_quad_row", "k_rowcol_quad", "k_rowcol", "k_seg_reduce")
+TAIL_TREE = (None, "k_small_tree_row", "k_small_tree_quad", "k_small_tree")
+TAIL_EXPORT = (None, "k_small_tree_row", "k_export_host", "hipMemcpyAsync")
+TAIL_HORNER = (None, "host", "k_msm_horner_row", "k_msm_horner_quad", "k_msm_horner")
+
+
+def decode_tail(word: int) -> dict:
+    """cg1_get_last_tail's word -> {"fold", "rowcol", "lgq", "rowcol_use_quad", "seg_m", "tree", "tree_waves", "export", "horner",
+    "horner_threads", "small_row_tail"}: kernel names (None: that stage launched nothing), numbers (0 where they do not apply) and, for
+    "small_row_tail", None unless k_msm_small served the call."""
+    f = lambda shift, bits: (word >> shift) & ((1 << bits) - 1)
+    small = f(29, 2)
+    return {"fold": TAIL_FOLD[f(0, 2)], "rowcol": TAIL_ROWCOL[f(2, 3)], "lgq": f(5, 3), "rowcol_use_quad": f(8, 1), "seg_m": f(9, 5),
+            "tree": TAIL_TREE[f(14, 2)], "tree_waves": f(16, 5), "export": TAIL_EXPORT[f(21, 2)], "horner": TAIL_HORNER[f(23, 3)],
+            "horner_threads": f(26, 3), "small_row_tail": small - 1 if small else None}
+
 
 class NativeError(RuntimeError):
     """HIP / argument failure inside libcurdle_g1.so (never silently replaced by a CPU path)."""
@@ -155,6 +173,7 @@ cg1_msm_batched = _proto("cg1_msm_batched", c_int, c_void_p, _u8p, _u8p, POINTER
 cg1_get_timings = _proto("cg1_get_timings", c_int, c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_int))
 cg1_get_host_timings = _proto("cg1_get_host_timings", c_int, c_void_p, POINTER(c_float))
 cg1_get_last_counts = _proto("cg1_get_last_counts", c_int, c_void_p, POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32))
+cg1_get_last_tail = _proto("cg1_get_last_tail", ctypes.c_uint32, c_void_p)
 cg1_get_last_launches = _proto("cg1_get_last_launches", c_int, c_void_p)
 cg1_plan_describe = _proto("cg1_plan_describe", c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int)
 cg1_timer_begin = _proto("cg1_timer_begin", c_int, c_void_p)
@@ -366,7 +385,7 @@ EXPORTED_SYMBOLS = [
     "cg1_is_identity", "cg1_compress", "cg1_decompress", "cg1_to_affine96", "cg1_from_affine96",
     "cg1_batch_to_affine96", "cg1_batch_decompress", "cg1_batch_compress", "cg1_device_count", "cg1_ctx_create",
     "cg1_ctx_destroy", "cg1_ctx_error", "cg1_dev_malloc", "cg1_dev_free", "cg1_h2d", "cg1_d2h", "cg1_d2h_2d", "cg1_h2d_async", "cg1_copy_fence", "cg1_stream_sync", "cg1_batch_decompress_enqueue", "cg1_host_alloc", "cg1_host_free", "cg1_ctx_sync", "cg1_ctx_set_param",
-    "cg1_msm", "cg1_msm_device", "cg1_msm_device_begin", "cg1_msm_device_end", "cg1_msm_batched_device", "cg1_msm_batched", "cg1_get_timings", "cg1_get_host_timings", "cg1_get_last_counts", "cg1_timer_begin", "cg1_timer_end", "cg1_batch_mul_device", "cg1_batch_mul_add_device", "cg1_batch_mul_add", "cg1_batch_mul_add_pool", "cg1_batch_decompress_device", "cg1_batch_compress_device", "cg1_batch_decompress_gpu", "cg1_gen_scalars_device", "cg1_probe_madd",
+    "cg1_msm", "cg1_msm_device", "cg1_msm_device_begin", "cg1_msm_device_end", "cg1_msm_batched_device", "cg1_msm_batched", "cg1_get_timings", "cg1_get_host_timings", "cg1_get_last_counts", "cg1_get_last_tail", "cg1_timer_begin", "cg1_timer_end", "cg1_batch_mul_device", "cg1_batch_mul_add_device", "cg1_batch_mul_add", "cg1_batch_mul_add_pool", "cg1_batch_decompress_device", "cg1_batch_compress_device", "cg1_batch_decompress_gpu", "cg1_gen_scalars_device", "cg1_probe_madd",
     "cg1_ctx_create_cu_mask", "cg1_shuffle_fe_create", "cg1_shuffle_fe_destroy", "cg1_shuffle_fe_aux_bytes", "cg1_shuffle_gather_aux", "cg1_shuffle_fe_enqueue", "cg1_shuffle_fe_nodes", "cg1_shuffle_fe_last_passes", "cg1_shuffle_fe_last_split", "cg1_shuffle_fe_program_shape", "cg1_shuffle_fe_emulate_to_first_barrier",
     "cg1_merlin_last_passes", "cg1_merlin_last_kernel", "cg1_merlin_block_program_emulate", "cg1_merlin_group_run", "cg1_probe_mad_rate", "cg1_batch_sum_device", "cg1_batch_sum", "cg1_ctx_device", "cg1_ctx_stream", "cg1_msm_multi_device",
     "cg1_comm_create", "cg1_comm_port", "cg1_comm_rank", "cg1_comm_connect", "cg1_comm_set_timeout", "cg1_comm_attach_rccl", "cg1_comm_transport",
@@ -759,6 +778,11 @@ class Context:
         cg1_get_last_counts(self.handle, ctypes.byref(e), ctypes.byref(c))
         return {"entries": int(e.value), "chunks": int(c.value), "mixed_adds": int(e.value) - int(c.value),
                 "accumulate_launches": int(cg1_get_last_launches(self.handle))}
+
+    def last_tail(self) -> dict:
+        """Which reduction-tail kernels the last MSM call launched (cg1_get_last_tail), by name; None / 0 where a stage did not run.
+        For the tests: nothing in the product reads it."""
+        return decode_tail(int(cg1_get_last_tail(self.handle)))
 
     def timer_begin(self) -> None:
         self.check(cg1_timer_begin(self.handle))

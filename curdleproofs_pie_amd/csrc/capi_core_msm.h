@@ -374,6 +374,9 @@ int cg1_msm_device_end(cg1_ctx* ctx, uint8_t* out) {
   return rc;
 }
 
+// Which reduction-tail kernels the last MSM call on this context launched (host_context.h: the TAIL_* bit fields).  For the tests.
+uint32_t cg1_get_last_tail(const cg1_ctx* ctx) { return ctx ? ctx->last_tail : 0u; }
+
 // One MSM over several GPUs of THIS process: context i owns point shard i on its own device.  Every launch chain is enqueued
 // before any is waited for, so the devices work concurrently; the partials are added in context order.
 int cg1_msm_multi_device(cg1_ctx* const* ctxs, size_t n_ctx, const void* const* d_points, const void* const* d_scalars, const size_t* n,

@@ -113,6 +113,7 @@ struct ChainHooks {
 static int msm_enqueue(Ctx* ctx, const PtSrc& src, const void* d_scalars32, size_t n, const WinPlan& plan, int rank, int world,
                        const ChainHooks& hooks = ChainHooks()) {
   ctx->pend.active = false;
+  ctx->last_tail = 0;
   HIPCHK(hipSetDevice(ctx->device));
   const int c = plan.cmax, nwin = plan.nwin;
   // an endomorphism-split call (plan.glv) runs over 2n records -- P_i, then phi(P_i) -- and 2n rows of digits; everything behind the digit
@@ -240,17 +241,22 @@ static int msm_enqueue(Ctx* ctx, const PtSrc& src, const void* d_scalars32, size
   hipLaunchKernelGGL(k_heavy_combine, dim3(512), dim3(256), 0, st, ctx->d_heavy, (uint32_t)ctx->cap_heavy, ctx->d_choff, ctx->d_sums, ctx->d_combined);
   // k_rowcol_quad (every addition by a DPP quad) only where the reduction is a pure latency chain: a few thousand buckets
   const bool small_quad = ctx->quad && ctx->rowcol_quad && nb_total <= (size_t)ctx->rowcol_quad_max;
-  // Buckets cut into 2..16 chunks are folded into their first slot before the row / column sums (k_rowcol_quad requires it;
+  // Buckets cut into 2..16 chunks are folded into their first slot before the row / column sums (k_rowcol_quad requires it, so with it
+  // as the consumer a fold is launched whatever "fold_quad" and "fold_pass" say;
   // k_rowcol / k_seg_reduce could add the chunk sums themselves -- bucket_sum -- but the divergent trip counts inside their lanes
   // cost more than the separate pass: profiles/r03_rowcol_ab.txt).
   // k_rowcol_quad_row can add a bucket's chunk sums itself: worth it only for a few thousand buckets (2^12 terms 0.354 -> 0.336 ms; at 2^15 -
   // 2^16 the uneven trip counts of a wave's quads cost more than the separate pass: 0.605 -> 0.657, profiles/r05_tree_row_ab.txt)
   const bool rows_fold = small_quad && use2d && ctx->rowcol_row && ctx->tree_row && nb_total <= 8192;
   if (rows_fold) {}
-  else if (small_quad && ctx->fold_quad)
+  else if (small_quad && ctx->fold_quad) {
     hipLaunchKernelGGL(k_bucket_fold_quad, dim3((uint32_t)((nb_total * 4 + 255) / 256)), dim3(256), 0, st, ctx->d_choff, ctx->d_sums, ctx->d_combined, (uint32_t)nb_total, ctx->d_any_multi);
-  else if (ctx->fold_pass)
+    ctx->last_tail |= 1u << TAIL_FOLD;
+  }
+  else if (ctx->fold_pass || (small_quad && use2d && !(ctx->rowcol_row && ctx->tree_row))) {      // (k_rowcol_quad has no bucket_sum loop: "fold_pass" = 0 cannot apply to it)
     hipLaunchKernelGGL(k_bucket_fold, dim3((uint32_t)((nb_total + 255) / 256)), dim3(256), 0, st, ctx->d_choff, ctx->d_sums, ctx->d_combined, (uint32_t)nb_total, ctx->d_any_multi);
+    ctx->last_tail |= 2u << TAIL_FOLD;
+  }
   bool tree_exports = false;
   if (use2d) {
     const uint32_t R = 1u << hb2, Cn = 1u << lb2;
@@ -273,10 +279,13 @@ static int msm_enqueue(Ctx* ctx, const PtSrc& src, const void* d_scalars32, size
       else
       hipLaunchKernelGGL(k_rowcol_quad, dim3((rc_waves + 3u) / 4u), dim3(256), 0, st, ctx->d_choff, ctx->d_sums,
                          rowsum, colsum, (uint32_t)nlw, hb2, lb2, lgq);
+      ctx->last_tail |= (ctx->rowcol_row && ctx->tree_row) ? 1u << TAIL_ROWCOL : (2u << TAIL_ROWCOL) | (lgq << TAIL_LGQ);
     }
-    else
+    else {
       hipLaunchKernelGGL(k_rowcol, dim3(nrow_blocks + ncol_blocks), dim3(256), 0, st, ctx->d_choff, ctx->d_sums, ctx->d_combined,
                          rowsum, colsum, (uint32_t)nlw, hb2, lb2, nrow_blocks, ctx->quad);
+      ctx->last_tail |= (3u << TAIL_ROWCOL) | ((ctx->quad ? 1u : 0u) << TAIL_RCQUAD);
+    }
     if (profile >= 2) HIPCHK(hipEventRecord(ctx->ev[6], st));
     // 4 lanes per element of the longer of the two sums (2^hb rows, 2^lb columns), at most 512 threads: no idle quads in the block
     const uint32_t tree_threads = std::min<uint32_t>(512u, std::max<uint32_t>(64u, 4u << std::max(hb2, lb2)) >> (ctx->tree_shift >= 0 ? ctx->tree_shift : (ctx->tree_half ? 1 : 0)));
@@ -288,12 +297,20 @@ static int msm_enqueue(Ctx* ctx, const PtSrc& src, const void* d_scalars32, size
       if (tree_exports) ++ctx->seq;
       hipLaunchKernelGGL(k_small_tree_row, dim3(nitems, nlw), dim3(64u * W), 0, st, rowsum, colsum, ctx->d_out, hb2, lb2,
                          tree_exports ? ctx->h_out_dev : (PointWords*)nullptr, bad_flag, ctx->h_flag_dev, ctx->seq);
+      ctx->last_tail |= (1u << TAIL_TREE) | (W << TAIL_WAVES);
     }
-    else if (ctx->quad) hipLaunchKernelGGL(k_small_tree_quad, dim3(nitems, nlw), dim3(std::max<uint32_t>(64u, tree_threads)), 0, st, rowsum, colsum, ctx->d_out, hb2, lb2);
-    else hipLaunchKernelGGL(k_small_tree, dim3(nitems, nlw), dim3(256), 0, st, rowsum, colsum, ctx->d_out, hb2, lb2);
+    else if (ctx->quad) {
+      hipLaunchKernelGGL(k_small_tree_quad, dim3(nitems, nlw), dim3(std::max<uint32_t>(64u, tree_threads)), 0, st, rowsum, colsum, ctx->d_out, hb2, lb2);
+      ctx->last_tail |= (2u << TAIL_TREE) | ((std::max<uint32_t>(64u, tree_threads) >> 6) << TAIL_WAVES);
+    }
+    else {
+      hipLaunchKernelGGL(k_small_tree, dim3(nitems, nlw), dim3(256), 0, st, rowsum, colsum, ctx->d_out, hb2, lb2);
+      ctx->last_tail |= (3u << TAIL_TREE) | (4u << TAIL_WAVES);
+    }
   } else {
     const uint32_t nseg_total = (uint32_t)(nb_total / m);
     hipLaunchKernelGGL(k_seg_reduce, dim3((nseg_total + 255) / 256), dim3(256), 0, st, ctx->d_choff, ctx->d_sums, ctx->d_combined, ctx->d_segrun, ctx->d_segtot, nseg_total, m);
+    ctx->last_tail |= (4u << TAIL_ROWCOL) | (m << TAIL_SEGM);
     if (profile >= 2) HIPCHK(hipEventRecord(ctx->ev[6], st));
     uint32_t S = (J + BT_ELEMS - 1) / BT_ELEMS; if (S < 1) S = 1; if (S > 64) S = 64;   // J <= 2^15 / seg_m
     hipLaunchKernelGGL(k_bit_tree, dim3(nitems, nlw, S), dim3(256), 0, st, ctx->d_segrun, ctx->d_segtot, ctx->d_partial, J);
@@ -302,6 +319,7 @@ static int msm_enqueue(Ctx* ctx, const PtSrc& src, const void* d_scalars32, size
   const bool zc = ctx->zero_copy != 0;
   if (zc && tree_exports) {
     // (k_small_tree_row has written the records, the status words and the flag)
+    ctx->last_tail |= 1u << TAIL_EXPORT;
   } else if (zc) {
     // the window sums + status words go straight into mapped host memory, then the call's sequence number into the flag word the
     // host polls: no DMA copy to set up, no stream wait to wake from (~25 us per call, all of it on the critical path of a small MSM)
@@ -309,8 +327,10 @@ static int msm_enqueue(Ctx* ctx, const PtSrc& src, const void* d_scalars32, size
     const uint32_t nvec = (uint32_t)((((size_t)nlw * nitems + 1) * sizeof(PointWords)) / 16);
     hipLaunchKernelGGL(k_export_host, dim3(1), dim3(1024), 0, st, reinterpret_cast<const uint4*>(ctx->d_out), reinterpret_cast<uint4*>(ctx->h_out_dev), nvec,
                        ctx->h_flag_dev, ctx->seq);
+    ctx->last_tail |= 2u << TAIL_EXPORT;
   } else {
     HIPCHK(hipMemcpyAsync(ctx->h_out, ctx->d_out, ((size_t)nlw * nitems + 1) * sizeof(PointWords), hipMemcpyDeviceToHost, st));
+    ctx->last_tail |= 3u << TAIL_EXPORT;
   }
   if (profile >= 2) HIPCHK(hipEventRecord(ctx->ev[7], st));
   auto h1 = std::chrono::steady_clock::now();
@@ -406,6 +426,7 @@ static int msm_finish(Ctx* ctx, cg1h::jac& result) {
   };
   cg1h::jac acc;
   const int nth = (!ctx->host_split || e_top < 96) ? 1 : (ctx->horner_threads >= 4 && e_top >= 112 ? 4 : 2);      // (112: the 128-position plans of the endomorphism split)
+  ctx->last_tail = (ctx->last_tail & ~((7u << TAIL_HORNER) | (7u << TAIL_NTH))) | (1u << TAIL_HORNER) | ((uint32_t)nth << TAIL_NTH);
   if (nth > 1) {
     // the exponent range cut into nth parts: part j (on its own thread) forms horner(lo_j, hi_j) and then doubles it lo_j times, so
     // every part ends with its full weight and the parts are simply added.  The critical path is the top part: e_top doublings,
@@ -500,6 +521,7 @@ static int msm_enqueue_small(Ctx* ctx, const PtSrc& src, const void* d_scalars32
   a.partial = ctx->d_small_partial; a.counters = ctx->d_small_ctr;
   a.out_host = ctx->h_small_out_dev; a.flag_host = ctx->h_flag_dev; a.seq = ++ctx->seq;
   a.row_tail = ctx->small_row_tail ? 1u : 0u;
+  ctx->last_tail = (a.row_tail ? 2u : 1u) << TAIL_SMALL;
   a.glv = glv ? 1u : 0u;
   int kind = (int)src.kind;
   if (src.kind == PtSrc::BLOBS && !src.normalised) {           // invert first (one lane per point), then run on the prepared records
@@ -585,6 +607,7 @@ static int msm_small_batched_finish(Ctx* ctx, uint32_t M, std::vector<cg1h::jac>
     Pool& pool = Pool::get();
     pool.run(work, std::min<size_t>(M, pool.size() + 1));
   }
+  ctx->last_tail = (ctx->last_tail & ~((7u << TAIL_HORNER) | (7u << TAIL_NTH))) | (1u << TAIL_HORNER) | ((M <= 4 ? M : 0u) << TAIL_NTH);
   auto t1 = std::chrono::steady_clock::now();
   ctx->host_ms[0] = std::chrono::duration<float, std::milli>(pd.h1 - pd.h0).count();
   ctx->host_ms[1] = std::chrono::duration<float, std::milli>(t0 - pd.h1).count();
@@ -607,7 +630,7 @@ static int msm_begin_split(Ctx* ctx, const PtSrc& src, const void* d_scalars32, 
 int msm_begin(Ctx* ctx, const PtSrc& src, const void* d_scalars32, size_t n, int c, int rank, int world) {
   ctx->pend.active = false;
   ctx->pend_c = 0;
-  ctx->last_entries = ctx->last_chunks = 0;          // a call that enqueues nothing (no terms, a shard without a window) sorted nothing
+  ctx->last_entries = ctx->last_chunks = 0; ctx->last_tail = 0;          // a call that enqueues nothing (no terms, a shard without a window) sorted nothing
   if (n == 0) return CG1_OK;
   if (n >= (1ull << 31)) { snprintf(ctx->err, sizeof ctx->err, "n too large"); return CG1_ERR_ARG; }
   if (world < 1 || world > 255 || rank < 0 || rank >= world) { snprintf(ctx->err, sizeof ctx->err, "bad window shard %d/%d", rank, world); return CG1_ERR_ARG; }
@@ -752,18 +775,21 @@ static int batched_chain_enqueue(Ctx* ctx, const void* d_points96, const void* d
   const uint32_t nseg_total = (uint32_t)(nb_total / m);
   hipLaunchKernelGGL(k_heavy_combine, dim3(512), dim3(256), 0, st, ctx->d_heavy, (uint32_t)ctx->cap_heavy, ctx->d_choff, ctx->d_sums, ctx->d_combined);
   hipLaunchKernelGGL(k_seg_reduce, dim3((nseg_total + 255) / 256), dim3(256), 0, st, ctx->d_choff, ctx->d_sums, ctx->d_combined, ctx->d_segrun, ctx->d_segtot, nseg_total, m);
+  ctx->last_tail = (4u << TAIL_ROWCOL) | (m << TAIL_SEGM) | (3u << TAIL_EXPORT);
   hipLaunchKernelGGL(k_group_reduce, dim3((uint32_t)((G + 255) / 256)), dim3(256), 0, st, ctx->d_segrun, ctx->d_segtot, ctx->d_gsum, (uint32_t)G, J, log2m);
   if (ctx->profile >= 2) HIPCHK(hipEventRecord(ctx->ev[6], st));
   if (host_horner) {
     hipLaunchKernelGGL(k_export_sums, dim3((uint32_t)((G + 63) / 64)), dim3(64), 0, st, ctx->d_gsum, ctx->d_gout, (uint32_t)G);
     HIPCHK(hipMemcpyAsync(ctx->h_gout, ctx->d_gout, G * sizeof(PointWords), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(ctx->h_bout + M, ctx->d_bout + M, sizeof(PointWords), hipMemcpyDeviceToHost, st));      // the status words
+    ctx->last_tail |= (1u << TAIL_HORNER) | ((uint32_t)std::min<size_t>(4, M) << TAIL_NTH);      // (batched_chain_finish: up to four host threads)
   } else {
     // up to ~2 000 MSMs one WAVE each, one limb per lane (fp_row.h: a lone wave's doubling in ~1.5 us instead of a quad's ~5); beyond,
     // a wave per MSM would be eight and more to a SIMD and the quads' throughput wins (profiles/r05_rowlane_ab.txt)
     if (ctx->horner_row && M <= 2048) hipLaunchKernelGGL(k_msm_horner_row, dim3((uint32_t)M), dim3(64), 0, st, ctx->d_gsum, ctx->d_bout, (uint32_t)M, nwin, (uint32_t)c);
     else if (ctx->quad) hipLaunchKernelGGL(k_msm_horner_quad, dim3((uint32_t)((M * 4 + 63) / 64)), dim3(64), 0, st, ctx->d_gsum, ctx->d_bout, (uint32_t)M, nwin, (uint32_t)c);
     else hipLaunchKernelGGL(k_msm_horner, dim3((uint32_t)((M + 63) / 64)), dim3(64), 0, st, ctx->d_gsum, ctx->d_bout, (uint32_t)M, nwin, (uint32_t)c);
+    ctx->last_tail |= ((ctx->horner_row && M <= 2048) ? 2u : (ctx->quad ? 3u : 4u)) << TAIL_HORNER;
     HIPCHK(hipMemcpyAsync(ctx->h_bout, ctx->d_bout, (M + 1) * sizeof(PointWords), hipMemcpyDeviceToHost, st));
   }
   if (ctx->profile >= 2) HIPCHK(hipEventRecord(ctx->ev[7], st));

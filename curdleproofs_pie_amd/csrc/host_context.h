@@ -221,12 +221,30 @@ struct Ctx {
   float host_ms[4] = {0, 0, 0, 0};      // enqueue, wait-for-GPU, event readout, Horner tail
   int profile = 1;                      // 0: no hipEvents; 1: around k_accumulate only; 2: around every phase (read_phase_events)
   uint32_t last_chunks = 0, last_entries = 0;   // of the last MSM call: non-zero digits sorted into buckets; chunks k_accumulate ran
+  uint32_t last_tail = 0;               // of the last MSM call: which reduction-tail kernels were launched (TAIL_* below; for the tests, cg1_get_last_tail)
   hipEvent_t tm_ev[2] = {nullptr, nullptr};     // cg1_timer_begin / cg1_timer_end
   int last_c = 0, pend_c = 0;
   int chunk_rule = 1;                   // "chunk_rule": whole-bucket chunks at 2^17 .. 2^19 terms (A/B switch)
   uint32_t L0 = 8;                      // MINIMUM chunk length; the per-call length grows with the entry count
   uint32_t seg_m = 4;
 };
+
+// Ctx::last_tail: which leaves of the reduction tail the last call launched, as bit fields.  Plain host stores beside the launches
+// (msm_enqueue, msm_finish, msm_enqueue_small, batched_chain_enqueue); nothing reads it but cg1_get_last_tail, which exists for the tests
+// (tests/msm_tail_cases.py restates the decision and compares).
+//   fold    bits 0-1    0 none launched, 1 k_bucket_fold_quad, 2 k_bucket_fold
+//   rowcol  bits 2-4    1 k_rowcol_quad_row, 2 k_rowcol_quad, 3 k_rowcol, 4 k_seg_reduce (regime A: + k_bit_tree, k_bit_tree_final; regime B: + k_group_reduce)
+//   lgq     bits 5-7    k_rowcol_quad's lgq
+//   rcquad  bit 8       k_rowcol's use_quad
+//   seg_m   bits 9-13   k_seg_reduce's segment length
+//   tree    bits 14-15  1 k_small_tree_row, 2 k_small_tree_quad, 3 k_small_tree
+//   waves   bits 16-20  waves of the tree kernel's block
+//   export  bits 21-22  1 k_small_tree_row wrote the mapped host records, 2 k_export_host, 3 hipMemcpyAsync
+//   horner  bits 23-25  1 host, 2 k_msm_horner_row, 3 k_msm_horner_quad, 4 k_msm_horner
+//   nth     bits 26-28  threads of the host Horner (0: the process's worker pool)
+//   small   bits 29-30  1 k_msm_small with row_tail = 0, 2 with row_tail = 1
+constexpr uint32_t TAIL_FOLD = 0, TAIL_ROWCOL = 2, TAIL_LGQ = 5, TAIL_RCQUAD = 8, TAIL_SEGM = 9, TAIL_TREE = 14, TAIL_WAVES = 16, TAIL_EXPORT = 21,
+                   TAIL_HORNER = 23, TAIL_NTH = 26, TAIL_SMALL = 29;
 
 // ------------------------------------------------------------------ kept buffers: one way to grow them, one way to release them
 // A buffer a handle keeps between calls: where its pointer lives, the bytes a growth allocates, and for page-locked host memory the

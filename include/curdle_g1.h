@@ -170,6 +170,14 @@ int cg1_get_timings(const cg1_ctx* ctx, float phase_ms[CG1_NPHASE], float* host_
 /* work counts of the last MSM call: non-zero signed digits sorted into buckets (= bucket additions + first-entry copies)
  * and the chunks k_accumulate ran (one copy each), so  mixed additions = entries - chunks */
 int cg1_get_last_counts(const cg1_ctx* ctx, uint32_t* entries, uint32_t* chunks);
+/* Which kernels of the reduction tail (everything behind k_accumulate) the last MSM call launched, as bit fields, low to high:
+ * fold (2 bits: 0 none, 1 k_bucket_fold_quad, 2 k_bucket_fold) | row / column sums (3: 1 k_rowcol_quad_row, 2 k_rowcol_quad, 3 k_rowcol,
+ * 4 k_seg_reduce) | k_rowcol_quad's lgq (3) | k_rowcol's use_quad (1) | k_seg_reduce's segment length (5) | tree (2: 1 k_small_tree_row,
+ * 2 k_small_tree_quad, 3 k_small_tree) | waves of the tree's block (5) | export (2: 1 by k_small_tree_row, 2 k_export_host,
+ * 3 hipMemcpyAsync) | Horner (3: 1 host, 2 k_msm_horner_row, 3 k_msm_horner_quad, 4 k_msm_horner) | host Horner threads (3; 0 = the worker
+ * pool) | k_msm_small (2: 1 row_tail = 0, 2 row_tail = 1).  Written by plain host stores next to the launches; it exists for the tests,
+ * which compare it with their own statement of the decision (tests/msm_tail_cases.py). */
+uint32_t cg1_get_last_tail(const cg1_ctx* ctx);
 /* k_accumulate launches of the last MSM call: 2 when it ran as two launch chains ("split"), 1, or 0 when k_msm_small served it */
 int cg1_get_last_launches(const cg1_ctx* ctx);
 /* The window plan of a width (window_c > 0: uniform; < 0: balanced with widths |c| and |c| - 1; glv: over the 128 positions of the halves of
