@@ -277,6 +277,12 @@ cg1_generator_mul_device = _proto("cg1_generator_mul_device", c_int, c_void_p, c
 cg1_tracker_match_device = _proto("cg1_tracker_match_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_tracker_match = _proto("cg1_tracker_match", c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p)
 cg1_tracker_match_last_ms = _proto("cg1_tracker_match_last_ms", c_int, c_void_p, c_void_p)
+# Whisk registrations in bulk (csrc/kernels_register.h): device path, host twin, the seed derivation, the five-multiple stage alone
+cg1_whisk_register_device = _proto("cg1_whisk_register_device", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p)
+cg1_whisk_register = _proto("cg1_whisk_register", c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+cg1_whisk_register_draws = _proto("cg1_whisk_register_draws", c_int, c_void_p, c_uint64, c_size_t, c_void_p, c_void_p)
+cg1_whisk_register_points_device = _proto("cg1_whisk_register_points_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int)
 # exact relations in bulk (csrc/kernels_exact.h): sum of (+-) k P == identity on all of E(Fp); index check, host twin, device launch, and
 # the opening proofs' challenges on the worker pool
 cg1_exact_relations_check = _proto("cg1_exact_relations_check", c_int, c_void_p, c_size_t, c_size_t, c_size_t)
@@ -403,6 +409,7 @@ EXPORTED_SYMBOLS = [
     "cg1_whisk_shuffle_proof_bytes", "cg1_whisk_shuffle_front", "cg1_whisk_shuffle_prove_device", "cg1_whisk_shuffle_front_emulate",
     "cg1_whisk_shuffle_draws_device", "cg1_whisk_shuffle_draws", "cg1_whisk_shuffle_prove_seeded",
     "cg1_tracker_match_device", "cg1_tracker_match", "cg1_tracker_match_last_ms",
+    "cg1_whisk_register_device", "cg1_whisk_register", "cg1_whisk_register_draws", "cg1_whisk_register_points_device",
     "cg1_exact_relations_check", "cg1_exact_relations", "cg1_exact_relations_device", "cg1_exact_gather_device", "cg1_opening_challenges",
     "cg1_chain_expand", "cg1_batch_decompress_strided_enqueue", "cg1_chain_gather_enqueue", "cg1_chain_scatter_enqueue",
     "cg1_chain_lineage", "cg1_chain_evolve_device", "cg1_chain_prove_seeded",

@@ -184,6 +184,7 @@ void cg1_ctx_destroy(cg1_ctx* ctx) {
   cg1::release_bufs(ctx->merlin_rows_cap, {cg1::dev_buf(ctx->d_merlin_rows)});
   cg1::release_bufs(ctx->cap_opening, {cg1::dev_buf(ctx->d_opening)});
   cg1::release_bufs(ctx->cap_prover, {cg1::dev_buf(ctx->d_prover)});
+  cg1::release_bufs(ctx->cap_register, {cg1::dev_buf(ctx->d_register)});
   cg1::release_bufs(ctx->cap_whisk_draws, {cg1::dev_buf(ctx->d_whisk_draws)});
   cg1::release_bufs(ctx->cap_chain_prove, {cg1::dev_buf(ctx->d_chain_prove)});
   cg1::release_bufs(ctx->cap_tscan_tab, {cg1::dev_buf(ctx->d_tscan_tab)});

@@ -128,6 +128,7 @@ struct Ctx {
   int tscan_ladder_max_ks = CG1_TRACKER_MATCH_LADDER_MAX_KS;      // "tracker_scan_ladder_max_ks": up to this many secrets a scan runs one ladder per pair (0: always the tables)
   int tscan_timing = 0; float tscan_ms[2] = {0.f, 0.f};           // "tracker_scan_timing": wait between the phases of a scan and keep build / match wall ms
   void* d_prover = nullptr; size_t cap_prover = 0;                // cg1_opening_prove_device's scratch (1 252 B per proof)
+  void* d_register = nullptr; size_t cap_register = 0;            // cg1_whisk_register_device's scratch (capi_register.h): a slice's columns and k_register_points' parking; the secret columns zeroed before every return
   void* d_whisk_draws = nullptr; size_t cap_whisk_draws = 0;      // the seeded draws of Whisk shuffles (capi_whisk_shuffle.h): swaps | perm | scalars; zeroed before every return
   void* d_chain_prove = nullptr; size_t cap_chain_prove = 0;      // the tracker stage of a proved chain (capi_chain_prove.h): certification, origins, composites (zeroed before every return), records
   PreparedPoint* d_gen_tab = nullptr;   // k_generator_mul's table of G (GEN_ENTRIES records), built at the first use (cg1_generator_mul_device)

@@ -33,6 +33,28 @@ __device__ __forceinline__ void compress_words(const uint32_t w[24], bool inf, u
   o[0] |= 0x80u | (is_large ? 0x20u : 0u);
 }
 
+// s * G for s below r (four little-endian 64-bit words): the recoding above and one mixed addition per non-zero digit.  Shared by
+// k_generator_mul and k_register_points (kernels_register.h).
+__device__ __forceinline__ xyzz generator_sum(const PreparedPoint* __restrict__ tab, const uint64_t s[4]) {
+  xyzz acc = xyzz_identity();
+  uint32_t carry = 0;
+#pragma unroll 1
+  for (int w = 0; w < GEN_WINDOWS; ++w) {
+    const int bit = w * GEN_C;
+    const uint32_t v = (uint32_t)(s[bit >> 6] >> (bit & 63)) & ((1u << GEN_C) - 1u);
+    const uint32_t u = v + carry;
+    carry = u > (uint32_t)GEN_HALF;
+    const uint32_t mag = carry ? (1u << GEN_C) - u : u;   // |d|; d < 0 when carry
+    if (!mag) continue;
+    fp x, y;
+    uint32_t fl;
+    load_affine(tab + (w * GEN_HALF + (mag - 1)), x, y, fl);
+    if (carry) y = fp_norm(fp_neg<3>(y));
+    acc = xyzz_madd(acc, x, y);
+  }
+  return acc;
+}
+
 // tab: GEN_ENTRIES prepared records, entry w * GEN_HALF + (d - 1) = d * 2^(c w) * G.  scalars: n x 32 bytes little-endian, any value
 // below 2^256.  out96 (affine std words, zeros = identity) and out48 (compressed) are each optional.
 __global__ void __launch_bounds__(256) k_generator_mul(const PreparedPoint* __restrict__ tab, const uint32_t* __restrict__ scalars, uint32_t n,
@@ -52,22 +74,7 @@ __global__ void __launch_bounds__(256) k_generator_mul(const PreparedPoint* __re
       s[k] = d;
     }
   }
-  xyzz acc = xyzz_identity();
-  uint32_t carry = 0;
-#pragma unroll 1
-  for (int w = 0; w < GEN_WINDOWS; ++w) {
-    const int bit = w * GEN_C;
-    const uint32_t v = (uint32_t)(s[bit >> 6] >> (bit & 63)) & ((1u << GEN_C) - 1u);
-    const uint32_t u = v + carry;
-    carry = u > (uint32_t)GEN_HALF;
-    const uint32_t mag = carry ? (1u << GEN_C) - u : u;   // |d|; d < 0 when carry
-    if (!mag) continue;
-    fp x, y;
-    uint32_t fl;
-    load_affine(tab + (w * GEN_HALF + (mag - 1)), x, y, fl);
-    if (carry) y = fp_norm(fp_neg<3>(y));
-    acc = xyzz_madd(acc, x, y);
-  }
+  const xyzz acc = generator_sum(tab, s);
   uint32_t o[24];
   for (int k = 0; k < 24; ++k) o[k] = 0;
   if (!acc.inf) {                                         // x = X/ZZ, y = Y/ZZZ with ONE inversion: 1/(ZZ*ZZZ)

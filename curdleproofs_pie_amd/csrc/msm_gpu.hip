@@ -75,6 +75,7 @@ int pick_window(size_t n);
 #include "kernels_merlin.h"
 #include "kernels_frontend.h"
 #include "kernels_opening.h"
+#include "kernels_register.h"      // k_register_scalars / k_register_points: Whisk registrations, five multiples of G per lane with one inversion
 #include "kernels_chain.h"         // the step skeleton of the device provers: lane-0 transcript, status merge, inversion, clocks
 #include "kernels_ipa.h"           // k_ipa_step: the inner-product argument's phases, op tables and Fr steps over that skeleton
 #include "kernels_same_msm.h"      // k_smsm_step: the same-MSM argument's
@@ -107,3 +108,4 @@ int pick_window(size_t n);
 #include "capi_tracker_set.h"     // a chain of shuffles over a resident tracker set: strided decoding, cg1_chain_gather_enqueue / _scatter_enqueue
 #include "capi_chain_prove.h"     // a chain of shuffles PROVED over the resident set: cg1_chain_evolve_device, cg1_chain_prove_seeded (host lineage: chain_lineage.h)
 #include "capi_tracker_scan.h"    // which trackers a set of secrets opens: cg1_tracker_match_device and its host twin cg1_tracker_match
+#include "capi_register.h"        // Whisk registrations in bulk: cg1_whisk_register_device, its host twin cg1_whisk_register, cg1_whisk_register_draws

@@ -1108,6 +1108,39 @@ int cg1_tracker_match(const uint8_t* trackers96 /* r_G | k_r_G */, size_t n_trac
                       uint64_t* out_bitmap, int32_t* out_tracker_status, int32_t* out_k_status);
 int cg1_tracker_match_last_ms(const cg1_ctx* ctx, float ms[2]);
 
+/* Whisk REGISTRATIONS made in bulk: per secret k the tracker (r_G48 | k_r_G48, generate_tracker, test_curdleproofs.py:759-790), the
+ * k_commitment k_G48 (get_k_commitment) and the opening proof A48 | B48 | s32 (GenerateWhiskTrackerProof, whisk_interface.py:177-190).
+ * The maker knows r, so all five points are multiples of the generator and come from the context's table of G with ONE inversion per
+ * item (csrc/kernels_register.h), with no square root and no doubling ladder:
+ *     r_G = r G    k_r_G = (k r mod r_order) G    k_G = k G    A = b G    B = (b r mod r_order) G
+ * then the "whisk_opening_proof" transcript over [k_G, G, k_r_G, r_G, A, B], the challenge c and s = b - c k (opening.py:42-56).
+ * With (r, b) supplied the bytes ARE the reference's when it draws that r and that b.  Item i of a call has the global index
+ * first_index + i < 2^32; its output depends on (k, r, b) -- or (k, seed, index) -- alone, not on its neighbours or on how a batch is cut.
+ *   rs32, blinders32   both given (n x scalar32 each) or both NULL.  NULL: r and b of an item are derived from seed32,
+ *                        block(index, d) = SHAKE256("whisk_registration_draw" || seed32 || le64(index) || le32(d)).digest(64)
+ *                        r = int.from_bytes(block(index, 0), "little") mod r_order,  b likewise with d = 1
+ *                      (cg1_whisk_register_draws is the host's copy).  A seed that is reused or known to anyone else reveals every k it
+ *                      was used with (k = (b - s) / c): 32 fresh bytes from the OS per call, a fixed one only in tests.
+ *   status[i]          0 made; CG1_SHUFFLE_BAD_SCALAR: k >= r_order; CG1_OPENING_BAD_BLINDER: an r or b, supplied or derived, that is zero
+ *                      or >= r_order.  k = 0 is legal (k_r_G and k_G are then the identity, 0xC0 00 .. 00).  A refused item gets zero
+ *                      bytes in all three outputs and leaves its neighbours alone.
+ * Host buffers in and out.  CG1_ERR_ARG, before anything is written, for n >= CG1_WHISK_REGISTER_MAX_ITEMS, first_index + n > 2^32, a null
+ * buffer, or only one of rs32 / blinders32.  The device call runs slices of 2^20 items on the context's stream and zeroes the device
+ * copies of k, r, b, k r and b r before it returns; no error text ever holds a secret.  cg1_whisk_register is the host twin on the
+ * worker pool (the same bytes and codes; it takes supplied r and b only).
+ * cg1_whisk_register_points_device is the stage of the five multiples alone, for measurements: five columns of n <= 2^20 canonical
+ * scalars -> five columns of n encodings (device pointers); shared_inversion != 0 runs k_register_points (one lane and one inversion per
+ * item: what the device call uses for slices above 32 768 items), 0 runs k_generator_mul over the 5 n scalars (one lane and one inversion
+ * per point: what it uses up to there, where the longer lanes of the first leave the chip idle). */
+#define CG1_WHISK_REGISTER_MAX_ITEMS (1ull << 26)
+int cg1_whisk_register_device(cg1_ctx* ctx, size_t n, const uint8_t* ks32, const uint8_t* rs32 /* or NULL */, const uint8_t* blinders32 /* or NULL */,
+                              const uint8_t* seed32 /* used when rs32 == NULL */, uint64_t first_index, uint8_t* out_trackers96, uint8_t* out_k_commitments48,
+                              uint8_t* out_proofs128, int32_t* status);
+int cg1_whisk_register(size_t n, const uint8_t* ks32, const uint8_t* rs32, const uint8_t* blinders32, uint8_t* out_trackers96, uint8_t* out_k_commitments48,
+                       uint8_t* out_proofs128, int32_t* status);
+int cg1_whisk_register_draws(const uint8_t seed32[32], uint64_t first_index, size_t n, uint8_t* out_rs32, uint8_t* out_blinders32);
+int cg1_whisk_register_points_device(cg1_ctx* ctx, const void* d_scalars32, size_t n, void* d_out48, int shared_inversion);
+
 #ifdef __cplusplus
 }
 #endif
