@@ -6,7 +6,7 @@
 //   lineage   cg1chain::lineage (chain_lineage.h, host): a status per block, (origin slot, composite scalar) per position, the last writers
 //   multiply  k_chain_lineage_mul (kernels_chain_prove.h): ONE launch without dependencies -> vec_R | vec_S, vec_T | vec_U, T_t | U_t
 //   advance   k_chain_scatter of the last writers' records, with zero status bytes, into the set
-// -- and the proofs, independent now, go through cg1_shuffle_prove_device in groups of CG1_SAME_MSM_MAX_PROVERS with M by whisk_m_enqueue.
+// -- and the proofs, independent now, go through shuffle_prove (capi_shuffle.h) in groups of CG1_SAME_MSM_MAX_PROVERS with M by whisk_m_run.
 //   cg1_chain_evolve_device   the tracker stage alone, permutations and scalars the caller's
 //   cg1_chain_prove_seeded    the draws of cg1_whisk_shuffle_prove_seeded for all blocks (kept in wiped host staging: D 32 bytes per block),
 //                             the tracker stage, the proofs
@@ -80,7 +80,7 @@ int chain_tracker_stage(cg1_ctx* ctx, const char* who, void* d_set_pts96, void* 
   // ---- lineage
   out.status.assign(n, 0); out.bad_at.assign(n, 0);
   out.writers.assign(2 * std::min(n_slots, n * ell), 0);
-  WipedBytes lin;                                           // origins (they spell the permutations out) | composites
+  cg1::WipedBytes lin;                                      // origins (they spell the permutations out) | composites
   lin.v.resize(pos * 36);
   uint32_t* origin = reinterpret_cast<uint32_t*>(lin.v.data());
   uint8_t* comp = lin.v.data() + pos * 4;
@@ -184,17 +184,16 @@ int cg1_chain_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_bloc
   const auto t_call = wall();
   t->chain_used = 0;
   // ---- 1. the draws of all blocks: on the device, one copy down, kept in wiped host staging
-  WipedBytes stage;
+  cg1::WipedBytes stage;
   if (const int rc = whisk_draws_run(ctx, ell, N, seed32, first_index, stage)) return rc;
-  const DrawBlock B = whisk_draw_block(ell, N);
-  const cg1whisk_host::DrawColumns C = cg1whisk_host::draw_columns(ell, N);
-  const uint32_t* perm = reinterpret_cast<const uint32_t*>(stage.v.data());
-  const uint8_t* sc = stage.v.data() + (B.scalars - B.perm);
-  if (const int rc = cg1chain::lineage_check(ctx->err, sizeof ctx->err, who, n_slots, indices, perm, sc + 32 * C.k, N, ell)) return rc;
+  const ShuffleWitness drawn = ShuffleWitness::of_draws(stage.v.data(), ell, N);
+  const uint8_t* k32 = drawn.col[cg1whisk_host::COL_K];
+  if (const int rc = cg1chain::lineage_check(ctx->err, sizeof ctx->err, who, n_slots, indices, drawn.perm, k32, N, ell)) return rc;
   // ---- 2. the trackers of every block, the set advanced
   ChainStageOut S;
-  if (const int rc = chain_tracker_stage(ctx, who, d_set_pts96, d_set_pstat, n_slots, indices, perm, sc + 32 * C.k, N, ell, true, S)) return rc;
-  // ---- 3. the proofs: the surviving blocks in groups, each M by one table launch and then the whole-shuffle chain, bases certified
+  if (const int rc = chain_tracker_stage(ctx, who, d_set_pts96, d_set_pstat, n_slots, indices, drawn.perm, k32, N, ell, true, S)) return rc;
+  // ---- 3. the proofs: the surviving blocks in groups, each M by one table launch and then the whole-shuffle chain, bases certified (its
+  // "prover" counts the blocks of the group)
   const size_t pb = cg1_shuffle_prover_proof_bytes(ell);
   std::vector<size_t> keep;
   for (size_t b = 0; b < N; ++b) if (!S.status[b]) keep.push_back(b);
@@ -203,60 +202,22 @@ int cg1_chain_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_bloc
   int rc = CG1_OK;
   for (size_t lo = 0; lo < keep.size() && !rc; lo += G) {
     const size_t Q = std::min(G, keep.size() - lo);
-    // the group's rows of every column, one after the other as the chain takes them
-    struct Col { size_t at, row; };
-    const Col cols[8] = {{C.k, 1}, {C.mbl, NB}, {C.abl, 2}, {C.cbl, NB}, {C.ipa_r, n}, {C.z_head, n - 2}, {C.bl, 5}, {C.vec_r, n}};
-    WipedBytes g;                                           // perm | the eight columns
-    size_t col_at[8], total = Q * ell * 4;
-    for (int c = 0; c < 8; ++c) { col_at[c] = total; total += Q * cols[c].row * 32; }
-    g.v.resize(total);
-    std::vector<uint8_t> rs(Q * 2 * ell * 96), tu(Q * 2 * ell * 96);
-    std::vector<uint32_t> gi(Q * ell), hi(Q * NB), ui(Q, u_index), gti(Q, gt_index), gui(Q, gu_index);
-    for (size_t q = 0; q < Q; ++q) {
-      const size_t b = keep[lo + q];
-      memcpy(g.v.data() + q * ell * 4, perm + b * ell, ell * 4);
-      for (int c = 0; c < 8; ++c) memcpy(g.v.data() + col_at[c] + q * cols[c].row * 32, sc + 32 * (cols[c].at + b * cols[c].row), cols[c].row * 32);
-      memcpy(&rs[q * 2 * ell * 96], &S.rs[b * 2 * ell * 96], 2 * ell * 96); memcpy(&tu[q * 2 * ell * 96], &S.tu[b * 2 * ell * 96], 2 * ell * 96);
-      memcpy(&gi[q * ell], g_index, ell * 4); memcpy(&hi[q * NB], h_index, NB * 4);
-    }
-    const uint32_t* gperm = reinterpret_cast<const uint32_t*>(g.v.data());
-    // M
-    struct MLayout : ChainLayout { WhiskMFields f; } ML{};
-    ML.begin(0);
-    ML.f.tb = ML.take(Q * n * 4); ML.f.sc = ML.take(Q * n * 32); ML.f.offs = ML.take((Q + 1) * 4);
-    ML.up_end = ML.down_begin = ML.total;
-    ML.f.m48 = ML.take(Q * 48); ML.f.st_msm = ML.take(16);
-    ML.down_end = ML.total;
-    uint8_t* H; uint8_t* D;
-    if ((rc = chain_reserve(ctx, t, ML.total, H, D))) break;
-    int shape_rc = CG1_OK;
-    const TableShape shape = whisk_m_shape(ctx, t, ell, Q, shape_rc);
-    if ((rc = shape_rc)) break;
-    whisk_m_rows(H, ML.f, ell, Q, gi.data(), hi.data(), gperm, g.v.data() + col_at[1]);
-    if ((rc = chain_upload(ctx, t, ML))) break;
-    if ((rc = whisk_m_enqueue(ctx, t, D, ML.f, ell, Q, shape))) break;
-    if ((rc = chain_download(ctx, t, ML))) { rc = shuffle_refuse(ctx, rc); break; }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) { snprintf(ctx->err, sizeof ctx->err, "%s: the device failed under M", who); rc = CG1_ERR_HIP; break; }
-    if ((rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + ML.f.st_msm)[0]))) break;
-    memcpy(&all_m[lo * 48], H + ML.f.m48, Q * 48);
-    // the chain
+    cg1::WipedBytes kept;
+    const ShuffleWitness w = drawn.gather(&keep[lo], Q, kept);
+    const ShuffleCrsRows crs(ShuffleCrsRows(g_index, h_index, one_each, one_each + 1, one_each + 2, gth_affine96), ell, 1, nullptr, Q);      // the one CRS, Q times
+    std::vector<uint8_t> rs_kept, tu_kept;
+    const uint8_t* rs = shuffle_rows(S.rs.data(), 2 * ell * 96, N, &keep[lo], Q, rs_kept);
+    const uint8_t* tu = shuffle_rows(S.tu.data(), 2 * ell * 96, N, &keep[lo], Q, tu_kept);
+    if ((rc = whisk_m_run(ctx, who, t, ell, Q, crs, w, &all_m[lo * 48]))) break;
     const auto t_chain = wall();
-    rc = cg1_shuffle_prove_device(ctx, t, ell, Q, gi.data(), hi.data(), ui.data(), gti.data(), gui.data(), gth_affine96, rs.data(), tu.data(), &all_m[lo * 48], gperm,
-                                  g.v.data() + col_at[0], g.v.data() + col_at[1], g.v.data() + col_at[2], g.v.data() + col_at[3], g.v.data() + col_at[4],
-                                  g.v.data() + col_at[5], g.v.data() + col_at[6], g.v.data() + col_at[7], 1, &all_proofs[lo * pb], nullptr);
+    rc = shuffle_prove(ctx, who, t, ell, Q, crs, rs, tu, &all_m[lo * 48], w, 1, &all_proofs[lo * pb], nullptr);
     ms_chain += ms_since(t_chain);
-    if (rc) whisk_chain_text(ctx, who);                     // (its "prover" counts the blocks of the group that reached it)
   }
   // ---- 4. secret hygiene (the draws and composites: whisk_draws_run, chain_tracker_stage, WipedBytes), then the caller's buffers
   const hipError_t wiped = whisk_wipe_block(ctx, t);
   if (rc) return rc;
   HIPCHK(wiped);
-  memset(out_proofs, 0, N * (48 + pb));
-  memcpy(out_post96, S.post.data(), S.post.size());
-  for (size_t q = 0; q < keep.size(); ++q) {               // M || proof: the wire form cg1_whisk_shuffle_proof_bytes counts
-    memcpy(out_proofs + keep[q] * (48 + pb), &all_m[48 * q], 48);
-    memcpy(out_proofs + keep[q] * (48 + pb) + 48, &all_proofs[q * pb], pb);
-  }
+  whisk_place_outputs(ell, N, keep.data(), keep.size(), S.post.data(), all_m.data(), all_proofs.data(), out_post96, out_proofs);
   memcpy(out_status, S.status.data(), N * 4); memcpy(out_bad_at, S.bad_at.data(), N * 4);
   memcpy(out_writers, S.writers.data(), S.n_writers * 8);
   *out_n_writers = S.n_writers;

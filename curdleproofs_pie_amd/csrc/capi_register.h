@@ -28,24 +28,16 @@ int register_refuse(char* err, size_t errlen, const char* who, size_t n, const u
   return CG1_ERR_ARG;
 }
 
-void register_wipe(void* p, size_t bytes) {               // a memset the optimiser may not drop
-  volatile uint8_t* v = (volatile uint8_t*)p;
-  while (bytes--) *v++ = 0;
-}
-
 // draw d (0: r, 1: b) of registration `index`: kernels_register.h draw_from_seed on the host
 cg1fr::fr register_draw(const uint8_t seed32[32], uint64_t index, uint32_t d) {
-  uint8_t st[200];
-  memset(st, 0, sizeof st);
-  memcpy(st, "whisk_registration_draw", 23);
-  memcpy(st + 23, seed32, 32);
-  for (int b = 0; b < 8; ++b) st[55 + b] = (uint8_t)(index >> (8 * b));
-  for (int b = 0; b < 4; ++b) st[63 + b] = (uint8_t)(d >> (8 * b));
-  st[67] ^= 0x1F;
-  st[135] ^= 0x80;
-  cg1_keccak_f1600(st);
+  uint8_t msg[67], st[64];
+  memcpy(msg, "whisk_registration_draw", 23);
+  memcpy(msg + 23, seed32, 32);
+  for (int b = 0; b < 8; ++b) msg[55 + b] = (uint8_t)(index >> (8 * b));
+  for (int b = 0; b < 4; ++b) msg[63 + b] = (uint8_t)(d >> (8 * b));
+  cg1::shake256_block64(msg, sizeof msg, st);
   const cg1fr::fr v = cg1fr::fr_from_le64_wide(st);
-  register_wipe(st, sizeof st);
+  cg1::wipe(msg, sizeof msg); cg1::wipe(st, sizeof st);
   return v;
 }
 
@@ -71,7 +63,7 @@ struct RegisterGenTable {
     cg1h::jac acc = cg1h::jac_identity();
     for (int w = 0; w < 32; ++w)
       if (le[w]) { const size_t e = (size_t)w * 255 + (le[w] - 1); acc = cg1h::jac_madd(acc, xs[e], ys[e]); }
-    register_wipe(le, sizeof le);
+    cg1::wipe(le, sizeof le);
     return acc;
   }
 };
@@ -125,24 +117,11 @@ int cg1_whisk_register(size_t n, const uint8_t* ks32, const uint8_t* rs32, const
     memcpy(pf, enc[3], 48); memcpy(pf + 48, enc[4], 48);
     cg1fr::fr_to_le32(cg1fr::fr_sub(b, cg1fr::fr_mul(c, k)), pf + 96);    // s = b - c k (opening.py:52)
     status[i] = 0;
-    register_wipe(sc, sizeof sc); register_wipe(&k, sizeof k); register_wipe(&r, sizeof r); register_wipe(&b, sizeof b);
-    register_wipe(pts, sizeof pts);
+    cg1::wipe(sc, sizeof sc); cg1::wipe(&k, sizeof k); cg1::wipe(&r, sizeof r); cg1::wipe(&b, sizeof b);
+    cg1::wipe(pts, sizeof pts);
   };
-  if (n < 8) {
-    for (size_t i = 0; i < n; ++i) one(i);
-    return CG1_OK;
-  }
-  std::atomic<size_t> next{0};
-  const size_t items = (n + 3) / 4;                                       // slices of 4 items
-  std::function<void()> work = [&]() {
-    for (;;) {
-      const size_t it = next.fetch_add(1);
-      if (it >= items) return;
-      for (size_t i = it * 4; i < std::min(n, it * 4 + 4); ++i) one(i);
-    }
-  };
-  cg1::Pool& pool = cg1::Pool::get();
-  pool.run(work, std::min(items, pool.size() + 1));
+  // slices of 4 items over the worker pool; fewer than 8 items on the caller's thread
+  cg1::pool_for((n + 3) / 4, n < 8 ? 1 : 0, [&](size_t it) { for (size_t i = it * 4; i < std::min(n, it * 4 + 4); ++i) one(i); });
   return CG1_OK;
 }
 

@@ -2,8 +2,11 @@
 // one ell in step, as ONE native call: k_shuffle_begin (kernels_shuffle.h) and the head MSMs A | A', then the parts of the same-scalar
 // block (capi_same_scalar.h), the same-permutation chain (capi_gprod.h, capi_same_perm.h) and the same-MSM chain (capi_same_msm.h) on one
 // stream, with the two transcript heads that need a device result run on the host behind an event each, under device work already queued.
+// The entry is a pointer check in front of shuffle_prove, which the Whisk entries and the chain prover call under their own names with the
+// witness as ONE value (ShuffleWitness, whisk_shuffle_host.h) and the CRS rows as another (ShuffleCrsRows).
 // Part of the single translation unit csrc/msm_gpu.hip (included there; not a stand-alone header).
 #pragma once
+#include "whisk_shuffle_host.h"
 
 namespace {
 // the entry's own fields; the three arguments' layouts follow it in the block, behind the one states field
@@ -24,45 +27,64 @@ ShuffleLayout shuffle_layout(size_t ell, size_t P, size_t base) {
   L.tb = L.take(P * cg1shuffle::head_terms((uint32_t)n) * 4); L.sc = L.take(P * cg1shuffle::head_terms((uint32_t)n) * 32);
   return L;
 }
-// run f(p) for every prover on the process's worker pool (the caller's thread takes part)
-template <typename F>
-void shuffle_for_provers(size_t P, F f) {
-  std::atomic<size_t> next{0};
-  const std::function<void()> work = [&] { for (size_t p; (p = next.fetch_add(1)) < P;) f(p); };
-  cg1::Pool& pool = cg1::Pool::get();
-  const size_t nt = std::min(P, pool.size() + 1);
-  if (nt <= 1) work(); else pool.run(work, nt);
-}
 struct ShuffleEvents {                                      // the two host waits of a call
   hipEvent_t head = nullptr, mid = nullptr;
   ~ShuffleEvents() { if (head) (void)hipEventDestroy(head); if (mid) (void)hipEventDestroy(mid); }
 };
 // after a refusal that came down in mid-pipeline: nothing of the call may still be running when the block is laid out afresh
 int shuffle_refuse(cg1_ctx* ctx, int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-}  // namespace
 
-extern "C" {
-size_t cg1_shuffle_prover_proof_bytes(size_t ell) {
-  const size_t n = ell + cg1shuffle::N_BLINDERS;
-  if (ell < 1 || n < ell || !chain_pow2(n) || n > CG1_SAME_MSM_MAX_N) return 0;
-  return 48 + 288 + cg1_same_perm_proof_bytes(ell, cg1shuffle::N_BLINDERS) + 288 + cg1_same_msm_proof_bytes(n);
+using cg1whisk_host::ShuffleWitness;
+static_assert(cg1whisk_host::N_BLINDERS == cg1shuffle::N_BLINDERS, "the witness's column table is laid out for the prover's blinders");
+
+// the rows keep[0 .. Q) of a table of P rows of `row` bytes, one after the other in `own`; all P rows: the table itself
+const uint8_t* shuffle_rows(const uint8_t* all, size_t row, size_t P, const size_t* keep, size_t Q, std::vector<uint8_t>& own) {
+  if (Q == P) return all;
+  own.resize(Q * row);
+  for (size_t q = 0; q < Q; ++q) memcpy(&own[q * row], all + keep[q] * row, row);
+  return own.data();
 }
 
-int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
-                             const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* rs_affine96, const uint8_t* tu_affine96,
-                             const uint8_t* m48, const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32, const uint8_t* vec_a_blinders32,
-                             const uint8_t* vec_c_blinders32, const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* blinders32, const uint8_t* vec_r32,
-                             int bases_certified, uint8_t* out_proofs, uint32_t* out_clocks) {
-  static const char* const who = "cg1_shuffle_prove_device";
+// The CRS of P provers as index rows into the table: g (ell per prover), h (4), u, gt, gu (one each); gth_affine96 = G_t | G_u | H is the
+// call's.  A view over the caller's rows, or over rows of its own: the rows a `keep` selects, or one row repeated.
+struct ShuffleCrsRows {
+  const uint32_t *g, *h, *u, *gt, *gu;
+  const uint8_t* gth_affine96;
+  ShuffleCrsRows(const uint32_t* g_, const uint32_t* h_, const uint32_t* u_, const uint32_t* gt_, const uint32_t* gu_, const uint8_t* gth)
+      : g(g_), h(h_), u(u_), gt(gt_), gu(gu_), gth_affine96(gth) {}
+  // the rows keep[0 .. Q) of `all`'s P (all P: `all` itself, and no copy); keep == NULL: row 0 of `all`, Q times
+  ShuffleCrsRows(const ShuffleCrsRows& all, size_t ell, size_t P, const size_t* keep, size_t Q) : ShuffleCrsRows(all.g, all.h, all.u, all.gt, all.gu, all.gth_affine96) {
+    constexpr size_t NB = cg1shuffle::N_BLINDERS;
+    if (keep && Q == P) return;
+    own.resize(Q * (ell + NB + 3));                         // g | h | u | gt | gu
+    uint32_t* o = own.data();
+    g = o; h = g + Q * ell; u = h + Q * NB; gt = u + Q; gu = gt + Q;
+    for (size_t q = 0; q < Q; ++q) {
+      const size_t p = keep ? keep[q] : 0;
+      memcpy(o + q * ell, all.g + p * ell, ell * 4); memcpy(o + Q * ell + q * NB, all.h + p * NB, NB * 4);
+      o[Q * (ell + NB) + q] = all.u[p]; o[Q * (ell + NB + 1) + q] = all.gt[p]; o[Q * (ell + NB + 2) + q] = all.gu[p];
+    }
+  }
+  ShuffleCrsRows(const ShuffleCrsRows&) = delete;
+
+ private:
+  std::vector<uint32_t> own;
+};
+
+// The body of cg1_shuffle_prove_device, under the calling entry's name: the whole-shuffle entry, the Whisk entries (capi_whisk_shuffle.h)
+// and the chain prover (capi_chain_prove.h) come here with pointers they have checked.  "prover p" in a refusal counts the P provers
+// that reached this function.
+int shuffle_prove(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t P, const ShuffleCrsRows& crs, const uint8_t* rs_affine96, const uint8_t* tu_affine96,
+                  const uint8_t* m48, const ShuffleWitness& witness, int bases_certified, uint8_t* out_proofs, uint32_t* out_clocks) {
+  namespace W = cg1whisk_host;
   static const char* const hashed_m[] = {"M"};
   constexpr size_t NB = cg1shuffle::N_BLINDERS;
-  if (!ctx) return CG1_ERR_HIP;
-  if (n_provers == 0) return CG1_OK;
+  const uint32_t *g_index = crs.g, *h_index = crs.h, *u_index = crs.u, *gt_index = crs.gt, *gu_index = crs.gu, *perm = witness.perm;
+  const uint8_t *gth_affine96 = crs.gth_affine96, *k32 = witness.col[W::COL_K], *vec_m_blinders32 = witness.col[W::COL_MBL], *vec_a_blinders32 = witness.col[W::COL_ABL],
+                *vec_c_blinders32 = witness.col[W::COL_CBL], *ipa_r32 = witness.col[W::COL_IPA_R], *ipa_z_head32 = witness.col[W::COL_Z_HEAD],
+                *blinders32 = witness.col[W::COL_BL], *vec_r32 = witness.col[W::COL_VEC_R];
   // ---- 1. refusals: the whole call, before anything is written -- the entry's own, then the three arguments' on what they will see
-  const size_t P = n_provers, n = ell + NB;
-  const bool pointers_ok = g_index && h_index && u_index && gt_index && gu_index && gth_affine96 && rs_affine96 && tu_affine96 && m48 && perm && k32 &&
-                           vec_m_blinders32 && vec_a_blinders32 && vec_c_blinders32 && ipa_r32 && ipa_z_head32 && blinders32 && vec_r32 && out_proofs;
-  if (!t || t->device != ctx->device || !pointers_ok) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
+  const size_t n = ell + NB;
   const size_t pb = cg1_shuffle_prover_proof_bytes(ell);
   if (!pb) { snprintf(ctx->err, sizeof ctx->err, "%s: ell + %zu must be a power of two in 8 .. %d", who, NB, CG1_SAME_MSM_MAX_N); return CG1_ERR_ARG; }
   if (P > CG1_SAME_MSM_MAX_PROVERS || P * 2 * n > CG1_LIGHT_MAX_BASES) {
@@ -130,7 +152,7 @@ int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_pr
   smsm_stage(H, SM, n, P, gi_m.data(), tu.data(), nullptr, vec_r32);
   memcpy(H + SH.perm, perm, P * ell * 4); memcpy(H + SH.abl, vec_a_blinders32, P * 64); memcpy(H + SH.gi_a, gi_a.data(), P * n * 4);
   for (uint32_t p = 0; p < Pn; ++p) cg1shuffle::head_offsets(nn, p * cg1shuffle::head_terms(nn), reinterpret_cast<uint32_t*>(H + SH.offs) + cg1shuffle::HEAD_MSMS * p);
-  shuffle_for_provers(P, [&](size_t p) {
+  cg1::pool_for(P, 0, [&](size_t p) {
     static const uint8_t label[] = "curdleproofs", step1[] = "curdleproofs_step1", l_a[] = "curdleproofs_vec_a";
     uint8_t* st = H + states + 208 * p;
     std::vector<uint8_t> list(4 * ell * 48);
@@ -171,7 +193,7 @@ int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_pr
   // ---- 6. the first wait; the same-permutation head on the host, under step 5, then its chain
   HIPCHK(hipEventSynchronize(ev.head));
   if (const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + SH.st_head)[0])) return shuffle_refuse(ctx, rc);
-  shuffle_for_provers(P, [&](size_t p) {
+  cg1::pool_for(P, 0, [&](size_t p) {
     uint8_t am[96];
     memcpy(am, H + SH.pts + p * 96, 48); memcpy(am + 48, &canon_m[48 * p], 48);
     same_perm_head(H, gp, p, am, H + SS.va + p * ell * 32);
@@ -196,7 +218,7 @@ int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_pr
   HIPCHK(hipEventSynchronize(ev.mid));
   if (const int rc = chain_status_error(ctx, H, GP, who, same_perm_status_error)) return shuffle_refuse(ctx, rc);
   if (const int rc = chain_status_error(ctx, H, SS, who, same_scalar_status_error)) return shuffle_refuse(ctx, rc);
-  shuffle_for_provers(P, [&](size_t p) {
+  cg1::pool_for(P, 0, [&](size_t p) {
     const uint8_t* ss = H + SS.proof + p * cg1sscalar::PROOF_BYTES;         // cm_T = T_1 | T_2, cm_U = U_1 | U_2, ...
     uint8_t head[144];
     memcpy(head, H + SH.pts + p * 96 + 48, 48); memcpy(head + 48, ss + 48, 48); memcpy(head + 96, ss + 144, 48);
@@ -224,5 +246,29 @@ int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_pr
     for (size_t i = 0; i < P * 4; ++i)
       out_clocks[i] = reinterpret_cast<const uint32_t*>(H + SS.clocks)[i] + reinterpret_cast<const uint32_t*>(H + GP.clocks)[i] + reinterpret_cast<const uint32_t*>(H + SM.clocks)[i];
   return CG1_OK;
+}
+}  // namespace
+
+extern "C" {
+size_t cg1_shuffle_prover_proof_bytes(size_t ell) {
+  const size_t n = ell + cg1shuffle::N_BLINDERS;
+  if (ell < 1 || n < ell || !chain_pow2(n) || n > CG1_SAME_MSM_MAX_N) return 0;
+  return 48 + 288 + cg1_same_perm_proof_bytes(ell, cg1shuffle::N_BLINDERS) + 288 + cg1_same_msm_proof_bytes(n);
+}
+
+int cg1_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
+                             const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* rs_affine96, const uint8_t* tu_affine96,
+                             const uint8_t* m48, const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32, const uint8_t* vec_a_blinders32,
+                             const uint8_t* vec_c_blinders32, const uint8_t* ipa_r32, const uint8_t* ipa_z_head32, const uint8_t* blinders32, const uint8_t* vec_r32,
+                             int bases_certified, uint8_t* out_proofs, uint32_t* out_clocks) {
+  static const char* const who = "cg1_shuffle_prove_device";
+  if (!ctx) return CG1_ERR_HIP;
+  if (n_provers == 0) return CG1_OK;
+  const bool pointers_ok = g_index && h_index && u_index && gt_index && gu_index && gth_affine96 && rs_affine96 && tu_affine96 && m48 && perm && k32 &&
+                           vec_m_blinders32 && vec_a_blinders32 && vec_c_blinders32 && ipa_r32 && ipa_z_head32 && blinders32 && vec_r32 && out_proofs;
+  if (!t || t->device != ctx->device || !pointers_ok) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
+  const ShuffleWitness w{ell, n_provers, perm, {k32, vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32, blinders32, vec_r32}};
+  return shuffle_prove(ctx, who, t, ell, n_provers, ShuffleCrsRows(g_index, h_index, u_index, gt_index, gu_index, gth_affine96), rs_affine96, tu_affine96, m48, w,
+                       bases_certified, out_proofs, out_clocks);
 }
 }  // extern "C"

@@ -129,15 +129,8 @@ int cg1_tracker_match(const uint8_t* trackers96, size_t n_trackers, const uint8_
         if (out_k_status[j] == 0 && cg1h::jac_eq(cg1h::jac_mul(Rs[i], ks32 + 32 * j), Ss[i])) bits |= 1ull << (j & 63);
     out_bitmap[it] = bits;
   };
-  auto spread = [&](size_t items, size_t serial_below, const std::function<void(size_t)>& one) {
-    if (items < serial_below) { for (size_t i = 0; i < items; ++i) one(i); return; }
-    std::atomic<size_t> next{0};
-    std::function<void()> work = [&]() { for (;;) { const size_t i = next.fetch_add(1); if (i >= items) return; one(i); } };
-    cg1::Pool& pool = cg1::Pool::get();
-    pool.run(work, std::min(items, pool.size() + 1));
-  };
-  spread(T, 16, decode);
-  spread(T * words, 2, word);
+  cg1::pool_for(T, T < 16 ? 1 : 0, decode);                 // (fewer than 16 decodings do not pay for waking the pool)
+  cg1::pool_for(T * words, 0, word);
   return CG1_OK;
 }
 }  // extern "C"

@@ -2,7 +2,7 @@
 //   cg1_whisk_shuffle_front          the device front: decode and certify the 2 ell tracker points per prover, vec_T | vec_U = perm(k vec_R |
 //                                    k vec_S) by k_whisk_permute_mul (kernels_whisk_shuffle.h), M as one k_table_msm over the CRS table --
 //                                    one stream, one wait
-//   cg1_whisk_shuffle_prove_device   the front, then cg1_shuffle_prove_device (capi_shuffle.h) on what it left, bases certified
+//   cg1_whisk_shuffle_prove_device   the front, then shuffle_prove (capi_shuffle.h) on what it left, bases certified
 //   cg1_whisk_shuffle_draws_device   permutation, k and every blinder of n_provers shuffles from a 32-byte seed (k_whisk_draws, k_whisk_fisher_yates)
 //   cg1_whisk_shuffle_prove_seeded   those draws, the front with a status PER PROVER, and the chain on the provers the front did not refuse
 // The refusals and their texts are shared with the host twin cg1_whisk_shuffle_front_emulate (whisk_shuffle_host.h, lazy_host.cpp).
@@ -144,37 +144,55 @@ int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t 
   return CG1_OK;
 }
 
-// the chain's refusal text under the entry's name
-void whisk_chain_text(cg1_ctx* ctx, const char* who) {
-  static const char* const chain = "cg1_shuffle_prove_device";
-  const size_t cl = strlen(chain);
-  if (strncmp(ctx->err, chain, cl) == 0) {
-    const std::string tail(ctx->err + cl);
-    snprintf(ctx->err, sizeof ctx->err, "%s%s", who, tail.c_str());
+// M alone, for the chain prover, whose trackers come from its own stage: the block laid out for M only, one launch, one copy down, one
+// wait.  (whisk_front runs the same pieces fused with the decode, under its one wait.)
+int whisk_m_run(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t Q, const ShuffleCrsRows& rows, const ShuffleWitness& witness, uint8_t* out_m48) {
+  const size_t n = ell + cg1whisk_host::N_BLINDERS;
+  struct MLayout : ChainLayout { WhiskMFields f; } ML{};
+  ML.begin(0);
+  ML.f.tb = ML.take(Q * n * 4); ML.f.sc = ML.take(Q * n * 32); ML.f.offs = ML.take((Q + 1) * 4);
+  ML.up_end = ML.down_begin = ML.total;
+  ML.f.m48 = ML.take(Q * 48); ML.f.st_msm = ML.take(16);
+  ML.down_end = ML.total;
+  uint8_t* H; uint8_t* D;
+  if (const int rc = chain_reserve(ctx, t, ML.total, H, D)) return rc;
+  int shape_rc = CG1_OK;
+  const TableShape shape = whisk_m_shape(ctx, t, ell, Q, shape_rc);
+  if (shape_rc) return shape_rc;
+  whisk_m_rows(H, ML.f, ell, Q, rows.g, rows.h, witness.perm, witness.col[cg1whisk_host::COL_MBL]);
+  if (const int rc = chain_upload(ctx, t, ML)) return rc;
+  if (const int rc = whisk_m_enqueue(ctx, t, D, ML.f, ell, Q, shape)) return rc;
+  if (const int rc = chain_download(ctx, t, ML)) return shuffle_refuse(ctx, rc);
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) { snprintf(ctx->err, sizeof ctx->err, "%s: the device failed under M", who); return CG1_ERR_HIP; }
+  if (const int rc = table_status_error<FixedKind>(ctx, reinterpret_cast<const uint32_t*>(H + ML.f.st_msm)[0])) return rc;
+  memcpy(out_m48, H + ML.f.m48, Q * 48);
+  return CG1_OK;
+}
+
+// M || proof of prover p: the wire form cg1_whisk_shuffle_proof_bytes counts (pb = cg1_shuffle_prover_proof_bytes(ell))
+void whisk_write_wire(uint8_t* out_proofs, size_t p, const uint8_t* m48, const uint8_t* proof, size_t pb) {
+  memcpy(out_proofs + p * (48 + pb), m48, 48);
+  memcpy(out_proofs + p * (48 + pb) + 48, proof, pb);
+}
+// The caller's two buffers: zeros for all P provers, then kept prover q at position keep[q] (keep == NULL: q) -- its post trackers
+// (post96: P rows, by position), its M and its proof (m48, proofs: Q rows, as the chain took them).
+void whisk_place_outputs(size_t ell, size_t P, const size_t* keep, size_t Q, const uint8_t* post96, const uint8_t* m48, const uint8_t* proofs, uint8_t* out_post96,
+                         uint8_t* out_proofs) {
+  const size_t pb = cg1_shuffle_prover_proof_bytes(ell), row = 2 * ell * 48;
+  memset(out_post96, 0, P * row); memset(out_proofs, 0, P * (48 + pb));
+  for (size_t q = 0; q < Q; ++q) {
+    const size_t p = keep ? keep[q] : q;
+    memcpy(out_post96 + p * row, post96 + p * row, row);
+    whisk_write_wire(out_proofs, p, m48 + 48 * q, proofs + q * pb, pb);
   }
 }
 
 // ---- the seeded draws
-void whisk_wipe(void* p, size_t n) {                        // a memset the optimiser may not drop
-  memset(p, 0, n);
-  __asm__ __volatile__("" : : "r"(p) : "memory");
-}
-struct WipedBytes {                                         // host staging of secrets: zeroed on every exit path
-  std::vector<uint8_t> v;
-  ~WipedBytes() { if (!v.empty()) whisk_wipe(v.data(), v.size()); }
-};
-struct DrawBlock { size_t swaps, perm, scalars, total; };   // ctx->d_whisk_draws; the host staging holds [perm, total)
-DrawBlock whisk_draw_block(size_t ell, size_t P) {
-  auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
-  DrawBlock B;
-  B.swaps = 0; B.perm = up(P * (ell - 1) * 4); B.scalars = B.perm + up(P * ell * 4);
-  B.total = B.scalars + cg1whisk_host::draw_columns(ell, P).total * 32;
-  return B;
-}
+using cg1whisk_host::DrawBlock;
 // k_whisk_draws and k_whisk_fisher_yates on the context's stream, ONE copy down (perm | scalars -> stage), the device buffer zeroed, one
 // wait.  The arguments have been checked (cg1whisk_host::check_draws).
-int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, uint64_t first_index, WipedBytes& stage) {
-  const DrawBlock B = whisk_draw_block(ell, P);
+int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, uint64_t first_index, cg1::WipedBytes& stage) {
+  const DrawBlock B = cg1whisk_host::draw_block(ell, P);
   HIPCHK(hipSetDevice(ctx->device));
   if (const int rc = cg1::grow_bufs(ctx, ctx->cap_whisk_draws, B.total, B.total, {cg1::dev_buf(ctx->d_whisk_draws, B.total)})) return rc;
   uint8_t* D = (uint8_t*)ctx->d_whisk_draws;
@@ -186,7 +204,7 @@ int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, u
   const uint32_t lanes = (uint32_t)P * cg1whisk_host::draw_count((uint32_t)ell);
   hipLaunchKernelGGL(cg1whisk::k_whisk_draws, dim3((lanes + cg1merlin::LANES - 1) / cg1merlin::LANES), dim3(cg1merlin::LANES), 0, ctx->stream, a);
   hipLaunchKernelGGL(cg1whisk::k_whisk_fisher_yates, dim3((uint32_t)P), dim3(64), 0, ctx->stream, (const uint32_t*)(D + B.swaps), (uint32_t)ell, (uint32_t*)(D + B.perm));
-  whisk_wipe(&a, sizeof a);
+  cg1::wipe(&a, sizeof a);
   hipError_t e = hipMemcpyAsync(stage.v.data(), D + B.perm, B.total - B.perm, hipMemcpyDeviceToHost, ctx->stream);
   const hipError_t e2 = hipMemsetAsync(D, 0, B.total, ctx->stream);        // the draws do not outlive the call on the device, whatever the copy said
   const hipError_t e3 = hipStreamSynchronize(ctx->stream);
@@ -234,23 +252,16 @@ int cg1_whisk_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   const bool pointers_ok = g_index && h_index && u_index && gt_index && gu_index && gth_affine96 && trackers96 && perm && k32 && vec_m_blinders32 && vec_a_blinders32 &&
                            vec_c_blinders32 && ipa_r32 && ipa_z_head32 && blinders32 && vec_r32 && out_post96 && out_proofs;
   if (!t || t->device != ctx->device || !pointers_ok) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
+  const ShuffleWitness w{ell, n_provers, perm, {k32, vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32, blinders32, vec_r32}};
   // both halves write into scratch of this call's; the caller's buffers are touched only when neither has refused.  (A shape or a P
   // the front refuses gets no scratch: the front refuses them before it writes.)
   const size_t P = n_provers, pts = cg1whisk_host::shape_ok(ell) && P <= CG1_SAME_MSM_MAX_PROVERS ? P * 2 * ell : 0;
   std::vector<uint8_t> rs(pts * 96), tu(pts * 96), post(pts * 48), m48(pts ? P * 48 : 0), proofs;
   if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, perm, k32, vec_m_blinders32, rs.data(), tu.data(), post.data(), m48.data())) return rc;
-  const size_t pb = cg1_shuffle_prover_proof_bytes(ell);
-  proofs.resize(P * pb);
-  if (const int rc = cg1_shuffle_prove_device(ctx, t, ell, P, g_index, h_index, u_index, gt_index, gu_index, gth_affine96, rs.data(), tu.data(), m48.data(), perm, k32,
-                                              vec_m_blinders32, vec_a_blinders32, vec_c_blinders32, ipa_r32, ipa_z_head32, blinders32, vec_r32, 1, proofs.data(), nullptr)) {
-    whisk_chain_text(ctx, who);
-    return rc;
-  }
-  memcpy(out_post96, post.data(), pts * 48);
-  for (size_t p = 0; p < P; ++p) {                          // M || proof: the wire form cg1_shuffle_proof_bytes counts
-    memcpy(out_proofs + p * (48 + pb), &m48[48 * p], 48);
-    memcpy(out_proofs + p * (48 + pb) + 48, &proofs[p * pb], pb);
-  }
+  proofs.resize(P * cg1_shuffle_prover_proof_bytes(ell));
+  if (const int rc = shuffle_prove(ctx, who, t, ell, P, ShuffleCrsRows(g_index, h_index, u_index, gt_index, gu_index, gth_affine96), rs.data(), tu.data(), m48.data(), w, 1,
+                                   proofs.data(), nullptr)) return rc;
+  whisk_place_outputs(ell, P, nullptr, P, post.data(), m48.data(), proofs.data(), out_post96, out_proofs);
   return CG1_OK;
 }
 
@@ -260,9 +271,9 @@ int cg1_whisk_shuffle_draws_device(cg1_ctx* ctx, size_t ell, size_t n_provers, c
   if (!seed32 || !out_perm || !out_scalars32) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
   if (const int rc = cg1whisk_host::check_draws(ctx->err, sizeof ctx->err, who, ell, n_provers, first_index)) return rc;
   if (n_provers == 0) return CG1_OK;
-  WipedBytes stage;
+  cg1::WipedBytes stage;
   if (const int rc = whisk_draws_run(ctx, ell, n_provers, seed32, first_index, stage)) return rc;
-  const DrawBlock B = whisk_draw_block(ell, n_provers);
+  const DrawBlock B = cg1whisk_host::draw_block(ell, n_provers);
   memcpy(out_perm, stage.v.data(), n_provers * ell * 4);
   memcpy(out_scalars32, stage.v.data() + (B.scalars - B.perm), B.total - B.scalars);
   return CG1_OK;
@@ -286,54 +297,35 @@ int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   if (const int rc = chain_check_indices(ctx, who, t, {{g_index, P * ell}, {h_index, P * NB}, {u_index, P}, {gt_index, P}, {gu_index, P}})) return rc;
   t->chain_used = 0;
   // ---- 1. the draws: on the device, one copy down
-  WipedBytes stage;
+  cg1::WipedBytes stage, kept;
   if (const int rc = whisk_draws_run(ctx, ell, P, seed32, first_index, stage)) return rc;
-  const DrawBlock B = whisk_draw_block(ell, P);
-  const cg1whisk_host::DrawColumns C = cg1whisk_host::draw_columns(ell, P);
-  uint32_t* perm = reinterpret_cast<uint32_t*>(stage.v.data());
-  uint8_t* sc = stage.v.data() + (B.scalars - B.perm);
+  const ShuffleWitness drawn = ShuffleWitness::of_draws(stage.v.data(), ell, P);
   // ---- 2. the front, a status per prover
-  const size_t pts = P * 2 * ell, pb = cg1_shuffle_prover_proof_bytes(ell);
-  std::vector<uint8_t> rs(pts * 96), tu(pts * 96), post(pts * 48), m48(P * 48), proofs;
+  const size_t pts = P * 2 * ell;
+  std::vector<uint8_t> rs(pts * 96), tu(pts * 96), post(pts * 48), m48(P * 48), proofs, rs_kept, tu_kept, m_kept;
   std::vector<int32_t> st(P);
   std::vector<uint32_t> at(P);
-  auto wipe_block = [&]() -> hipError_t { return whisk_wipe_block(ctx, t); };
-  if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, perm, sc + 32 * C.k, sc + 32 * C.mbl, rs.data(), tu.data(), post.data(), m48.data(),
-                                 st.data(), at.data())) { (void)wipe_block(); return rc; }
-  // ---- 3. the provers it did not refuse, moved to the front of every array, through the chain
+  if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, drawn.perm, drawn.col[cg1whisk_host::COL_K], drawn.col[cg1whisk_host::COL_MBL], rs.data(),
+                                 tu.data(), post.data(), m48.data(), st.data(), at.data())) { (void)whisk_wipe_block(ctx, t); return rc; }
+  // ---- 3. the provers it did not refuse, through the chain (its "prover" counts them, not the call's)
   std::vector<size_t> keep;
   for (size_t p = 0; p < P; ++p) if (!st[p]) keep.push_back(p);
   const size_t Q = keep.size();
-  std::vector<uint32_t> gi, hi, ui, gti, gui;
-  if (Q && Q < P) {
-    auto rows = [&](uint8_t* base, size_t row) { for (size_t q = 0; q < Q; ++q) memmove(base + q * row, base + keep[q] * row, row); };       // keep[q] >= q
-    rows(reinterpret_cast<uint8_t*>(perm), ell * 4);
-    rows(sc + 32 * C.k, 32); rows(sc + 32 * C.mbl, 32 * NB); rows(sc + 32 * C.abl, 64); rows(sc + 32 * C.cbl, 32 * NB); rows(sc + 32 * C.ipa_r, 32 * n);
-    rows(sc + 32 * C.z_head, 32 * (n - 2)); rows(sc + 32 * C.bl, 32 * 5); rows(sc + 32 * C.vec_r, 32 * n);
-    rows(rs.data(), 2 * ell * 96); rows(tu.data(), 2 * ell * 96); rows(m48.data(), 48);
-    auto pick = [&](std::vector<uint32_t>& dst, const uint32_t* src, size_t row) { dst.resize(Q * row); for (size_t q = 0; q < Q; ++q) memcpy(&dst[q * row], src + keep[q] * row, row * 4); };
-    pick(gi, g_index, ell); pick(hi, h_index, NB); pick(ui, u_index, 1); pick(gti, gt_index, 1); pick(gui, gu_index, 1);
-    g_index = gi.data(); h_index = hi.data(); u_index = ui.data(); gt_index = gti.data(); gu_index = gui.data();
-  }
   int rc = CG1_OK;
+  const uint8_t* m_q = m48.data();                           // M of the kept provers, one after the other
   if (Q) {
-    proofs.resize(Q * pb);
-    rc = cg1_shuffle_prove_device(ctx, t, ell, Q, g_index, h_index, u_index, gt_index, gu_index, gth_affine96, rs.data(), tu.data(), m48.data(), perm, sc + 32 * C.k,
-                                  sc + 32 * C.mbl, sc + 32 * C.abl, sc + 32 * C.cbl, sc + 32 * C.ipa_r, sc + 32 * C.z_head, sc + 32 * C.bl, sc + 32 * C.vec_r, 1, proofs.data(),
-                                  nullptr);
-    if (rc) whisk_chain_text(ctx, who);                     // (its "prover" counts the provers the front let through)
+    const ShuffleWitness w = drawn.gather(keep.data(), Q, kept);
+    const ShuffleCrsRows crs(ShuffleCrsRows(g_index, h_index, u_index, gt_index, gu_index, gth_affine96), ell, P, keep.data(), Q);
+    m_q = shuffle_rows(m48.data(), 48, P, keep.data(), Q, m_kept);
+    proofs.resize(Q * cg1_shuffle_prover_proof_bytes(ell));
+    rc = shuffle_prove(ctx, who, t, ell, Q, crs, shuffle_rows(rs.data(), 2 * ell * 96, P, keep.data(), Q, rs_kept), shuffle_rows(tu.data(), 2 * ell * 96, P, keep.data(), Q, tu_kept),
+                       m_q, w, 1, proofs.data(), nullptr);
   }
   // ---- 4. secret hygiene (the draws' own device buffer and host staging: whisk_draws_run, WipedBytes), then the caller's buffers
-  const hipError_t wiped = wipe_block();
+  const hipError_t wiped = whisk_wipe_block(ctx, t);
   if (rc) return rc;
   HIPCHK(wiped);
-  memset(out_post96, 0, pts * 48); memset(out_proofs, 0, P * (48 + pb));
-  for (size_t q = 0; q < Q; ++q) {                          // M || proof: the wire form cg1_shuffle_proof_bytes counts
-    const size_t p = keep[q];
-    memcpy(out_post96 + p * 2 * ell * 48, &post[p * 2 * ell * 48], 2 * ell * 48);
-    memcpy(out_proofs + p * (48 + pb), &m48[48 * q], 48);
-    memcpy(out_proofs + p * (48 + pb) + 48, &proofs[q * pb], pb);
-  }
+  whisk_place_outputs(ell, P, keep.data(), Q, post.data(), m_q, proofs.data(), out_post96, out_proofs);
   memcpy(out_status, st.data(), P * 4); memcpy(out_bad_at, at.data(), P * 4);
   return CG1_OK;
 }

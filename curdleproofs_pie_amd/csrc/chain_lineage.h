@@ -15,16 +15,12 @@
 #include <cstring>
 #include <vector>
 #include "fr.h"
+#include "secret_wipe.h"
 #include "../../include/curdle_g1.h"
 
 namespace cg1chain {
 
 constexpr uint32_t NO_ORIGIN = 0xffffffffu;               // out_origin of a refused block's positions
-
-inline void wipe(void* p, size_t n) {                      // a memset the optimiser may not drop
-  memset(p, 0, n);
-  __asm__ __volatile__("" : : "r"(p) : "memory");
-}
 
 // The refusals, before anything is written.  err (nullable) never holds a scalar.
 inline int lineage_check(char* err, size_t err_len, const char* who, size_t n_slots, const uint32_t* indices, const uint32_t* perm, const uint8_t* k32, size_t n_blocks,
@@ -105,9 +101,9 @@ inline int lineage(size_t n_slots, const uint8_t* point_status, const uint32_t* 
       cur[idx[t]] = post;                                  // in order of t: the last write of a repeated index wins
       last[idx[t]] = (int32_t)(b * ell + t);
     }
-    wipe(&k, sizeof k);
+    cg1::wipe(&k, sizeof k);
   }
-  wipe(cur.data(), cur.size() * sizeof(Value)); wipe(pre.data(), pre.size() * sizeof(Value));
+  cg1::wipe(cur.data(), cur.size() * sizeof(Value)); cg1::wipe(pre.data(), pre.size() * sizeof(Value));
   if (out_n_writers) {
     size_t m = 0;
     for (size_t s = 0; s < n_slots; ++s)

@@ -602,10 +602,7 @@ static int msm_small_batched_finish(Ctx* ctx, uint32_t M, std::vector<cg1h::jac>
     for (size_t j = 0; j < M; j += nth) one(j);
     for (size_t t = 1; t < nth; ++t) ctx->helper[t - 1].wait();
   } else {                                             // more Horners than the context's own helpers: the process's worker pool, one Horner at a time per thread
-    std::atomic<size_t> next{0};
-    std::function<void()> work = [&]() { for (;;) { const size_t j = next.fetch_add(1); if (j >= M) return; one(j); } };
-    Pool& pool = Pool::get();
-    pool.run(work, std::min<size_t>(M, pool.size() + 1));
+    cg1::pool_for(M, 0, one);
   }
   ctx->last_tail = (ctx->last_tail & ~((7u << TAIL_HORNER) | (7u << TAIL_NTH))) | (1u << TAIL_HORNER) | ((M <= 4 ? M : 0u) << TAIL_NTH);
   auto t1 = std::chrono::steady_clock::now();

@@ -261,13 +261,6 @@ static inline bool load_affine96(const uint8_t* rec, aff& o) {
   return fe_from_le48(rec, o.x) && fe_from_le48(rec + 48, o.y);
 }
 
-static inline void run_pool(const std::function<void()>& work, size_t items, int n_threads) {
-  cg1::Pool& pool = cg1::Pool::get();
-  size_t nt = n_threads > 0 ? (size_t)n_threads : pool.size() + 1;
-  nt = std::min(nt, items);
-  if (nt <= 1) work(); else pool.run(work, nt);
-}
-
 int lincomb_pool_jac(const uint8_t* bases_affine96, size_t n_bases, const uint32_t* offsets, const uint32_t* term_base, const uint8_t* term_scalars32,
                      const uint32_t* sel, size_t n_sel, jac* results, int n_threads) {
   if (n_sel == 0) return 0;
@@ -300,20 +293,19 @@ int lincomb_pool_jac(const uint8_t* bases_affine96, size_t n_bases, const uint32
     }
     n_threads = (int)std::max<double>(1.0, std::min<double>(256.0, ops / 400.0));
   }
+  // the one loop with per-thread scratch of the call's size (max_k): pool_for hands out the WORKERS, and they share a counter of their own
+  const size_t workers = std::min<size_t>((size_t)n_threads, n_sel);
   std::atomic<size_t> next{0};
-  std::function<void()> work = [&]() {
+  cg1::pool_for(workers, (int)workers, [&](size_t) {
     std::vector<uint32_t> idx(max_k);
     std::vector<uint8_t> neg(max_k);
-    for (;;) {
-      const size_t q = next.fetch_add(1);
-      if (q >= n_sel) return;
+    for (size_t q; (q = next.fetch_add(1)) < n_sel;) {
       const size_t j = sel ? sel[q] : q;
       const size_t lo = offsets[j], k = offsets[j + 1] - lo;
       for (size_t t = 0; t < k; ++t) { idx[t] = term_base[lo + t] & 0x7fffffffu; neg[t] = (uint8_t)(term_base[lo + t] >> 31); }
       results[j] = lincomb_one(pts.data(), idx.data(), neg.data(), term_scalars32 + 32 * lo, k);
     }
-  };
-  run_pool(work, n_sel, n_threads);
+  });
   return 0;
 }
 
@@ -323,7 +315,7 @@ int lincomb_pool_jac(const uint8_t* bases_affine96, size_t n_bases, const uint32
 namespace {
 
 using cg1h::aff; using cg1h::fe; using cg1h::jac;
-using cg1h::load_affine96; using cg1h::run_pool;
+using cg1h::load_affine96;
 
 }  // namespace
 
@@ -348,34 +340,28 @@ int cg1_fp_jacobi(const uint8_t* le48) {
 int cg1_batch_decompress_pool(const uint8_t* in48, size_t n, uint8_t* out_blobs144, uint8_t* out_affine96, int n_threads, size_t* bad_index) {
   if (n == 0) return CG1_OK;
   if (!in48) return CG1_ERR_ARG;
-  std::atomic<size_t> next{0};
   std::atomic<size_t> bad{(size_t)-1};
   std::atomic<int> bad_rc{0};
   const size_t slice = 8, items = (n + slice - 1) / slice;
   if (n_threads <= 0) n_threads = (int)std::max<size_t>(1, std::min<size_t>(256, n / 8));        // ~0.1 ms of square roots per thread
-  std::function<void()> work = [&]() {
-    for (;;) {
-      const size_t it = next.fetch_add(1);
-      if (it >= items) return;
-      for (size_t i = it * slice; i < std::min(n, it * slice + slice); ++i) {
-        jac p;
-        const int rc = cg1h::g1_decompress(in48 + 48 * i, false, p);
-        if (rc != 0) {
-          size_t cur = bad.load();
-          while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
-          if (bad.load() == i) bad_rc.store(rc == 3 ? CG1_ERR_NOT_ON_CURVE : CG1_ERR_ENCODING);
-          p = cg1h::jac_identity();
-        }
-        if (out_blobs144) memcpy(out_blobs144 + CG1_POINT_BYTES * i, &p, sizeof p);
-        if (out_affine96) {
-          uint8_t* o = out_affine96 + 96 * i;
-          if (cg1h::jac_is_identity(p)) memset(o, 0, 96);
-          else { cg1h::fe_to_le48(p.X, o); cg1h::fe_to_le48(p.Y, o + 48); }      // decoded points are in normal form (Z = 1)
-        }
+  cg1::pool_for(items, n_threads, [&](size_t it) {
+    for (size_t i = it * slice; i < std::min(n, it * slice + slice); ++i) {
+      jac p;
+      const int rc = cg1h::g1_decompress(in48 + 48 * i, false, p);
+      if (rc != 0) {
+        size_t cur = bad.load();
+        while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
+        if (bad.load() == i) bad_rc.store(rc == 3 ? CG1_ERR_NOT_ON_CURVE : CG1_ERR_ENCODING);
+        p = cg1h::jac_identity();
+      }
+      if (out_blobs144) memcpy(out_blobs144 + CG1_POINT_BYTES * i, &p, sizeof p);
+      if (out_affine96) {
+        uint8_t* o = out_affine96 + 96 * i;
+        if (cg1h::jac_is_identity(p)) memset(o, 0, 96);
+        else { cg1h::fe_to_le48(p.X, o); cg1h::fe_to_le48(p.Y, o + 48); }      // decoded points are in normal form (Z = 1)
       }
     }
-  };
-  run_pool(work, items, n_threads);
+  });
   if (bad.load() != (size_t)-1) { if (bad_index) *bad_index = bad.load(); return bad_rc.load() ? bad_rc.load() : CG1_ERR_ENCODING; }
   return CG1_OK;
 }
@@ -383,22 +369,16 @@ int cg1_batch_decompress_pool(const uint8_t* in48, size_t n, uint8_t* out_blobs1
 int cg1_batch_subgroup_pool(const uint8_t* affine96, size_t n, uint8_t* out_flags, int n_threads) {
   if (n == 0) return CG1_OK;
   if (!affine96 || !out_flags) return CG1_ERR_ARG;
-  std::atomic<size_t> next{0};
   std::atomic<int> bad{0};
   const size_t slice = 4, items = (n + slice - 1) / slice;
   if (n_threads <= 0) n_threads = (int)std::max<size_t>(1, std::min<size_t>(256, n / 3));        // ~0.1 ms of subgroup tests per thread
-  std::function<void()> work = [&]() {
-    for (;;) {
-      const size_t it = next.fetch_add(1);
-      if (it >= items) return;
-      for (size_t i = it * slice; i < std::min(n, it * slice + slice); ++i) {
-        aff a;
-        if (!load_affine96(affine96 + 96 * i, a)) { bad.store(1); out_flags[i] = 0; continue; }
-        out_flags[i] = a.inf ? 1 : (cg1h::g1_in_subgroup_fast(a.x, a.y) ? 1 : 0);
-      }
+  cg1::pool_for(items, n_threads, [&](size_t it) {
+    for (size_t i = it * slice; i < std::min(n, it * slice + slice); ++i) {
+      aff a;
+      if (!load_affine96(affine96 + 96 * i, a)) { bad.store(1); out_flags[i] = 0; continue; }
+      out_flags[i] = a.inf ? 1 : (cg1h::g1_in_subgroup_fast(a.x, a.y) ? 1 : 0);
     }
-  };
-  run_pool(work, items, n_threads);
+  });
   return bad.load() ? CG1_ERR_ENCODING : CG1_OK;
 }
 
@@ -888,10 +868,9 @@ int cg1_whisk_shuffle_draws(size_t ell, size_t n_provers, const uint8_t* seed32,
     uint32_t* perm = out_perm + (size_t)p * L;
     for (uint32_t i = 0; i < L; ++i) perm[i] = i;
     for (uint32_t d = 0; d < D; ++d) {
-      alignas(8) uint8_t st[200] = {0};
-      cg1whisk_host::draw_message(seed32, (uint32_t)(first_index + p), d, st);
-      st[135] ^= 0x80;
-      cg1_keccak_f1600(st);
+      uint8_t msg[64], st[64];
+      cg1whisk_host::draw_message(seed32, (uint32_t)(first_index + p), d, msg);
+      cg1::shake256_block64(msg, 62, st);                      // (draw_message's byte 62 is the domain byte the helper sets)
       if (d + 1 < L) {
         uint64_t lo, hi;
         memcpy(&lo, st, 8); memcpy(&hi, st + 8, 8);
@@ -900,7 +879,7 @@ int cg1_whisk_shuffle_draws(size_t ell, size_t n_provers, const uint8_t* seed32,
       } else {
         cg1fr::fr_to_le32(cg1fr::fr_from_le64_wide(st), out_scalars32 + 32 * cg1whisk_host::draw_slot(L, P, p, d - (L - 1)));
       }
-      memset(st, 0, sizeof st);
+      cg1::wipe(msg, sizeof msg); cg1::wipe(st, sizeof st);
     }
   }
   return CG1_OK;

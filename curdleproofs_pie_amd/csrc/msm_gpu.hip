@@ -47,6 +47,7 @@
 #include "host_g1.h"
 #include "lazy_host.h"
 #include "pool.h"
+#include "secret_wipe.h"
 #include "../../include/curdle_g1.h"
 
 namespace cg1 {

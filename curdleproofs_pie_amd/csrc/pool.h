@@ -3,6 +3,7 @@
 #pragma once
 #include <pthread.h>
 #include <sched.h>
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -106,5 +107,21 @@ class Pool {
   const std::function<void()>* job_ = nullptr;
   size_t want_ = 0, pending_ = 0, generation_ = 0;
 };
+
+// body(i) for every i in 0 .. items - 1, handed out one at a time to up to n_threads threads (the caller's among them; n_threads <= 0:
+// the whole pool and the caller; never more threads than items).  One thread or one item runs on the caller's thread and does not wake
+// the pool.  Slices: pass the slice count and loop over the slice in `body`.  A template: one std::function per call, none per item.
+template <typename F>
+void pool_for(size_t items, int n_threads, F&& body) {
+  size_t nt = 1;
+  if (n_threads != 1 && items > 1) nt = std::min({items, Pool::get().size() + 1, n_threads > 0 ? (size_t)n_threads : items});
+  if (nt <= 1) {
+    for (size_t i = 0; i < items; ++i) body(i);
+    return;
+  }
+  std::atomic<size_t> next{0};
+  const std::function<void()> work = [&] { for (size_t i; (i = next.fetch_add(1)) < items;) body(i); };
+  Pool::get().run(work, nt);
+}
 
 }  // namespace cg1

@@ -41,6 +41,7 @@
 #include "host_g1.h"
 #include "merlin_group.h"
 #include "pool.h"
+#include "secret_wipe.h"
 
 using namespace cg1fr;
 using cg1h::jac;
@@ -903,13 +904,9 @@ static int prepare_dispatch(const cg1_shuffle_crs* crs_, size_t n_proofs, const 
   const Layout L(crs.ell, crs.lg);
   const size_t inst_b = 4 * crs.ell * 48, proof_b = proof_wire_bytes(crs.lg), nch = 8 + 2 * crs.lg + crs.ell;
   const size_t rin_b = rowin_scalars(crs.ell, crs.lg) * 32;
-  std::atomic<size_t> next{0};
   const bool grouped = g_grouped.load() != 0;
   const size_t per_item = grouped ? (size_t)cg1m::G : 1, n_items = (n_proofs + per_item - 1) / per_item;
-  auto work = [&]() {
-    for (;;) {
-      const size_t item = next.fetch_add(1);
-      if (item >= n_items) return;
+  cg1::pool_for(n_items, n_threads, [&](size_t item) {
       if (grouped) {
         const size_t lo = item * per_item, cnt = std::min(per_item, n_proofs - lo);
         const uint8_t *in[cg1m::G], *pr[cg1m::G], *we[cg1m::G], *de[cg1m::G];
@@ -927,7 +924,7 @@ static int prepare_dispatch(const cg1_shuffle_crs* crs_, size_t n_proofs, const 
           sts[k] = status + i;
         }
         prepare_group(crs, (int)cnt, in, pr, we, de, pts, scs, ccs, chs, sts, out_rowin ? rin : nullptr);
-        continue;
+        return;
       }
       const size_t i = item;
       uint8_t* pts = out_points48 + i * L.count() * 48;
@@ -941,16 +938,7 @@ static int prepare_dispatch(const cg1_shuffle_crs* crs_, size_t n_proofs, const 
         else { memset(scs, 0, L.count() * 32); memset(ccs, 0, L.ncrs() * 32); }
       }
       status[i] = rc;
-    }
-  };
-  if (n_threads == 1 || n_items <= 1) {
-    work();
-  } else {
-    Pool& pool = Pool::get();
-    size_t nt = n_threads > 0 ? (size_t)n_threads : pool.size() + 1;
-    if (nt > n_items) nt = n_items;
-    pool.run(work, nt);
-  }
+  });
   return CG1_OK;
 }
 
@@ -1014,21 +1002,8 @@ int cg1_opening_prepare(size_t n, const uint8_t* trackers, const uint8_t* k_comm
     fr_to_le32(fr_mul(r1, s_), gs);                // G
     status[i] = 0;
   };
-  if (n < 256) {
-    for (size_t i = 0; i < n; ++i) one(i);
-  } else {                                                    // slices of 64 proofs over the worker pool
-    std::atomic<size_t> next{0};
-    const size_t items = (n + 63) / 64;
-    std::function<void()> work = [&]() {
-      for (;;) {
-        const size_t it = next.fetch_add(1);
-        if (it >= items) return;
-        for (size_t i = it * 64; i < std::min(n, it * 64 + 64); ++i) one(i);
-      }
-    };
-    Pool& pool = Pool::get();
-    pool.run(work, std::min(items, pool.size() + 1));
-  }
+  // slices of 64 proofs over the worker pool; fewer than 256 proofs on the caller's thread
+  cg1::pool_for((n + 63) / 64, n < 256 ? 1 : 0, [&](size_t it) { for (size_t i = it * 64; i < std::min(n, it * 64 + 64); ++i) one(i); });
   return CG1_OK;
 }
 
@@ -1076,21 +1051,8 @@ int cg1_opening_prove(size_t n, const uint8_t* trackers96, const uint8_t* ks32, 
     memcpy(kc, row, 48);
     status[i] = 0;
   };
-  if (n < 8) {
-    for (size_t i = 0; i < n; ++i) one(i);
-    return CG1_OK;
-  }
-  std::atomic<size_t> next{0};
-  const size_t items = (n + 3) / 4;                            // slices of 4 proofs (~0.1 ms each)
-  std::function<void()> work = [&]() {
-    for (;;) {
-      const size_t it = next.fetch_add(1);
-      if (it >= items) return;
-      for (size_t i = it * 4; i < std::min(n, it * 4 + 4); ++i) one(i);
-    }
-  };
-  Pool& pool = Pool::get();
-  pool.run(work, std::min(items, pool.size() + 1));
+  // slices of 4 proofs (~0.1 ms each) over the worker pool; fewer than 8 proofs on the caller's thread
+  cg1::pool_for((n + 3) / 4, n < 8 ? 1 : 0, [&](size_t it) { for (size_t i = it * 4; i < std::min(n, it * 4 + 4); ++i) one(i); });
   return CG1_OK;
 }
 
@@ -1104,7 +1066,6 @@ int cg1_batch_mul_add_pool(const uint8_t* bases, size_t nbase, const uint8_t* sc
   if (!bases || !scalars || !out || nbase == 0 || nscalars == 0) return CG1_ERR_ARG;
   using cg1h::fe; using cg1h::jac;
   std::atomic<int> bad{0};
-  std::atomic<size_t> next{0};
   const size_t slice = 16, items = (n + slice - 1) / slice;
   auto load = [&](const uint8_t* rec, jac& o) {
     bool zero = true;
@@ -1115,13 +1076,10 @@ int cg1_batch_mul_add_pool(const uint8_t* bases, size_t nbase, const uint8_t* sc
     o = cg1h::jac_from_affine(x, y);
     return true;
   };
-  std::function<void()> work = [&]() {
-    jac acc[slice];
-    fe xs[slice], ys[slice];
-    uint8_t inf[slice];
-    for (;;) {
-      const size_t it = next.fetch_add(1);
-      if (it >= items) return;
+  cg1::pool_for(items, n_threads, [&](size_t it) {
+      jac acc[slice];
+      fe xs[slice], ys[slice];
+      uint8_t inf[slice];
       const size_t lo = it * slice, cnt = std::min(slice, n - lo);
       for (size_t k = 0; k < cnt; ++k) {
         const size_t i = lo + k;
@@ -1136,12 +1094,7 @@ int cg1_batch_mul_add_pool(const uint8_t* bases, size_t nbase, const uint8_t* sc
         cg1h::fe_to_le48(xs[k], o);
         cg1h::fe_to_le48(ys[k], o + 48);
       }
-    }
-  };
-  Pool& pool = Pool::get();
-  size_t nt = n_threads > 0 ? (size_t)n_threads : pool.size() + 1;
-  nt = std::min(nt, items);
-  if (nt <= 1) work(); else pool.run(work, nt);
+  });
   return bad.load() ? CG1_ERR_ENCODING : CG1_OK;
 }
 
@@ -1150,18 +1103,16 @@ int cg1_batch_mul_add_pool(const uint8_t* bases, size_t nbase, const uint8_t* sc
 int cg1_opening_weights_from_seed(const uint8_t seed32[32], size_t first, size_t n, uint8_t* out_weights64) {
   if (!seed32 || (n && !out_weights64)) return CG1_ERR_ARG;
   for (size_t k = 0; k < n; ++k) {
-    uint8_t st[200];
-    memset(st, 0, sizeof st);
-    memcpy(st, seed32, 32);
+    uint8_t msg[40], st[64];
+    memcpy(msg, seed32, 32);
     const uint64_t i = (uint64_t)(first + k);
-    for (int b = 0; b < 8; ++b) st[32 + b] = (uint8_t)(i >> (8 * b));
-    st[40] ^= 0x1F;
-    st[135] ^= 0x80;
-    cg1_keccak_f1600(st);
+    for (int b = 0; b < 8; ++b) msg[32 + b] = (uint8_t)(i >> (8 * b));
+    cg1::shake256_block64(msg, sizeof msg, st);
     uint8_t* o = out_weights64 + 64 * k;
     memset(o, 0, 64);
     memcpy(o, st, 16);
     memcpy(o + 32, st + 16, 16);
+    cg1::wipe(msg, sizeof msg); cg1::wipe(st, sizeof st);
   }
   return CG1_OK;
 }
@@ -1195,16 +1146,6 @@ void opening_challenge(const uint8_t* tracker96, const uint8_t* k_commitment48, 
   for (const uint8_t* p : order) tr.point("tracker_opening_proof", p);
   fr_to_le32(tr.challenge("tracker_opening_proof_challenge"), c32);
 }
-
-// items 0 .. n-1 over the worker pool (n_threads <= 0: the whole pool and the caller)
-void exact_spread(size_t n, int n_threads, const std::function<void(size_t)>& one) {
-  std::atomic<size_t> next{0};
-  std::function<void()> work = [&]() { for (;;) { const size_t i = next.fetch_add(1); if (i >= n) return; one(i); } };
-  Pool& pool = Pool::get();
-  size_t nt = n_threads > 0 ? (size_t)n_threads : pool.size() + 1;
-  nt = std::min(nt, n);
-  if (nt <= 1) work(); else pool.run(work, nt);
-}
 }  // namespace
 }  // extern "C++"
 
@@ -1225,7 +1166,7 @@ int cg1_exact_relations(const uint8_t* points96, size_t n_points, const uint8_t*
   // decode every point once (a relation names a point by index, and relations share points)
   std::vector<jac> P(n_points);
   std::atomic<int> bad{0};
-  exact_spread(n_points, n_threads, [&](size_t i) {
+  cg1::pool_for(n_points, n_threads, [&](size_t i) {
     const uint8_t* b = points96 + 96 * i;
     bool any = false;
     for (int t = 0; t < 96; ++t) any = any || b[t];
@@ -1235,7 +1176,7 @@ int cg1_exact_relations(const uint8_t* points96, size_t n_points, const uint8_t*
     else P[i] = cg1h::jac_from_affine(x, y);
   });
   if (bad.load()) return CG1_ERR_ENCODING;
-  exact_spread(n_relations, n_threads, [&](size_t i) {
+  cg1::pool_for(n_relations, n_threads, [&](size_t i) {
     ExactOperand ops[CG1_EXACT_TERMS];
     size_t cnt = 0;
     for (size_t j = 0; j < CG1_EXACT_TERMS; ++j) {
@@ -1251,7 +1192,7 @@ int cg1_exact_relations(const uint8_t* points96, size_t n_points, const uint8_t*
 int cg1_opening_challenges(const uint8_t* trackers96, const uint8_t* k_commitments48, const uint8_t* proofs128, size_t n, uint8_t* out_c32,
                            int n_threads) {
   if (n && (!trackers96 || !k_commitments48 || !proofs128 || !out_c32)) return CG1_ERR_ARG;
-  exact_spread(n, n_threads, [&](size_t i) { opening_challenge(trackers96 + 96 * i, k_commitments48 + 48 * i, proofs128 + 128 * i, out_c32 + 32 * i); });
+  cg1::pool_for(n, n_threads, [&](size_t i) { opening_challenge(trackers96 + 96 * i, k_commitments48 + 48 * i, proofs128 + 128 * i, out_c32 + 32 * i); });
   return CG1_OK;
 }
 

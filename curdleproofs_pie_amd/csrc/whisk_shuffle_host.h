@@ -1,10 +1,12 @@
 // The refusals cg1_whisk_shuffle_front (capi_whisk_shuffle.h, on the device) and cg1_whisk_shuffle_front_emulate (lazy_host.cpp, its host
 // twin for the CPU tests) share: one set of checks and one set of texts, so that the two cannot drift apart.  Host only, but for the few
 // functions marked CG1WHISK_HD: the format of the seeded draws, which the device kernels (kernels_whisk_shuffle.h) and the host twin share.
+// Also the column table of a shuffle's witness and the view over it (ShuffleWitness) that every host entry of the Whisk provers passes on.
 #pragma once
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include "secret_wipe.h"
 #include "../../include/curdle_g1.h"
 
 namespace cg1whisk_host {
@@ -73,16 +75,23 @@ static_assert(sizeof DRAW_DOMAIN == DRAW_DOMAIN_LEN + 1, "");
 CG1WHISK_HD uint32_t draw_scalars(uint32_t ell) { return 3u * (ell + (uint32_t)N_BLINDERS) + 14u; }        // per shuffle
 CG1WHISK_HD uint32_t draw_count(uint32_t ell) { return ell - 1u + draw_scalars(ell); }                    // D = ell + 3 n + 13
 
+// THE COLUMN TABLE: the eight scalar columns of a shuffle's witness in the order the draws fill them, and the scalars a prover's row of
+// each holds (n = ell + 4).  Everything on the host that cuts, gathers or sizes a column reads the widths here.
+enum Column { COL_K, COL_MBL, COL_ABL, COL_CBL, COL_IPA_R, COL_Z_HEAD, COL_BL, COL_VEC_R, N_COLUMNS };
+inline size_t column_width(int column, size_t n) {
+  const size_t width[N_COLUMNS] = {1, N_BLINDERS, 2, N_BLINDERS, n, n - 2, 5, n};
+  return width[column];
+}
 // where the columns begin, in scalars, for P provers: k | vec_m_blinders | vec_a_blinders | vec_c_blinders | ipa_r | ipa_z_head | blinders | vec_r
-struct DrawColumns { size_t k, mbl, abl, cbl, ipa_r, z_head, bl, vec_r, total; };
+struct DrawColumns { size_t at[N_COLUMNS], total; };
 inline DrawColumns draw_columns(size_t ell, size_t P) {
-  const size_t n = ell + N_BLINDERS;
   DrawColumns c;
-  c.k = 0; c.mbl = P; c.abl = 5 * P; c.cbl = 7 * P; c.ipa_r = 11 * P; c.z_head = (11 + n) * P; c.bl = (9 + 2 * n) * P; c.vec_r = (14 + 2 * n) * P;
-  c.total = (14 + 3 * n) * P;
+  c.total = 0;
+  for (int col = 0; col < N_COLUMNS; ++col) { c.at[col] = c.total; c.total += P * column_width(col, ell + N_BLINDERS); }
   return c;
 }
-// the slot (in scalars) of scalar number s of prover p
+// the slot (in scalars) of scalar number s of prover p: the same table spelt out for the device (it compiles into k_whisk_draws);
+// tests/native/witness_gather.cpp holds the two against each other
 CG1WHISK_HD size_t draw_slot(uint32_t ell, uint32_t P, uint32_t p, uint32_t s) {
   const size_t n = ell + (uint32_t)N_BLINDERS, Pz = P, pz = p;
   if (s < 1u) return pz;
@@ -127,5 +136,51 @@ inline void m_scalar_row(size_t ell, const uint32_t* perm, const uint8_t* vec_m_
   for (size_t i = 0; i < ell; ++i) memcpy(out + 32 * i, perm + i, 4);
   memcpy(out + 32 * ell, vec_m_blinders32, 32 * N_BLINDERS);
 }
+
+// the draws' block on the device (ctx->d_whisk_draws): the Fisher-Yates swaps, the permutations, the scalars in the column layout, each on
+// a 64-byte boundary; the host staging of a seeded entry holds [perm, total)
+struct DrawBlock { size_t swaps, perm, scalars, total; };
+inline DrawBlock draw_block(size_t ell, size_t P) {
+  auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
+  DrawBlock B;
+  B.swaps = 0; B.perm = up(P * (ell - 1) * 4); B.scalars = B.perm + up(P * ell * 4);
+  B.total = B.scalars + draw_columns(ell, P).total * 32;
+  return B;
+}
+
+// The witness of P shuffles of one ell as the whole-shuffle prover takes it: the permutations (P rows of ell indices) and the eight scalar
+// columns (P rows of column_width scalars each).  A view: it owns nothing, and whoever owns the bytes wipes them.
+struct ShuffleWitness {
+  size_t ell, P;
+  const uint32_t* perm;
+  const uint8_t* col[N_COLUMNS];
+  // the permutations at `perm`, the columns one after the other from `scalars`
+  static ShuffleWitness over(const uint8_t* perm, const uint8_t* scalars, size_t ell, size_t P) {
+    const DrawColumns C = draw_columns(ell, P);
+    ShuffleWitness w{ell, P, reinterpret_cast<const uint32_t*>(perm), {}};
+    for (int c = 0; c < N_COLUMNS; ++c) w.col[c] = scalars + 32 * C.at[c];
+    return w;
+  }
+  // over the staging the draws of P shuffles come down into: [perm, total) of their DrawBlock
+  static ShuffleWitness of_draws(const uint8_t* stage, size_t ell, size_t P) {
+    const DrawBlock B = draw_block(ell, P);
+    return over(stage, stage + (B.scalars - B.perm), ell, P);
+  }
+  // the rows keep[0] < keep[1] < .. < keep[Q - 1] of every column copied into `into`; all P rows: this view itself, and no copy
+  ShuffleWitness gather(const size_t* keep, size_t Q, cg1::WipedBytes& into) const {
+    if (Q == P) return *this;
+    into.v.assign(Q * ell * 4 + 32 * draw_columns(ell, Q).total, 0);
+    uint8_t* base = into.v.data();
+    const ShuffleWitness w = over(base, base + Q * ell * 4, ell, Q);
+    for (size_t q = 0; q < Q; ++q) {
+      memcpy(base + q * ell * 4, perm + keep[q] * ell, ell * 4);
+      for (int c = 0; c < N_COLUMNS; ++c) {
+        const size_t row = 32 * column_width(c, ell + N_BLINDERS);
+        memcpy(base + (w.col[c] - base) + q * row, col[c] + keep[q] * row, row);
+      }
+    }
+    return w;
+  }
+};
 
 }  // namespace cg1whisk_host

@@ -1,8 +1,10 @@
 // ASan/UBSan driver for the shuffle-verifier front-end (csrc/shuffle_verify.cpp): a golden proof, bit-flipped
-// copies of it and random garbage through cg1_shuffle_prepare, single- and multi-threaded.  Input file (written by
-// tests/test_sanitizers.py from tests/golden/shuffle_vectors.json): u64 ell | crs bytes | instance | proof.
+// copies of it and random garbage through cg1_shuffle_prepare, single- and multi-threaded; then the other loops of that file
+// over the worker pool: cg1_opening_prepare, and cg1_opening_prove and cg1_batch_mul_add_pool each against its single-thread result.
+// Input file (written by tests/test_sanitizers.py from tests/golden/shuffle_vectors.json): u64 ell | crs bytes | instance | proof.
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -13,6 +15,7 @@ static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 
 
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
+  setenv("CURDLE_G1_THREADS", "4", 1);      // the pool is sized at its first use: four threads wherever this runs, for the entries that take no thread count
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
   uint64_t ell = 0;
@@ -83,6 +86,41 @@ int main(int argc, char** argv) {
     size_t okc = 0;
     for (size_t i = 0; i < m; ++i) okc += ost[i] == 0;
     printf("opening front-end prepared %zu of %zu\n", okc, m);
+  }
+  {   // the opening prover: 9 proofs -- one above its serial threshold of 8: two slices of 4 and a last slice of one over the pool --
+      // against the same 9 proved one call each (below the threshold: the caller's thread alone).  The trackers are points of the instance.
+    const size_t m = 9, npts = 4 * ell;
+    std::vector<uint8_t> trk(m * 96), ks(m * 32), bl(m * 32), pf(m * 128), kc(m * 48), pf1(m * 128), kc1(m * 48);
+    std::vector<int32_t> ost(m), ost1(m);
+    for (size_t i = 0; i < m; ++i) {
+      memcpy(&trk[96 * i], &inst[48 * (i % npts)], 48);
+      memcpy(&trk[96 * i + 48], &inst[48 * ((i + 5) % npts)], 48);
+    }
+    for (auto& b : ks) b = (uint8_t)rnd();
+    for (auto& b : bl) b = (uint8_t)rnd();
+    for (size_t i = 31; i < m * 32; i += 32) { ks[i] &= 0x3f; bl[i] &= 0x3f; }
+    if (cg1_opening_prove(m, trk.data(), ks.data(), bl.data(), pf.data(), kc.data(), ost.data())) return 1;
+    for (size_t i = 0; i < m; ++i)
+      if (cg1_opening_prove(1, &trk[96 * i], &ks[32 * i], &bl[32 * i], &pf1[128 * i], &kc1[48 * i], &ost1[i])) return 1;
+    for (size_t i = 0; i < m; ++i)
+      if (ost[i] != 0) { printf("opening prover refused item %zu (%d)\n", i, ost[i]); return 1; }
+    if (ost != ost1 || pf != pf1 || kc != kc1) { printf("opening prover: the pool and the caller's thread disagree\n"); return 1; }
+  }
+  {   // out = addend + scalar * base on the pool: 17 items -- two slices of 16, the last of one -- at 1 and 4 threads.  The records are
+      // taken as given (coordinates below p, never checked against the curve); record 3 is the identity.
+    const size_t m = 17, nbase = 5, nsc = 7;
+    std::vector<uint8_t> bases(nbase * 96), scs(nsc * 32), add(m * 96), o1(m * 96, 0xAA), o4(m * 96, 0x55), o0(m * 96, 0x33);
+    for (auto& b : bases) b = (uint8_t)rnd();
+    for (auto& b : add) b = (uint8_t)rnd();
+    for (auto& b : scs) b = (uint8_t)rnd();
+    for (size_t i = 47; i < bases.size(); i += 48) bases[i] &= 0x0f;
+    for (size_t i = 47; i < add.size(); i += 48) add[i] &= 0x0f;
+    memset(&bases[96 * 3], 0, 96);
+    memset(&add[96 * 16], 0, 96);
+    if (cg1_batch_mul_add_pool(bases.data(), nbase, scs.data(), nsc, add.data(), o1.data(), m, 1)) return 1;
+    if (cg1_batch_mul_add_pool(bases.data(), nbase, scs.data(), nsc, add.data(), o4.data(), m, 4)) return 1;
+    if (cg1_batch_mul_add_pool(bases.data(), nbase, scs.data(), nsc, add.data(), o0.data(), m, 0)) return 1;
+    if (o1 != o4 || o1 != o0) { printf("batch_mul_add_pool: thread counts disagree\n"); return 1; }
   }
   cg1_shuffle_crs_destroy(crs);
   printf("sanitize ok\n");

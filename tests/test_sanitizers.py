@@ -74,6 +74,20 @@ def test_shuffle_front_end_under_asan_ubsan(tmp_path):
     assert "sanitize ok" in r.stdout
 
 
+def test_shuffle_witness_gather_under_asan_ubsan():
+    """csrc/whisk_shuffle_host.h + csrc/secret_wipe.h alone: the witness view over a draw block and its gather by `keep` (all, none, first,
+    last, two and three of five provers; n = 8 and n = 16), every row held against draw_slot and the widths of the format's comment."""
+    out_dir = os.path.join(ROOT, "tests", "native", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "witness_gather")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "native", "witness_gather.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300,
+                       env={**os.environ, "ASAN_OPTIONS": "detect_leaks=1", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "sanitize ok" in r.stdout
+
+
 import pytest
 
 

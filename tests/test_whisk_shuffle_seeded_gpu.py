@@ -198,6 +198,27 @@ def test_a_bad_tracker_refuses_its_own_shuffle_only(native_lib, kits):
     assert by_definition(kit, lists[:1], S.SEED_A)[1] == item(clean[1], wb, 0)                          # ... and prove_many after it
 
 
+def test_a_refused_first_or_last_item_leaves_the_others_their_own_draws(native_lib, kits):
+    """Batches of three at ell = 4 with the refused item first, then last: the two survivors move up by one row, or not at all, in every
+    column of the witness, and each still gets the proof of prove_many fed the draws of ITS index."""
+    N = native_lib
+    kit = kits(4)
+    ell, lists = 4, kit.lists(3)
+    wb = N.cg1_whisk_shuffle_proof_bytes(ell)
+    item = lambda buf, size, p: buf[size * p: size * (p + 1)]
+    want = [by_definition(kit, [lists[i]], S.SEED_A, i) for i in range(3)]
+    for bad in (0, 2):
+        batch = list(lists)
+        batch[bad] = [lists[bad][0], (W.torsion_encoding(), lists[bad][1][1])] + lists[bad][2:]
+        post, proofs, status = kit.prover.generate_packed(flat(batch), seed=S.SEED_A)
+        assert status == [3 if p == bad else 0 for p in range(3)], (bad, status)
+        for p in range(3):
+            if p == bad:
+                assert item(post, 96 * ell, p) == bytes(96 * ell) and item(proofs, wb, p) == bytes(wb), (bad, p)
+            else:
+                assert (item(post, 96 * ell, p), item(proofs, wb, p)) == want[p], (bad, p)
+
+
 def test_the_batch_verifier_accepts_fresh_seeds(native_lib, kits):
     """Eight shuffles at ell = 28 under seed=None go into are_valid_whisk_shuffle_proofs as they come out; one post tracker replaced by the
     encoding of the negated point (the edit of test_whisk_shuffle_prover_gpu.test_the_batch_verifier_accepts) rejects that item only."""
