@@ -364,6 +364,10 @@ cg1_whisk_shuffle_draws_device = _proto("cg1_whisk_shuffle_draws_device", c_int,
 cg1_whisk_shuffle_draws = _proto("cg1_whisk_shuffle_draws", c_int, c_size_t, c_size_t, c_void_p, ctypes.c_uint64, c_void_p, c_void_p)
 cg1_whisk_shuffle_prove_seeded = _proto("cg1_whisk_shuffle_prove_seeded", c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p)
+cg1_whisk_last_witness_traffic = _proto("cg1_whisk_last_witness_traffic", None, c_void_p, c_void_p)
+cg1_whisk_draws_buffer_is_zero = _proto("cg1_whisk_draws_buffer_is_zero", c_int, c_void_p)
+cg1_whisk_witness_block_emulate = _proto("cg1_whisk_witness_block_emulate", c_size_t, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_size_t,
+                                         c_void_p, c_void_p)
 WHISK_SHUFFLE_DRAWS_MAX_PROVERS, WHISK_SHUFFLE_NO_DECODE, WHISK_SHUFFLE_NOT_G1 = 4096, 2, 3      # CG1_WHISK_SHUFFLE_* of include/curdle_g1.h
 # a chain of shuffles over a device-resident tracker set (csrc/kernels_tracker_set.h, csrc/capi_tracker_set.h; cg1_chain_expand: csrc/shuffle_verify.cpp)
 cg1_chain_expand = _proto("cg1_chain_expand", c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, POINTER(c_size_t))
@@ -408,6 +412,7 @@ EXPORTED_SYMBOLS = [
     "cg1_shuffle_prover_proof_bytes", "cg1_shuffle_prove_device", "cg1_shuffle_begin_emulate",
     "cg1_whisk_shuffle_proof_bytes", "cg1_whisk_shuffle_front", "cg1_whisk_shuffle_prove_device", "cg1_whisk_shuffle_front_emulate",
     "cg1_whisk_shuffle_draws_device", "cg1_whisk_shuffle_draws", "cg1_whisk_shuffle_prove_seeded",
+    "cg1_whisk_last_witness_traffic", "cg1_whisk_draws_buffer_is_zero", "cg1_whisk_witness_block_emulate",
     "cg1_tracker_match_device", "cg1_tracker_match", "cg1_tracker_match_last_ms",
     "cg1_whisk_register_device", "cg1_whisk_register", "cg1_whisk_register_draws", "cg1_whisk_register_points_device",
     "cg1_exact_relations_check", "cg1_exact_relations", "cg1_exact_relations_device", "cg1_exact_gather_device", "cg1_opening_challenges",

@@ -291,6 +291,7 @@ void* cg1_ctx_stream(cg1_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; 
 int cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value) {
   if (!ctx || !name) return CG1_ERR_ARG;
   if (!strcmp(name, "alloc_fail_at")) { if (value < 0) return CG1_ERR_ARG; ctx->alloc_fail_at = value; return CG1_OK; }
+  if (!strcmp(name, "whisk_resident_witness")) { if (value != 0 && value != 1) return CG1_ERR_ARG; ctx->whisk_resident = value; return CG1_OK; }
   if (!strcmp(name, "chunk_rule")) { ctx->chunk_rule = value != 0; return CG1_OK; }
   if (!strcmp(name, "chunk_len")) { if (value < 1 || value > 65536) return CG1_ERR_ARG; ctx->L0 = (uint32_t)value; cg1::free_bufs(ctx); return CG1_OK; }
   if (!strcmp(name, "stage_sort")) { ctx->stage_sort = value ? 1 : 0; return CG1_OK; }

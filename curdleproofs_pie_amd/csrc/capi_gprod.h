@@ -91,7 +91,7 @@ int gprod_check(cg1_ctx* ctx, const char* who, ChainOwnStatus own_status, const 
   if (P > CG1_IPA_MAX_PROVERS) { snprintf(ctx->err, sizeof ctx->err, "%s: more than %d provers in one call", who, CG1_IPA_MAX_PROVERS); return CG1_ERR_ARG; }
   if (const int rc = chain_check_indices(ctx, who, t, {{g_index, P * n}, {u_index, P}})) return rc;
   if (sp) {
-    for (size_t i = 0; i < P * ell; ++i)                    // the kernel gathers vec_a[perm[i]]; the reference's get_permutation raises IndexError
+    for (size_t i = 0; sp->perm && i < P * ell; ++i)        // the kernel gathers vec_a[perm[i]]; the reference's get_permutation raises IndexError
       if (sp->perm[i] >= ell) { snprintf(ctx->err, sizeof ctx->err, "%s: a permutation entry is >= ell", who); return CG1_ERR_ARG; }
     if (const int rc = chain_check_scalars(ctx, who, {{sp->vec_a32, P * ell}, {sp->vec_a_blinders32, P * nb}, {sp->vec_m_blinders32, P * nb}, {vec_c_blinders32, P * nb},
                                                       {ipa_r32, P * n}, {ipa_z_head32, P * (n - 2)}})) return rc;
@@ -99,21 +99,23 @@ int gprod_check(cg1_ctx* ctx, const char* who, ChainOwnStatus own_status, const 
     if (const int rc = chain_check_scalars(ctx, who, {{gprod_result32, P}, {vec_b32, P * n}, {vec_c_blinders32, P * nb}, {ipa_r32, P * n}, {ipa_z_head32, P * (n - 2)}})) return rc;
   }
   if (const int rc = chain_check_points(ctx, who, hashed48, P, per, names, canon)) return rc;
-  for (size_t p = 0; p < P; ++p) {                          // c[n-2], the first denominator of generate_ipa_blinders (ipa.py:36)
+  for (size_t p = 0; vec_c_blinders32 && p < P; ++p) {      // c[n-2], the first denominator of generate_ipa_blinders (ipa.py:36)
     static const uint8_t zero[32] = {0};
     if (memcmp(vec_c_blinders32 + 32 * (p * nb + nb - 2), zero, 32) == 0) return own_status(ctx, who, cg1gprod::ST_ZERO_C);
   }
   return CG1_OK;
 }
 // ---- the inputs into the block, but for the same-permutation head's vec_a, A | M and challenges (same_perm_head).  canon_b: B as the
-// transcript absorbs it (the grand-product argument only)
+// transcript absorbs it (the grand-product argument only).  A null witness list (vec_c_blinders32, ipa_r32, ipa_z_head32, sp's perm and
+// blinders): its field is not written here -- a resident witness, placed on the device (k_whisk_witness_place)
 void gprod_stage(uint8_t* H, const GprodPlan& g, const uint32_t* g_index, const uint32_t* u_index, const SamePermHead* sp, const uint8_t* canon_b,
                  const uint8_t* gprod_result32, const uint8_t* vec_b32, const uint8_t* vec_c_blinders32, const uint8_t* ipa_r32, const uint8_t* ipa_z_head32) {
   const GprodLayout& L = g.L;
   const size_t P = g.P, n = g.n, nb = g.nb, ell = g.ell;
   memcpy(H + L.gi, g_index, P * n * 4); memcpy(H + L.ui, u_index, P * 4);
   if (!sp) memcpy(H + L.vb, vec_b32, P * n * 32);
-  memcpy(H + L.cbl, vec_c_blinders32, P * nb * 32); memcpy(H + L.r, ipa_r32, P * n * 32);
+  if (vec_c_blinders32) memcpy(H + L.cbl, vec_c_blinders32, P * nb * 32);
+  if (ipa_r32) memcpy(H + L.r, ipa_r32, P * n * 32);
   const uint32_t nn = (uint32_t)n;
   uint32_t* offs_b = reinterpret_cast<uint32_t*>(H + L.offs_b);
   uint32_t* offs_s = reinterpret_cast<uint32_t*>(H + L.offs_s);
@@ -125,15 +127,17 @@ void gprod_stage(uint8_t* H, const GprodPlan& g, const uint32_t* g_index, const 
       memcpy(row, canon_b + 48 * p, 48);
       memcpy(row + 48, gprod_result32 + 32 * p, 32);
     }
-    uint8_t* z = H + L.z + p * n * 32;
-    memcpy(z, ipa_z_head32 + p * (n - 2) * 32, (n - 2) * 32);
-    memset(z + (n - 2) * 32, 0, 64);
+    if (ipa_z_head32) {
+      uint8_t* z = H + L.z + p * n * 32;
+      memcpy(z, ipa_z_head32 + p * (n - 2) * 32, (n - 2) * 32);
+      memset(z + (n - 2) * 32, 0, 64);
+    }
     if (sp) cg1sperm::begin_offsets(nn, (uint32_t)(p * cg1sperm::begin_terms(nn)), offs_b + 4 * p);
     else cg1gprod::begin_offsets(nn, (uint32_t)(p * cg1gprod::begin_terms(nn)), offs_b + 2 * p);
     cg1gprod::step_offsets(nn, (uint32_t)(p * cg1gprod::step_terms(nn)), offs_s + 3 * p);
     cg1ipa::round_offsets(nn, (uint32_t)(p * cg1ipa::round_terms(nn)), offsr + 4 * p);
   }
-  if (sp) {
+  if (sp && sp->perm) {
     memcpy(H + L.perm, sp->perm, P * ell * 4);
     memcpy(H + L.abl, sp->vec_a_blinders32, P * nb * 32); memcpy(H + L.mbl, sp->vec_m_blinders32, P * nb * 32);
   }

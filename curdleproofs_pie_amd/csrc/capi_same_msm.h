@@ -42,11 +42,12 @@ int smsm_check(cg1_ctx* ctx, const char* who, const cg1_fixed* t, bool pointers_
   cg1_batch_compress(tu48.data(), blobs.data(), P * 2 * n);
   return CG1_OK;
 }
-// ---- the inputs into the block (vec_x32 null: k_shuffle_begin writes the field on the device)
+// ---- the inputs into the block (vec_x32 null: k_shuffle_begin writes the field on the device; vec_r32 null: a resident witness, placed
+// on the device by k_whisk_witness_place)
 void smsm_stage(uint8_t* H, const SmsmLayout& L, size_t n, size_t P, const uint32_t* g_index, const uint8_t* tu_affine96, const uint8_t* vec_x32, const uint8_t* vec_r32) {
   memcpy(H + L.gi, g_index, P * n * 4);
   if (vec_x32) memcpy(H + L.vx, vec_x32, P * n * 32);
-  memcpy(H + L.vr, vec_r32, P * n * 32);
+  if (vec_r32) memcpy(H + L.vr, vec_r32, P * n * 32);
   memcpy(H + L.tu96, tu_affine96, P * 2 * n * 96);
   const uint32_t nn = (uint32_t)n, Pn = (uint32_t)P, hh = nn / 2;
   uint32_t* oa1 = reinterpret_cast<uint32_t*>(H + L.offs_a1);

@@ -54,14 +54,15 @@ int sscalar_check(cg1_ctx* ctx, const char* who, const cg1_fixed* t, bool pointe
   }
   return CG1_OK;
 }
-// ---- the inputs into the block (vec_a32 null: its field is filled by the caller)
+// ---- the inputs into the block (vec_a32 null: its field is filled by the caller; k32 and blinders32 null: a resident witness, placed on
+// the device by k_whisk_witness_place)
 void sscalar_stage(uint8_t* H, const SscalarLayout& L, size_t ell, size_t P, const uint8_t* gth_affine96, const uint8_t* rs_affine96, const uint8_t* vec_a32,
                    const uint8_t* k32, const uint8_t* blinders32) {
   const uint32_t el = (uint32_t)ell, Pn = (uint32_t)P, terms = cg1sscalar::terms(el);
   memcpy(H + L.bases96, gth_affine96, cg1sscalar::SHARED_BASES * 96);
   memcpy(H + L.bases96 + cg1sscalar::SHARED_BASES * 96, rs_affine96, P * 2 * ell * 96);
   if (vec_a32) memcpy(H + L.va, vec_a32, P * ell * 32);
-  memcpy(H + L.k, k32, P * 32); memcpy(H + L.bl, blinders32, P * 5 * 32);
+  if (k32) { memcpy(H + L.k, k32, P * 32); memcpy(H + L.bl, blinders32, P * 5 * 32); }
   uint32_t* offs = reinterpret_cast<uint32_t*>(H + L.offs);
   for (uint32_t p = 0; p < Pn; ++p) cg1sscalar::offsets(el, p * terms, offs + cg1sscalar::MSMS * p);
 }

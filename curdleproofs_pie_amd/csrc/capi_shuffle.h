@@ -71,6 +71,94 @@ struct ShuffleCrsRows {
   std::vector<uint32_t> own;
 };
 
+// The block of a whole shuffle for P provers: states | the entry's fields | same-scalar | same-permutation | same-MSM, laid end to end
+// behind the one states field.  shuffle_prove lays its block out by this, and so does the host emulation of the witness's placement
+// (cg1_whisk_witness_block_emulate): there is no second statement of the sequence.
+struct ShuffleBlock {
+  size_t states, pb_msm, total;
+  ShuffleLayout SH;
+  SscalarLayout SS;
+  GprodPlan gp;
+  SmsmLayout SM;
+};
+ShuffleBlock shuffle_block(size_t ell, size_t P) {
+  const size_t n = ell + cg1shuffle::N_BLINDERS;
+  ShuffleBlock B{};
+  ChainLayout C{};
+  B.states = C.take(P * 208);
+  B.SH = shuffle_layout(ell, P, C.total);
+  B.SS = sscalar_layout(ell, P, B.SH.total, B.states);
+  B.gp = gprod_plan(ell, cg1shuffle::N_BLINDERS, P, true, B.SS.total, B.states);
+  B.pb_msm = cg1_same_msm_proof_bytes(n);
+  B.SM = smsm_layout(n, P, B.pb_msm, B.gp.L.total, B.states);
+  B.total = B.SM.total;
+  return B;
+}
+
+// ---- a resident witness (ShuffleWitness::resident): its fields are placed on the device, not staged.
+// the fields of `block` that `phase` places (phase < 0: all of them), resolved for draws of draws_P provers; at[]: the fields' offsets in
+// the block, by PlaceFieldId
+size_t place_fields(int block, int phase, size_t ell, size_t draws_P, const size_t* at, cg1whisk_host::PlaceField* out) {
+  namespace W = cg1whisk_host;
+  size_t m = 0;
+  for (int id = 0; id < W::N_PLACE_FIELDS; ++id) {
+    const W::PlaceRule& r = W::PLACE_RULES[id];
+    if (r.block == block && (phase < 0 || r.phase == phase)) out[m++] = W::place_resolve(r, ell, draws_P, at[id]);
+  }
+  return m;
+}
+// ... and ONE k_whisk_witness_place launch for them on the context's stream: behind the uploads that cover the fields (which carry whatever
+// the host block held there) and in front of the first kernel that reads one
+int whisk_place_enqueue(cg1_ctx* ctx, uint8_t* D, const ShuffleWitness& w, int block, int phase, const size_t* at) {
+  namespace W = cg1whisk_host;
+  W::PlaceField f[W::N_PLACE_FIELDS];
+  cg1whisk::PlaceArgs a{};
+  a.draws = w.d_draws; a.block = D; a.ell = (uint32_t)w.ell; a.Q = (uint32_t)w.P;
+  a.n_fields = (uint32_t)place_fields(block, phase, w.ell, w.draws_P, at, f);
+  if (a.n_fields > cg1whisk::PLACE_MAX_FIELDS || w.P > CG1_SAME_MSM_MAX_PROVERS) { snprintf(ctx->err, sizeof ctx->err, "the witness placement does not fit one launch"); return CG1_ERR_ARG; }
+  for (size_t q = 0; q < w.P; ++q) a.keep[q] = (uint8_t)(w.keep ? w.keep[q] : q);
+  uint32_t most = 1;
+  for (uint32_t i = 0; i < a.n_fields; ++i) {
+    a.f[i] = f[i];
+    const uint32_t row = f[i].kind != W::PLACE_WORDS ? f[i].dst_w * 2u : (f[i].dst_w & 3u) ? f[i].dst_w : f[i].dst_w / 4u;      // lanes per row: the kernel's cut
+    most = std::max(most, a.Q * row);
+  }
+  hipLaunchKernelGGL(cg1whisk::k_whisk_witness_place, dim3((most + cg1whisk::PLACE_THREADS - 1) / cg1whisk::PLACE_THREADS, a.n_fields), dim3(cg1whisk::PLACE_THREADS), 0,
+                     ctx->stream, a);
+  HIPCHK(hipGetLastError());
+  return CG1_OK;
+}
+
+// The inputs of a whole shuffle into its block: the three arguments' (their *_stage functions) and the entry's own fields.  A resident
+// witness leaves every witness field of the host block unwritten.  -> the witness bytes written into host memory: the lengths of the
+// chain block's witness fields (place_bytes), which is what the copies below and in the *_stage functions write of it
+size_t shuffle_stage(uint8_t* H, const ShuffleLayout& SH, const SscalarLayout& SS, const GprodPlan& gp, const SmsmLayout& SM, size_t ell, size_t P, const uint32_t* gi_a,
+                     const uint32_t* gi_m, const uint32_t* u_index, const uint8_t* gth_affine96, const uint8_t* rs_affine96, const uint8_t* tu, const SamePermHead& sp,
+                     const ShuffleWitness& w) {
+  namespace W = cg1whisk_host;
+  const size_t n = ell + cg1shuffle::N_BLINDERS;
+  sscalar_stage(H, SS, ell, P, gth_affine96, rs_affine96, nullptr, w.col[W::COL_K], w.col[W::COL_BL]);
+  gprod_stage(H, gp, gi_a, u_index, &sp, nullptr, nullptr, nullptr, w.col[W::COL_CBL], w.col[W::COL_IPA_R], w.col[W::COL_Z_HEAD]);
+  smsm_stage(H, SM, n, P, gi_m, tu, nullptr, w.col[W::COL_VEC_R]);
+  memcpy(H + SH.gi_a, gi_a, P * n * 4);
+  if (w.resident()) return 0;
+  memcpy(H + SH.perm, w.perm, P * ell * 4); memcpy(H + SH.abl, w.col[W::COL_ABL], P * 64);
+  return W::place_bytes(W::BLOCK_CHAIN, ell, P);
+}
+// vec_a_blinders | 0 | 0 per prover, as the same-permutation head takes them (a host witness)
+std::vector<uint8_t> shuffle_abl4(const ShuffleWitness& w) {
+  constexpr size_t NB = cg1shuffle::N_BLINDERS;
+  std::vector<uint8_t> abl4(w.P * NB * 32, 0);
+  for (size_t p = 0; p < w.P; ++p) memcpy(&abl4[p * NB * 32], w.col[cg1whisk_host::COL_ABL] + p * 64, 64);
+  return abl4;
+}
+void shuffle_place_at(size_t* at, const ShuffleLayout& SH, const SscalarLayout& SS, const GprodLayout& GP, const SmsmLayout& SM) {
+  namespace W = cg1whisk_host;
+  at[W::PF_SH_PERM] = SH.perm; at[W::PF_SH_ABL] = SH.abl; at[W::PF_SS_K] = SS.k; at[W::PF_SS_BL] = SS.bl;
+  at[W::PF_GP_PERM] = GP.perm; at[W::PF_GP_ABL] = GP.abl; at[W::PF_GP_MBL] = GP.mbl; at[W::PF_GP_CBL] = GP.cbl; at[W::PF_GP_R] = GP.r; at[W::PF_GP_Z] = GP.z;
+  at[W::PF_SM_VR] = SM.vr;
+}
+
 // The body of cg1_shuffle_prove_device, under the calling entry's name: the whole-shuffle entry, the Whisk entries (capi_whisk_shuffle.h)
 // and the chain prover (capi_chain_prove.h) come here with pointers they have checked.  "prover p" in a refusal counts the P provers
 // that reached this function.
@@ -80,7 +168,7 @@ int shuffle_prove(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_
   static const char* const hashed_m[] = {"M"};
   constexpr size_t NB = cg1shuffle::N_BLINDERS;
   const uint32_t *g_index = crs.g, *h_index = crs.h, *u_index = crs.u, *gt_index = crs.gt, *gu_index = crs.gu, *perm = witness.perm;
-  const uint8_t *gth_affine96 = crs.gth_affine96, *k32 = witness.col[W::COL_K], *vec_m_blinders32 = witness.col[W::COL_MBL], *vec_a_blinders32 = witness.col[W::COL_ABL],
+  const uint8_t *gth_affine96 = crs.gth_affine96, *k32 = witness.col[W::COL_K], *vec_m_blinders32 = witness.col[W::COL_MBL],
                 *vec_c_blinders32 = witness.col[W::COL_CBL], *ipa_r32 = witness.col[W::COL_IPA_R], *ipa_z_head32 = witness.col[W::COL_Z_HEAD],
                 *blinders32 = witness.col[W::COL_BL], *vec_r32 = witness.col[W::COL_VEC_R];
   // ---- 1. refusals: the whole call, before anything is written -- the entry's own, then the three arguments' on what they will see
@@ -92,18 +180,25 @@ int shuffle_prove(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_
     return CG1_ERR_ARG; }
   // what the arguments take: vec_G | vec_H and vec_G | vec_H[:2] | G_t | G_u as index rows, vec_a_blinders | 0 | 0, and the same-MSM
   // argument's vec_T | Z1 Z1 H Z1 | vec_U | Z1 Z1 Z1 H (the all-zero record is the identity)
+  // A RESIDENT witness has no byte on the host: abl4 is not built, and every check below on a witness value is skipped (its list is
+  // null, which the checks read as absent).  That is sound because such a witness is the device's own draws and nothing a caller stated:
+  // every scalar left k_whisk_draws through fr_from_le64_wide, which reduces mod r, so it is canonical; k_whisk_fisher_yates swaps the
+  // identity row in place, so each row is a permutation of 0 .. ell - 1 by construction; and the zero events (vec_c_blinders[2] == 0,
+  // the second denominator) set the chains' device status bits as they do for a host witness -- ST_ZERO_C is checked here only to
+  // refuse early.  Every check on a public input -- shape, indices, points -- stays.
+  const bool resident = witness.resident();
   std::vector<uint32_t> gi_a(P * n), gi_m(P * n);
-  std::vector<uint8_t> abl4(P * NB * 32, 0), tu(P * 2 * n * 96, 0), canon_m(P * 48), tu48;
+  std::vector<uint8_t> abl4, tu(P * 2 * n * 96, 0), canon_m(P * 48), tu48;
+  if (!resident) { abl4 = shuffle_abl4(witness); ctx->whisk_traffic[1] += abl4.size(); }
   for (size_t p = 0; p < P; ++p) {
     memcpy(&gi_a[p * n], g_index + p * ell, ell * 4); memcpy(&gi_a[p * n + ell], h_index + p * NB, NB * 4);
     memcpy(&gi_m[p * n], g_index + p * ell, ell * 4); memcpy(&gi_m[p * n + ell], h_index + p * NB, 2 * 4);
     gi_m[p * n + ell + 2] = gt_index[p]; gi_m[p * n + ell + 3] = gu_index[p];
-    memcpy(&abl4[p * NB * 32], vec_a_blinders32 + p * 64, 64);
     uint8_t* T = &tu[p * 2 * n * 96];
     memcpy(T, tu_affine96 + p * 2 * ell * 96, ell * 96); memcpy(T + (ell + 2) * 96, gth_affine96 + 2 * 96, 96);
     memcpy(T + n * 96, tu_affine96 + (p * 2 * ell + ell) * 96, ell * 96); memcpy(T + (n + ell + 3) * 96, gth_affine96 + 2 * 96, 96);
   }
-  const SamePermHead sp{nullptr, nullptr, perm, abl4.data(), vec_m_blinders32};
+  const SamePermHead sp{nullptr, nullptr, perm, resident ? nullptr : abl4.data(), vec_m_blinders32};
   if (const int rc = gprod_check(ctx, who, same_perm_status_error, t, true, ell, NB, P, gi_a.data(), u_index, &sp, m48, 1, hashed_m, canon_m.data(), nullptr, nullptr,
                                  vec_c_blinders32, ipa_r32, ipa_z_head32)) return rc;
   if (const int rc = sscalar_check(ctx, who, t, true, ell, P, gth_affine96, rs_affine96, nullptr, k32, blinders32)) return rc;
@@ -118,14 +213,13 @@ int shuffle_prove(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_
 
   // ---- the block: states | the entry's fields | same-scalar | same-permutation | same-MSM, and everything a launch could otherwise
   // allocate in mid-chain
-  ChainLayout C{};
-  const size_t states = C.take(P * 208);
-  const ShuffleLayout SH = shuffle_layout(ell, P, C.total);
-  const SscalarLayout SS = sscalar_layout(ell, P, SH.total, states);
-  GprodPlan gp = gprod_plan(ell, NB, P, true, SS.total, states);
+  ShuffleBlock blk = shuffle_block(ell, P);
+  const size_t states = blk.states, pb_msm = blk.pb_msm;
+  const ShuffleLayout& SH = blk.SH;
+  const SscalarLayout& SS = blk.SS;
+  GprodPlan& gp = blk.gp;
   const GprodLayout& GP = gp.L;
-  const size_t pb_msm = cg1_same_msm_proof_bytes(n);
-  const SmsmLayout SM = smsm_layout(n, P, pb_msm, GP.total, states);
+  const SmsmLayout& SM = blk.SM;
   uint8_t* H; uint8_t* D;
   if (const int rc = chain_reserve(ctx, t, SM.total, H, D)) return rc;
   const size_t bases_rs = cg1sscalar::SHARED_BASES + P * 2 * ell, bases_tu = P * 2 * n;
@@ -147,10 +241,9 @@ int shuffle_prove(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_
 
   // ---- 2. the head on the host, per prover: curdleproofs_step1 [vec_R + vec_S + vec_T + vec_U], M, curdleproofs_vec_a x ell
   chain_clear(H, SS, P); chain_clear(H, GP, P); chain_clear(H, SM, P);
-  sscalar_stage(H, SS, ell, P, gth_affine96, rs_affine96, nullptr, k32, blinders32);
-  gprod_stage(H, gp, gi_a.data(), u_index, &sp, nullptr, nullptr, nullptr, vec_c_blinders32, ipa_r32, ipa_z_head32);
-  smsm_stage(H, SM, n, P, gi_m.data(), tu.data(), nullptr, vec_r32);
-  memcpy(H + SH.perm, perm, P * ell * 4); memcpy(H + SH.abl, vec_a_blinders32, P * 64); memcpy(H + SH.gi_a, gi_a.data(), P * n * 4);
+  ctx->whisk_traffic[1] += shuffle_stage(H, SH, SS, gp, SM, ell, P, gi_a.data(), gi_m.data(), u_index, gth_affine96, rs_affine96, tu.data(), sp, witness);
+  size_t place_at[W::N_PLACE_FIELDS] = {0};
+  shuffle_place_at(place_at, SH, SS, GP, SM);
   for (uint32_t p = 0; p < Pn; ++p) cg1shuffle::head_offsets(nn, p * cg1shuffle::head_terms(nn), reinterpret_cast<uint32_t*>(H + SH.offs) + cg1shuffle::HEAD_MSMS * p);
   cg1::pool_for(P, 0, [&](size_t p) {
     static const uint8_t label[] = "curdleproofs", step1[] = "curdleproofs_step1", l_a[] = "curdleproofs_vec_a";
@@ -167,6 +260,7 @@ int shuffle_prove(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_
   if (const int rc = chain_upload(ctx, t, SH)) return rc;
   if (const int rc = chain_upload(ctx, t, SS)) return rc;
   if (const int rc = chain_upload(ctx, t, SM)) return rc;     // (its vx field goes up as it lies: k_shuffle_begin writes it next)
+  if (resident) { if (const int rc = whisk_place_enqueue(ctx, D, witness, W::BLOCK_CHAIN, 0, place_at)) return shuffle_refuse(ctx, rc); }
 
   // ---- 3, 4. k_shuffle_begin, then A | A' as one launch over the CRS table; their encodings come down behind the first event
   lt->n_bases = bases_rs;
@@ -200,6 +294,7 @@ int shuffle_prove(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_
   });
   HIPCHK(hipMemcpyAsync(D + states, H + states, P * 208, hipMemcpyHostToDevice, ctx->stream));
   if (const int rc = chain_upload(ctx, t, GP)) return shuffle_refuse(ctx, rc);
+  if (resident) { if (const int rc = whisk_place_enqueue(ctx, D, witness, W::BLOCK_CHAIN, 1, place_at)) return shuffle_refuse(ctx, rc); }
   const cg1sperm::SamePermArgs spa = gprod_args(ctx, t, D, gp, true);
   if (const int rc = gprod_enqueue(ctx, t, D, gp, spa, true)) return shuffle_refuse(ctx, rc);
 

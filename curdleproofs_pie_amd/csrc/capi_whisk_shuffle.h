@@ -49,7 +49,7 @@ void whisk_m_rows(uint8_t* H, const WhiskMFields& F, size_t ell, size_t P, const
   uint32_t* offs = reinterpret_cast<uint32_t*>(H + F.offs);
   for (size_t p = 0; p < P; ++p) {
     memcpy(tb + p * n, g_index + p * ell, ell * 4); memcpy(tb + p * n + ell, h_index + p * NB, NB * 4);
-    cg1whisk_host::m_scalar_row(ell, perm + p * ell, vec_m_blinders32 + 32 * NB * p, H + F.sc + 32 * n * p);
+    if (perm) cg1whisk_host::m_scalar_row(ell, perm + p * ell, vec_m_blinders32 + 32 * NB * p, H + F.sc + 32 * n * p);      // (null: a resident witness, placed on the device)
     offs[p] = (uint32_t)(p * n);
   }
   offs[P] = (uint32_t)(P * n);
@@ -62,12 +62,27 @@ int whisk_m_enqueue(cg1_ctx* ctx, cg1_fixed* t, uint8_t* D, const WhiskMFields& 
   return CG1_OK;
 }
 
+// the witness fields of the front's block as the host stages them, and the public rows of M beside them -> the witness bytes written
+// (a resident witness: none, its fields stay as they lie)
+size_t whisk_front_stage(uint8_t* H, const WhiskLayout& L, const WhiskMFields& MF, size_t ell, size_t P, const uint32_t* g_index, const uint32_t* h_index,
+                         const ShuffleWitness& w) {
+  whisk_m_rows(H, MF, ell, P, g_index, h_index, w.perm, w.col[cg1whisk_host::COL_MBL]);
+  if (w.resident()) return 0;
+  memcpy(H + L.perm, w.perm, P * ell * 4); memcpy(H + L.k, w.col[cg1whisk_host::COL_K], P * 32);
+  return cg1whisk_host::place_bytes(cg1whisk_host::BLOCK_FRONT, ell, P);
+}
+void whisk_front_place_at(size_t* at, const WhiskLayout& L) {
+  at[cg1whisk_host::PF_L_PERM] = L.perm; at[cg1whisk_host::PF_L_K] = L.k; at[cg1whisk_host::PF_MF_SC] = L.sc;
+}
+
 // The front on the context's stream.  The outputs are host buffers of the caller's or of the whole call's; nothing is written into them
 // before every refusal has been ruled out.  out_status / out_bad_at (both or neither): a tracker point that does not decode or lies
 // outside G1 then refuses ITS prover only -- code and tracker 2 + half of its first such point; its four outputs are zeros -- and the call
-// goes on for the others.
+// goes on for the others.  The witness: its permutations, COL_K and COL_MBL (a host view needs no other column).  A resident one is
+// placed into the block on the device, behind the upload and in front of the first kernel; check_inputs is skipped for it, which is sound
+// for the reasons shuffle_prove gives (capi_shuffle.h): the device's own draws are reduced mod r and are permutations by construction.
 int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t P, const uint32_t* g_index, const uint32_t* h_index, const uint8_t* trackers96,
-                const uint32_t* perm, const uint8_t* k32, const uint8_t* vec_m_blinders32, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96, uint8_t* out_post96,
+                const ShuffleWitness& witness, uint8_t* out_rs_affine96, uint8_t* out_tu_affine96, uint8_t* out_post96,
                 uint8_t* out_m48, int32_t* out_status = nullptr, uint32_t* out_bad_at = nullptr) {
   constexpr size_t NB = cg1whisk_host::N_BLINDERS;
   if (const int rc = cg1whisk_host::check_shape(ctx->err, sizeof ctx->err, who, ell)) return rc;
@@ -76,7 +91,9 @@ int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t 
     snprintf(ctx->err, sizeof ctx->err, "%s: more than %d provers, or more than %d bases T | U, in one call", who, CG1_SAME_MSM_MAX_PROVERS, CG1_LIGHT_MAX_BASES);
     return CG1_ERR_ARG; }
   if (const int rc = chain_check_indices(ctx, who, t, {{g_index, P * ell}, {h_index, P * NB}})) return rc;
-  if (const int rc = cg1whisk_host::check_inputs(ctx->err, sizeof ctx->err, who, ell, P, perm, k32, vec_m_blinders32)) return rc;
+  if (!witness.resident()) {
+    if (const int rc = cg1whisk_host::check_inputs(ctx->err, sizeof ctx->err, who, ell, P, witness.perm, witness.col[cg1whisk_host::COL_K], witness.col[cg1whisk_host::COL_MBL])) return rc;
+  }
 
   // ---- the block
   const WhiskLayout L = whisk_layout(ell, P);
@@ -94,10 +111,14 @@ int whisk_front(cg1_ctx* ctx, const char* who, cg1_fixed* t, size_t ell, size_t 
       memcpy(enc + 48 * (ell + i), trackers96 + 96 * (p * ell + i) + 48, 48);
     }
   }
-  whisk_m_rows(H, MF, ell, P, g_index, h_index, perm, vec_m_blinders32);
-  memcpy(H + L.perm, perm, P * ell * 4); memcpy(H + L.k, k32, P * 32);
+  ctx->whisk_traffic[1] += whisk_front_stage(H, L, MF, ell, P, g_index, h_index, witness);
   memset(H + L.wst, 0, 16);
   if (const int rc = chain_upload(ctx, t, L)) return rc;
+  if (witness.resident()) {
+    size_t at[cg1whisk_host::N_PLACE_FIELDS] = {0};
+    whisk_front_place_at(at, L);
+    if (const int rc = whisk_place_enqueue(ctx, D, witness, cg1whisk_host::BLOCK_FRONT, 0, at)) return shuffle_refuse(ctx, rc);
+  }
 
   // ---- M for every prover as one launch over the CRS table; it depends on no tracker and runs ahead of the scalar multiplications
   if (const int rc = whisk_m_enqueue(ctx, t, D, MF, ell, P, shape)) return rc;
@@ -189,14 +210,14 @@ void whisk_place_outputs(size_t ell, size_t P, const size_t* keep, size_t Q, con
 
 // ---- the seeded draws
 using cg1whisk_host::DrawBlock;
-// k_whisk_draws and k_whisk_fisher_yates on the context's stream, ONE copy down (perm | scalars -> stage), the device buffer zeroed, one
-// wait.  The arguments have been checked (cg1whisk_host::check_draws).
-int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, uint64_t first_index, cg1::WipedBytes& stage) {
+// k_whisk_draws and k_whisk_fisher_yates on the context's stream, into ctx->d_whisk_draws (grown here), and nothing else: no copy, no
+// zeroing, no wait.  The arguments have been checked (cg1whisk_host::check_draws).  This is the whole of the RESIDENT form of the draws:
+// they stay in the buffer for k_whisk_witness_place to read, in stream order, and whoever calls this for them holds a WhiskDrawsWipe.
+int whisk_draws_enqueue(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, uint64_t first_index) {
   const DrawBlock B = cg1whisk_host::draw_block(ell, P);
   HIPCHK(hipSetDevice(ctx->device));
   if (const int rc = cg1::grow_bufs(ctx, ctx->cap_whisk_draws, B.total, B.total, {cg1::dev_buf(ctx->d_whisk_draws, B.total)})) return rc;
   uint8_t* D = (uint8_t*)ctx->d_whisk_draws;
-  stage.v.resize(B.total - B.perm);
   cg1whisk::DrawArgs a;
   memcpy(a.seed.w, seed32, 32);
   a.ell = (uint32_t)ell; a.n_provers = (uint32_t)P; a.first_index = (uint32_t)first_index;      // (first_index = 2^32 only with P = 0)
@@ -205,6 +226,15 @@ int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, u
   hipLaunchKernelGGL(cg1whisk::k_whisk_draws, dim3((lanes + cg1merlin::LANES - 1) / cg1merlin::LANES), dim3(cg1merlin::LANES), 0, ctx->stream, a);
   hipLaunchKernelGGL(cg1whisk::k_whisk_fisher_yates, dim3((uint32_t)P), dim3(64), 0, ctx->stream, (const uint32_t*)(D + B.swaps), (uint32_t)ell, (uint32_t*)(D + B.perm));
   cg1::wipe(&a, sizeof a);
+  return CG1_OK;
+}
+// The copying form: those kernels, ONE copy down (perm | scalars -> stage), the device buffer zeroed, one wait.
+int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, uint64_t first_index, cg1::WipedBytes& stage) {
+  const DrawBlock B = cg1whisk_host::draw_block(ell, P);
+  if (const int rc = whisk_draws_enqueue(ctx, ell, P, seed32, first_index)) return rc;
+  uint8_t* D = (uint8_t*)ctx->d_whisk_draws;
+  stage.v.resize(B.total - B.perm);
+  ctx->whisk_traffic[0] += B.total - B.perm; ctx->whisk_traffic[1] += B.total - B.perm;
   hipError_t e = hipMemcpyAsync(stage.v.data(), D + B.perm, B.total - B.perm, hipMemcpyDeviceToHost, ctx->stream);
   const hipError_t e2 = hipMemsetAsync(D, 0, B.total, ctx->stream);        // the draws do not outlive the call on the device, whatever the copy said
   const hipError_t e3 = hipStreamSynchronize(ctx->stream);
@@ -213,6 +243,19 @@ int whisk_draws_run(cg1_ctx* ctx, size_t ell, size_t P, const uint8_t* seed32, u
   HIPCHK(hipGetLastError());
   return CG1_OK;
 }
+// The scope guard of a resident seeded call: the context's draws buffer, all of it, zeroed behind whatever the stream still holds, and
+// waited for -- on success, on every refusal of whisk_front / shuffle_prove, on a HIP error and on a growth that failed (which leaves
+// no buffer: nothing to zero).
+struct WhiskDrawsWipe {
+  cg1_ctx* ctx;
+  explicit WhiskDrawsWipe(cg1_ctx* c) : ctx(c) {}          // (null: the copying path, whose whisk_draws_run has zeroed the buffer itself)
+  WhiskDrawsWipe(const WhiskDrawsWipe&) = delete;
+  ~WhiskDrawsWipe() {
+    if (!ctx || !ctx->d_whisk_draws || !ctx->cap_whisk_draws) return;
+    (void)hipMemsetAsync(ctx->d_whisk_draws, 0, ctx->cap_whisk_draws, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+};
 // the table's staging block holds k, the permutations and, after the chain, every blinder: both copies are zeroed before any return of a
 // seeded entry (which set t->chain_used = 0 when it began)
 hipError_t whisk_wipe_block(cg1_ctx* ctx, cg1_fixed* t) {
@@ -238,7 +281,9 @@ int cg1_whisk_shuffle_front(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_pro
   if (n_provers == 0) return CG1_OK;
   const bool pointers_ok = g_index && h_index && trackers96 && perm && k32 && vec_m_blinders32 && out_rs_affine96 && out_tu_affine96 && out_post96 && out_m48;
   if (!t || t->device != ctx->device || !pointers_ok) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
-  return whisk_front(ctx, who, t, ell, n_provers, g_index, h_index, trackers96, perm, k32, vec_m_blinders32, out_rs_affine96, out_tu_affine96, out_post96, out_m48);
+  ShuffleWitness w{ell, n_provers, perm, {}};
+  w.col[cg1whisk_host::COL_K] = k32; w.col[cg1whisk_host::COL_MBL] = vec_m_blinders32;
+  return whisk_front(ctx, who, t, ell, n_provers, g_index, h_index, trackers96, w, out_rs_affine96, out_tu_affine96, out_post96, out_m48);
 }
 
 int cg1_whisk_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
@@ -257,7 +302,7 @@ int cg1_whisk_shuffle_prove_device(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   // the front refuses gets no scratch: the front refuses them before it writes.)
   const size_t P = n_provers, pts = cg1whisk_host::shape_ok(ell) && P <= CG1_SAME_MSM_MAX_PROVERS ? P * 2 * ell : 0;
   std::vector<uint8_t> rs(pts * 96), tu(pts * 96), post(pts * 48), m48(pts ? P * 48 : 0), proofs;
-  if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, perm, k32, vec_m_blinders32, rs.data(), tu.data(), post.data(), m48.data())) return rc;
+  if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, w, rs.data(), tu.data(), post.data(), m48.data())) return rc;
   proofs.resize(P * cg1_shuffle_prover_proof_bytes(ell));
   if (const int rc = shuffle_prove(ctx, who, t, ell, P, ShuffleCrsRows(g_index, h_index, u_index, gt_index, gu_index, gth_affine96), rs.data(), tu.data(), m48.data(), w, 1,
                                    proofs.data(), nullptr)) return rc;
@@ -285,6 +330,7 @@ int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   static const char* const who = "cg1_whisk_shuffle_prove_seeded";
   constexpr size_t NB = cg1whisk_host::N_BLINDERS;
   if (!ctx) return CG1_ERR_HIP;
+  ctx->whisk_traffic[0] = ctx->whisk_traffic[1] = 0;
   if (n_provers == 0) return CG1_OK;
   const bool pointers_ok = g_index && h_index && u_index && gt_index && gu_index && gth_affine96 && trackers96 && seed32 && out_post96 && out_proofs && out_status && out_bad_at;
   if (!t || t->device != ctx->device || !pointers_ok) { snprintf(ctx->err, sizeof ctx->err, "%s: bad argument", who); return CG1_ERR_ARG; }
@@ -296,17 +342,20 @@ int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   if (const int rc = cg1whisk_host::check_draws(ctx->err, sizeof ctx->err, who, ell, P, first_index)) return rc;
   if (const int rc = chain_check_indices(ctx, who, t, {{g_index, P * ell}, {h_index, P * NB}, {u_index, P}, {gt_index, P}, {gu_index, P}})) return rc;
   t->chain_used = 0;
-  // ---- 1. the draws: on the device, one copy down
+  // ---- 1. the draws: on the device, and one copy down -- or, with "whisk_resident_witness", no copy: they stay where the kernels wrote
+  // them until the guard zeroes them, and the front and the chain place them into their blocks on the device
+  const bool resident = ctx->whisk_resident != 0;
   cg1::WipedBytes stage, kept;
-  if (const int rc = whisk_draws_run(ctx, ell, P, seed32, first_index, stage)) return rc;
-  const ShuffleWitness drawn = ShuffleWitness::of_draws(stage.v.data(), ell, P);
+  WhiskDrawsWipe wipe_draws(resident ? ctx : nullptr);
+  if (const int rc = resident ? whisk_draws_enqueue(ctx, ell, P, seed32, first_index) : whisk_draws_run(ctx, ell, P, seed32, first_index, stage)) return rc;
+  const ShuffleWitness drawn = resident ? ShuffleWitness::resident_draws((const uint8_t*)ctx->d_whisk_draws, ell, P) : ShuffleWitness::of_draws(stage.v.data(), ell, P);
   // ---- 2. the front, a status per prover
   const size_t pts = P * 2 * ell;
   std::vector<uint8_t> rs(pts * 96), tu(pts * 96), post(pts * 48), m48(P * 48), proofs, rs_kept, tu_kept, m_kept;
   std::vector<int32_t> st(P);
   std::vector<uint32_t> at(P);
-  if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, drawn.perm, drawn.col[cg1whisk_host::COL_K], drawn.col[cg1whisk_host::COL_MBL], rs.data(),
-                                 tu.data(), post.data(), m48.data(), st.data(), at.data())) { (void)whisk_wipe_block(ctx, t); return rc; }
+  if (const int rc = whisk_front(ctx, who, t, ell, P, g_index, h_index, trackers96, drawn, rs.data(), tu.data(), post.data(), m48.data(), st.data(), at.data())) {
+    (void)whisk_wipe_block(ctx, t); return rc; }
   // ---- 3. the provers it did not refuse, through the chain (its "prover" counts them, not the call's)
   std::vector<size_t> keep;
   for (size_t p = 0; p < P; ++p) if (!st[p]) keep.push_back(p);
@@ -315,18 +364,94 @@ int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* t, size_t ell, size_
   const uint8_t* m_q = m48.data();                           // M of the kept provers, one after the other
   if (Q) {
     const ShuffleWitness w = drawn.gather(keep.data(), Q, kept);
+    ctx->whisk_traffic[1] += kept.v.size();
     const ShuffleCrsRows crs(ShuffleCrsRows(g_index, h_index, u_index, gt_index, gu_index, gth_affine96), ell, P, keep.data(), Q);
     m_q = shuffle_rows(m48.data(), 48, P, keep.data(), Q, m_kept);
     proofs.resize(Q * cg1_shuffle_prover_proof_bytes(ell));
     rc = shuffle_prove(ctx, who, t, ell, Q, crs, shuffle_rows(rs.data(), 2 * ell * 96, P, keep.data(), Q, rs_kept), shuffle_rows(tu.data(), 2 * ell * 96, P, keep.data(), Q, tu_kept),
                        m_q, w, 1, proofs.data(), nullptr);
   }
-  // ---- 4. secret hygiene (the draws' own device buffer and host staging: whisk_draws_run, WipedBytes), then the caller's buffers
+  // ---- 4. secret hygiene (the draws' own device buffer and host staging: whisk_draws_run and WipedBytes, or WhiskDrawsWipe), then the caller's buffers
   const hipError_t wiped = whisk_wipe_block(ctx, t);
   if (rc) return rc;
   HIPCHK(wiped);
   whisk_place_outputs(ell, P, keep.data(), Q, post.data(), m_q, proofs.data(), out_post96, out_proofs);
   memcpy(out_status, st.data(), P * 4); memcpy(out_bad_at, at.data(), P * 4);
   return CG1_OK;
+}
+
+// What the last cg1_whisk_shuffle_prove_seeded call on this context moved of its witness: out[0] bytes copied device -> host, out[1] bytes
+// the library wrote into host memory (the staging of the draws, the gathered rows, the block's witness fields, abl4).  Plain host counters
+// beside those sites, zeroed when a seeded call begins; both are 0 after a call under "whisk_resident_witness" = 1.  The sites lie in
+// whisk_front and shuffle_prove, which other entries share: read the counters straight after the seeded call, before any other.  For the tests.
+void cg1_whisk_last_witness_traffic(const cg1_ctx* ctx, uint64_t out[2]) {
+  out[0] = ctx ? ctx->whisk_traffic[0] : 0; out[1] = ctx ? ctx->whisk_traffic[1] : 0;
+}
+// 1 when every byte of the context's draws buffer is zero (or there is none), 0 when one is not, -1 on a HIP error.  One D2H copy.  For the tests.
+int cg1_whisk_draws_buffer_is_zero(cg1_ctx* ctx) {
+  if (!ctx) return -1;
+  if (!ctx->d_whisk_draws || !ctx->cap_whisk_draws) return 1;
+  std::vector<uint8_t> h(ctx->cap_whisk_draws);
+  if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+      hipMemcpy(h.data(), ctx->d_whisk_draws, h.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  for (const uint8_t b : h) if (b) return 0;
+  return 1;
+}
+
+// Host only, no HIP call: the front's (which_block = 0) or the chain's (1) staging block laid out exactly as the seeded entry lays it out
+// for P drawn shuffles (the front) or for the Q of them keep[0] < .. < keep[Q - 1] names (the chain; keep == NULL: all P), with ONLY its
+// witness fields filled, from draws_block (DrawBlock: swaps | perm | scalars, draw_block(ell, P).total bytes) -- resident = 0: by the
+// copying path's own code, ShuffleWitness::gather and the stage functions over zero public inputs, of which only the witness fields are
+// kept; resident = 1: by the placement map (place_source), as k_whisk_witness_place does.  -> the block's length, 0 for a shape or a
+// keep list the entry would not reach; `out` (cap bytes) is written only when it holds the block, out_fields (2 words per field: offset,
+// length) only up to *n_fields fields, and *n_fields becomes the number of witness fields.
+size_t cg1_whisk_witness_block_emulate(size_t ell, size_t P, const size_t* keep, size_t Q, const uint8_t* draws_block, int resident, int which_block, uint8_t* out, size_t cap,
+                                       uint64_t* out_fields, size_t* n_fields) {
+  namespace W = cg1whisk_host;
+  constexpr size_t NB = W::N_BLINDERS;
+  const size_t n = ell + NB;
+  if (!W::shape_ok(ell) || P < 1 || P > CG1_SAME_MSM_MAX_PROVERS || P * 2 * n > CG1_LIGHT_MAX_BASES || !draws_block || !n_fields || (which_block != 0 && which_block != 1)) return 0;
+  std::vector<size_t> all(P);
+  for (size_t p = 0; p < P; ++p) all[p] = p;
+  if (which_block == 0 || !keep) { keep = all.data(); Q = P; }
+  if (Q < 1 || Q > P) return 0;
+  for (size_t q = 0; q < Q; ++q) if (keep[q] >= P || (q && keep[q] <= keep[q - 1])) return 0;
+  // ---- the layouts, as whisk_front and shuffle_prove make them
+  const WhiskLayout L = whisk_layout(ell, P);
+  const ShuffleBlock blk = shuffle_block(ell, Q);
+  const ShuffleLayout& SH = blk.SH;
+  const SscalarLayout& SS = blk.SS;
+  const GprodPlan& gp = blk.gp;
+  const SmsmLayout& SM = blk.SM;
+  const size_t total = which_block == 0 ? L.total : blk.total;
+  size_t at[W::N_PLACE_FIELDS] = {0};
+  whisk_front_place_at(at, L);
+  shuffle_place_at(at, SH, SS, gp.L, SM);
+  W::PlaceField f[W::N_PLACE_FIELDS];
+  const size_t m = place_fields(which_block, -1, ell, P, at, f);
+  for (size_t i = 0; out_fields && i < m && i < *n_fields; ++i) { out_fields[2 * i] = f[i].dst; out_fields[2 * i + 1] = (uint64_t)Q * f[i].dst_w * W::place_elem_bytes(f[i]); }
+  *n_fields = m;
+  if (!out || cap < total) return total;
+  memset(out, 0, total);
+  if (resident) {
+    for (size_t i = 0; i < m; ++i) W::place_field_host(out, f[i], draws_block, ell, keep, Q);
+    return total;
+  }
+  // ---- the copying path: the staging as it comes down, the gather, the stage functions into a block of its own
+  const W::DrawBlock B = W::draw_block(ell, P);
+  cg1::WipedBytes kept, block;
+  block.v.assign(total, 0);
+  const ShuffleWitness drawn = ShuffleWitness::of_draws(draws_block + B.perm, ell, P);
+  const std::vector<uint32_t> zi(Q * n + 1, 0);
+  if (which_block == 0) {
+    (void)whisk_front_stage(block.v.data(), L, WhiskMFields{L.tb, L.sc, L.offs, L.m48, L.st_msm}, ell, P, zi.data(), zi.data(), drawn);
+  } else {
+    const ShuffleWitness w = drawn.gather(keep, Q, kept);
+    const std::vector<uint8_t> zp(Q * 2 * n * 96 + cg1sscalar::SHARED_BASES * 96, 0), abl4 = shuffle_abl4(w);
+    const SamePermHead sp{nullptr, nullptr, w.perm, abl4.data(), w.col[W::COL_MBL]};
+    (void)shuffle_stage(block.v.data(), SH, SS, gp, SM, ell, Q, zi.data(), zi.data(), zi.data(), zp.data(), zp.data(), zp.data(), sp, w);
+  }
+  for (size_t i = 0; i < m; ++i) memcpy(out + f[i].dst, block.v.data() + f[i].dst, (size_t)Q * f[i].dst_w * W::place_elem_bytes(f[i]));
+  return total;
 }
 }  // extern "C"

@@ -130,6 +130,8 @@ struct Ctx {
   void* d_prover = nullptr; size_t cap_prover = 0;                // cg1_opening_prove_device's scratch (1 252 B per proof)
   void* d_register = nullptr; size_t cap_register = 0;            // cg1_whisk_register_device's scratch (capi_register.h): a slice's columns and k_register_points' parking; the secret columns zeroed before every return
   void* d_whisk_draws = nullptr; size_t cap_whisk_draws = 0;      // the seeded draws of Whisk shuffles (capi_whisk_shuffle.h): swaps | perm | scalars; zeroed before every return
+  int whisk_resident = 0;               // "whisk_resident_witness": cg1_whisk_shuffle_prove_seeded keeps its draws on the device (k_whisk_witness_place) instead of staging them through the host
+  uint64_t whisk_traffic[2] = {0, 0};   // since the last seeded call began: witness bytes copied device -> host | written into host memory by the library (plain host counters beside those sites; cg1_whisk_last_witness_traffic)
   void* d_chain_prove = nullptr; size_t cap_chain_prove = 0;      // the tracker stage of a proved chain (capi_chain_prove.h): certification, origins, composites (zeroed before every return), records
   PreparedPoint* d_gen_tab = nullptr;   // k_generator_mul's table of G (GEN_ENTRIES records), built at the first use (cg1_generator_mul_device)
   int fixed_slice = 0;                  // "fixed_slice": terms per workgroup of k_table_msm (1 .. 128; 0 = by the size of the call).  A/B switch

@@ -198,4 +198,43 @@ __global__ void __launch_bounds__(64) k_whisk_fisher_yates(const uint32_t* __res
   for (uint32_t i = threadIdx.x; i < ell; i += 64u) perm[(size_t)p * ell + i] = pm[i];
 }
 
+// ---- the witness kept on the device (the seeded entry with "whisk_resident_witness"): the draws' block -> the witness fields of a staging
+// block, by the placement map of whisk_shuffle_host.h (PLACE_RULES resolved by the host into PlaceField, place_source called here).
+// A copy and nothing else: blockIdx.y is the field, so the field's record is read once per wave from the kernel arguments and every
+// branch on it is uniform; a lane moves 16 bytes.  The draws' columns and permutations begin on 64-byte boundaries, ChainLayout::take
+// aligns the fields to 64, and ell is a multiple of 4 (ell + 4 a power of two >= 8), so every 16-byte piece is aligned on both sides; a
+// row of words that is no multiple of 16 bytes would go a word per lane.  No LDS, no atomics; the stores are plain vector stores.
+constexpr uint32_t PLACE_MAX_FIELDS = 8, PLACE_THREADS = 256;
+struct PlaceArgs {
+  const uint8_t* draws;                      // ctx->d_whisk_draws: DrawBlock
+  uint8_t* block;                            // the table's staging block on the device
+  uint32_t ell, Q, n_fields, pad;            // Q destination provers
+  uint8_t keep[CG1_SAME_MSM_MAX_PROVERS];    // destination prover q reads prover keep[q] of the draws
+  cg1whisk_host::PlaceField f[PLACE_MAX_FIELDS];
+};
+static_assert(CG1_SAME_MSM_MAX_PROVERS <= 256, "a prover's index fits a byte of PlaceArgs::keep");
+__global__ void __launch_bounds__(PLACE_THREADS) k_whisk_witness_place(PlaceArgs a) {
+  namespace W = cg1whisk_host;
+  if (blockIdx.y >= a.n_fields) return;                    // (uniform)
+  const W::PlaceField f = a.f[blockIdx.y];
+  const uint32_t ell = a.ell, t = blockIdx.x * PLACE_THREADS + threadIdx.x;
+  const bool words = f.kind == W::PLACE_WORDS;
+  if (words && (f.dst_w & 3u) != 0u) {                     // (uniform) rows of words that are not 16-byte aligned: a word per lane
+    if (t >= a.Q * f.dst_w) return;
+    const uint32_t q = t / f.dst_w, e = t - q * f.dst_w;
+    const W::PlaceSrc s = W::place_source(f, ell, a.keep[q], e);
+    *reinterpret_cast<uint32_t*>(a.block + f.dst + 4ull * t) = *reinterpret_cast<const uint32_t*>(a.draws + s.at);
+    return;
+  }
+  const uint32_t row16 = words ? f.dst_w / 4u : f.dst_w * 2u;              // 16-byte pieces of a destination row
+  if (t >= a.Q * row16) return;
+  const uint32_t q = t / row16, j = t - q * row16;
+  const W::PlaceSrc s = W::place_source(f, ell, a.keep[q], words ? 4u * j : j >> 1);
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (words) v = *reinterpret_cast<const uint4*>(a.draws + s.at);          // four entries of the row: they lie side by side in the source
+  else if (s.bytes == 32u) v = *reinterpret_cast<const uint4*>(a.draws + s.at + 16u * (j & 1u));
+  else if (s.bytes == 4u && (j & 1u) == 0u) v.x = *reinterpret_cast<const uint32_t*>(a.draws + s.at);       // a widened permutation entry
+  *reinterpret_cast<uint4*>(a.block + f.dst + 16ull * t) = v;
+}
+
 }  // namespace cg1whisk

@@ -148,12 +148,105 @@ inline DrawBlock draw_block(size_t ell, size_t P) {
   return B;
 }
 
+// ---- THE PLACEMENT MAP: which bytes of the draws' block land in which witness field of the two staging blocks a seeded call lays out --
+// the front's (whisk_front: WhiskLayout) and the chain's (shuffle_prove: ShuffleLayout | SscalarLayout | GprodLayout | SmsmLayout).  The
+// device kernel k_whisk_witness_place and the host emulation cg1_whisk_witness_block_emulate both read PLACE_RULES and call place_source;
+// neither restates what goes where.  (The host staging of the copying path -- m_scalar_row, the *_stage functions -- is the OTHER
+// statement of it, and tests/test_whisk_witness_place.py holds the two against each other byte for byte.)
+enum PlaceKind : uint32_t {
+  PLACE_WORDS,                               // 4-byte elements: a row of a permutation
+  PLACE_SCALARS,                             // 32-byte elements: the first scalars of a column's row, zero scalars behind them
+  PLACE_M_ROW                                // 32-byte elements: m_scalar_row -- perm[i] widened, ell times, then the four vec_m_blinders
+};
+enum PlaceBlock : uint8_t { BLOCK_FRONT, BLOCK_CHAIN };
+// a field's phase: the launch that places it.  The chain's GprodLayout goes up at step 6 of shuffle_prove, behind the first host wait, so
+// its fields are placed there (phase 1); everything else behind the uploads in front of the first kernel (phase 0)
+enum PlaceFieldId { PF_L_PERM, PF_L_K, PF_MF_SC, PF_SH_PERM, PF_SH_ABL, PF_SS_K, PF_SS_BL, PF_GP_PERM, PF_GP_ABL, PF_GP_MBL, PF_GP_CBL, PF_GP_R, PF_GP_Z, PF_SM_VR,
+                    N_PLACE_FIELDS };
+struct PlaceRule { uint8_t block, phase; PlaceKind kind; int column; int dst_n, dst_c; };      // a prover's destination row: dst_n * n + dst_c elements (n = ell + 4)
+constexpr PlaceRule PLACE_RULES[N_PLACE_FIELDS] = {
+    {BLOCK_FRONT, 0, PLACE_WORDS, -1, 1, -4},              // L.perm
+    {BLOCK_FRONT, 0, PLACE_SCALARS, COL_K, 0, 1},          // L.k
+    {BLOCK_FRONT, 0, PLACE_M_ROW, COL_MBL, 1, 0},          // MF.sc
+    {BLOCK_CHAIN, 0, PLACE_WORDS, -1, 1, -4},              // SH.perm
+    {BLOCK_CHAIN, 0, PLACE_SCALARS, COL_ABL, 0, 2},        // SH.abl
+    {BLOCK_CHAIN, 0, PLACE_SCALARS, COL_K, 0, 1},          // SS.k
+    {BLOCK_CHAIN, 0, PLACE_SCALARS, COL_BL, 0, 5},         // SS.bl
+    {BLOCK_CHAIN, 1, PLACE_WORDS, -1, 1, -4},              // GP.perm
+    {BLOCK_CHAIN, 1, PLACE_SCALARS, COL_ABL, 0, 4},        // GP.abl: the two blinders, then two zero scalars
+    {BLOCK_CHAIN, 1, PLACE_SCALARS, COL_MBL, 0, 4},        // GP.mbl
+    {BLOCK_CHAIN, 1, PLACE_SCALARS, COL_CBL, 0, 4},        // GP.cbl
+    {BLOCK_CHAIN, 1, PLACE_SCALARS, COL_IPA_R, 1, 0},      // GP.r
+    {BLOCK_CHAIN, 1, PLACE_SCALARS, COL_Z_HEAD, 1, 0},     // GP.z: n - 2 scalars, then 64 zero bytes (the step kernel completes them)
+    {BLOCK_CHAIN, 0, PLACE_SCALARS, COL_VEC_R, 1, 0},      // SM.vr
+};
+// a rule resolved for one call: byte offsets into the block and into the draws' block, row widths in elements
+struct PlaceField {
+  uint64_t dst;                              // of the field in the staging block
+  uint64_t src, src2;                        // of row 0 of the source in the draws' block; PLACE_M_ROW: src the permutations, src2 vec_m_blinders
+  uint32_t kind, dst_w, src_w, pad;          // src_w: the elements a source row holds (PLACE_M_ROW: its blinders)
+};
+inline PlaceField place_resolve(const PlaceRule& r, size_t ell, size_t P, size_t dst) {
+  const size_t n = ell + N_BLINDERS;
+  const DrawColumns C = draw_columns(ell, P);
+  const DrawBlock B = draw_block(ell, P);
+  const size_t perm_at = B.perm, scalars_at = B.scalars;
+  PlaceField f{};
+  f.dst = dst; f.kind = r.kind; f.dst_w = (uint32_t)(r.dst_n * (long)n + r.dst_c);
+  if (r.kind == PLACE_WORDS) { f.src = perm_at; f.src_w = (uint32_t)ell; return f; }
+  f.src = scalars_at + 32 * C.at[r.column]; f.src_w = (uint32_t)column_width(r.column, n);
+  if (r.kind == PLACE_M_ROW) { f.src2 = f.src; f.src = perm_at; }
+  return f;
+}
+// the bytes of a block's witness fields for P provers: the sum of the fields' lengths
+inline size_t place_bytes(int block, size_t ell, size_t P) {
+  const long n = (long)(ell + N_BLINDERS);
+  size_t sum = 0;
+  for (const PlaceRule& r : PLACE_RULES)
+    if (r.block == block) sum += P * (size_t)(r.dst_n * n + r.dst_c) * (r.kind == PLACE_WORDS ? 4u : 32u);
+  return sum;
+}
+CG1WHISK_HD uint32_t place_elem_bytes(const PlaceField& f) { return f.kind == PLACE_WORDS ? 4u : 32u; }
+// THE FUNCTION: element e of destination prover q's row of field f comes from `bytes` bytes at `at` in the draws' block, the rest of the
+// element zero (bytes == 0: a zero element); p = keep[q], the prover of the draws that destination prover q is
+struct PlaceSrc { uint64_t at; uint32_t bytes; };
+CG1WHISK_HD PlaceSrc place_source(const PlaceField& f, uint32_t ell, uint32_t p, uint32_t e) {
+  PlaceSrc s; s.at = 0; s.bytes = 0;
+  if (f.kind == PLACE_WORDS || (f.kind == PLACE_M_ROW && e < ell)) { s.at = f.src + 4ull * ((uint64_t)p * ell + e); s.bytes = 4u; return s; }
+  if (f.kind == PLACE_M_ROW) { s.at = f.src2 + 32ull * ((uint64_t)p * f.src_w + (e - ell)); s.bytes = 32u; return s; }
+  if (e < f.src_w) { s.at = f.src + 32ull * ((uint64_t)p * f.src_w + e); s.bytes = 32u; }
+  return s;
+}
+// a field placed on the host: the emulation's loop over what the kernel does a lane per 16 bytes.  keep == NULL: q itself
+inline void place_field_host(uint8_t* block, const PlaceField& f, const uint8_t* draws, size_t ell, const size_t* keep, size_t Q) {
+  const size_t eb = place_elem_bytes(f);
+  for (size_t q = 0; q < Q; ++q)
+    for (size_t e = 0; e < f.dst_w; ++e) {
+      const PlaceSrc s = place_source(f, (uint32_t)ell, (uint32_t)(keep ? keep[q] : q), (uint32_t)e);
+      uint8_t* d = block + f.dst + (q * f.dst_w + e) * eb;
+      memset(d, 0, eb);
+      memcpy(d, draws + s.at, s.bytes);
+    }
+}
+
 // The witness of P shuffles of one ell as the whole-shuffle prover takes it: the permutations (P rows of ell indices) and the eight scalar
 // columns (P rows of column_width scalars each).  A view: it owns nothing, and whoever owns the bytes wipes them.
+// Two variants.  HOST: perm and col point into host memory.  RESIDENT (d_draws set; perm and col null): the witness is the draws' block
+// on the device, `draws_P` provers of it, of which this view's prover q is number keep[q] (keep == NULL: q) -- no byte of it is on the
+// host, and whisk_front / shuffle_prove place it into their blocks with k_whisk_witness_place instead of staging it.
 struct ShuffleWitness {
   size_t ell, P;
   const uint32_t* perm;
   const uint8_t* col[N_COLUMNS];
+  const uint8_t* d_draws = nullptr;
+  size_t draws_P = 0;
+  const size_t* keep = nullptr;
+  bool resident() const { return d_draws != nullptr; }
+  static ShuffleWitness resident_draws(const uint8_t* d_draws, size_t ell, size_t P) {
+    ShuffleWitness w{ell, P, nullptr, {}};
+    w.d_draws = d_draws; w.draws_P = P;
+    return w;
+  }
   // the permutations at `perm`, the columns one after the other from `scalars`
   static ShuffleWitness over(const uint8_t* perm, const uint8_t* scalars, size_t ell, size_t P) {
     const DrawColumns C = draw_columns(ell, P);
@@ -167,7 +260,9 @@ struct ShuffleWitness {
     return over(stage, stage + (B.scalars - B.perm), ell, P);
   }
   // the rows keep[0] < keep[1] < .. < keep[Q - 1] of every column copied into `into`; all P rows: this view itself, and no copy
+  // (a resident witness: the same view with the list as its index, and no copy -- `keep` must outlive it)
   ShuffleWitness gather(const size_t* keep, size_t Q, cg1::WipedBytes& into) const {
+    if (resident()) { ShuffleWitness w = *this; w.P = Q; w.keep = keep; return w; }
     if (Q == P) return *this;
     into.v.assign(Q * ell * 4 + 32 * draw_columns(ell, Q).total, 0);
     uint8_t* base = into.v.data();

@@ -84,9 +84,12 @@ class ShuffleBatchProver:
 
     crs: any object with vec_G (ell points), vec_H (4), H, G_t and G_u as G1Points; ell + 4 is a power of two in 8 .. 1024.
     table: a fixed_base.FixedBaseTable holding those very objects (FixedBaseTable.for_crs(crs)); made here when not given, and then
-    owned and closed by this prover (close(), or the `with` statement)."""
+    owned and closed by this prover (close(), or the `with` statement).
+    resident_witness: the seeded calls (generate_packed, generate_seeded) keep what they draw on the device -- the context parameter
+    "whisk_resident_witness", set around each native call and left at 0; the same bytes come out.  prove_many and generate() take the
+    caller's draws, host data by definition, and do not look at it."""
 
-    def __init__(self, crs, table=None):
+    def __init__(self, crs, table=None, resident_witness=False):
         from .fixed_base import FixedBaseTable
 
         self.crs = crs
@@ -99,6 +102,7 @@ class ShuffleBatchProver:
             table = FixedBaseTable.for_crs(crs) if hasattr(crs, "G_sum") and hasattr(crs, "H_sum") else FixedBaseTable(
                 list(crs.vec_G) + list(crs.vec_H) + [crs.H, crs.G_t, crs.G_u])
         self.table = table
+        self.resident_witness = bool(resident_witness)
         self._fixed = None                                   # the table indices and G_t | G_u | H, looked up at the first call
         self.last_status: List[int] = []                     # of the last seeded call, per shuffle: a key of REJECT_NAMES
         self.last_refusals: List[Optional[Tuple[int, str]]] = []        # ... and (tracker index, "r_G" | "k_r_G") where the status is not 0
@@ -222,12 +226,16 @@ class ShuffleBatchProver:
             if table._KIND != "fixed-base":
                 raise TypeError("the device pipeline of a shuffle proof runs over a FixedBaseTable")
             gi, hi, ui, gti, gui, gth = self._crs_args()
-            for lo in range(0, count, step):
-                P = min(step, count - lo)
-                post, out, st, at = table._ctx.whisk_shuffle_prove_seeded(table._tab, ell, P, gi * P, hi * P, [ui] * P, [gti] * P, [gui] * P, gth,
-                                                                          trackers96[96 * ell * lo: 96 * ell * (lo + P)], seed, first_index + lo)
-                posts.append(post); proofs.append(out); status += st
-                refusals += [(a >> 1, HALF_NAMES[a & 1]) if s else None for s, a in zip(st, at)]
+            table._ctx.set_param("whisk_resident_witness", int(self.resident_witness))
+            try:
+                for lo in range(0, count, step):
+                    P = min(step, count - lo)
+                    post, out, st, at = table._ctx.whisk_shuffle_prove_seeded(table._tab, ell, P, gi * P, hi * P, [ui] * P, [gti] * P, [gui] * P, gth,
+                                                                              trackers96[96 * ell * lo: 96 * ell * (lo + P)], seed, first_index + lo)
+                    posts.append(post); proofs.append(out); status += st
+                    refusals += [(a >> 1, HALF_NAMES[a & 1]) if s else None for s, a in zip(st, at)]
+            finally:
+                table._ctx.set_param("whisk_resident_witness", 0)
         self.last_status, self.last_refusals = status, refusals
         return b"".join(posts), b"".join(proofs), list(status)
 

@@ -108,6 +108,8 @@ void* cg1_ctx_stream(cg1_ctx* ctx);                                  /* the cont
  *   verifier front-end  "fe_rows" (1: block program, 0: byte-level machine), "fe_timed" (shader-clock split of a launch), "fe_prio" (0..3)
  *   fixed-base tables   "fixed_slice" (terms per workgroup of k_table_msm, 1..128; 0: by the size of the call), "fixed_waves" (4, 8, 16 waves per
  *                       workgroup; 0: by the size of the call)
+ *   Whisk shuffles      "whisk_resident_witness" (0 | 1, default 0: cg1_whisk_shuffle_prove_seeded keeps the permutation, k and every blinder it draws
+ *                       on the device -- see there)
  *   test support        "alloc_fail_at" (k >= 1: the k-th allocation this context attempts from now on while growing a buffer it keeps between calls
  *                       -- its own, or a table's / front-end handle's -- fails as out of memory without reaching the runtime, then the parameter is
  *                       0 again; 0 disarms.  The refused call returns CG1_ERR_HIP and leaves the buffers it was growing empty, as a real failure does)
@@ -1036,7 +1038,29 @@ int cg1_whisk_shuffle_front_emulate(size_t ell, const uint8_t* trackers96, const
  *   out_post96 and out_proofs and leaves the others as they would be without it.  Every other refusal is the whole call's, as
  *   cg1_whisk_shuffle_prove_device makes it, and leaves all four outputs untouched; a text of the chain counts the provers that reached it.
  *   Before returning, the device buffer of the draws and the table's staging block (both copies) are zeroed and the host staging of the
- *   draws is wiped; neither the seed nor a draw appears in an error text. */
+ *   draws is wiped; neither the seed nor a draw appears in an error text.
+ *   With the context parameter "whisk_resident_witness" = 1 step (1) makes NO copy down: the draws stay in the context's draws buffer and
+ *   k_whisk_witness_place (csrc/kernels_whisk_shuffle.h) copies them, on the device, into the witness fields of the front's and the chain's
+ *   staging blocks, behind the uploads of the public fields and in front of the first kernel that reads them -- destination prover q from
+ *   the q-th prover with status 0.  The host block's witness fields are never written, no gathered copy or staging vector is made, and the
+ *   host checks on witness VALUES (scalars below r, permutation entries below ell, vec_c_blinders[2] != 0) are skipped: the draws are
+ *   reduced mod r and permutations by construction, and the zero events set the chains' status bits on the device all the same.  The same
+ *   bytes come out for the same seed.  The draws buffer is zeroed by a scope guard on every way out of the call.  What then still touches
+ *   host memory of a call's secrets: the 32-byte seed (the caller's buffer, the kernel arguments).  cg1_chain_prove_seeded,
+ *   cg1_whisk_shuffle_prove_device and cg1_whisk_shuffle_draws_device do not read the parameter.
+ * cg1_whisk_last_witness_traffic   test support: of the last cg1_whisk_shuffle_prove_seeded call on the context, out[0] = witness bytes copied
+ *   device -> host, out[1] = witness bytes the library wrote into host memory (staging, gathered rows, the blocks' witness fields).  Plain
+ *   host counters, zeroed when a seeded call begins.  Both non-zero after a call that proved something on the copying path; 0 and 0 on the
+ *   resident one.
+ * cg1_whisk_draws_buffer_is_zero   test support: 1 when every byte of the context's draws buffer is zero (or it has none), 0 when not, -1
+ *   on a HIP error.  One D2H copy.
+ * cg1_whisk_witness_block_emulate  host only, no HIP call, test support: the front's (which_block = 0) or the chain's (1) staging block laid
+ *   out as the seeded entry lays it out for P drawn shuffles, of which keep[0] < .. < keep[Q - 1] reach the chain (NULL: all; the front
+ *   takes all P whatever keep says), with ONLY the witness fields filled from draws_block (swaps | perm | scalars as the draws buffer holds
+ *   them, 64-byte aligned parts) -- resident = 0: by the copying path's gather and stage functions; resident = 1: by the placement map the
+ *   kernel shares.  -> the block's length in bytes (0: a shape the entry refuses, a bad keep list, a null pointer).  out (cap bytes) is
+ *   written only if cap >= that length; out_fields gets (offset, length) per witness field, up to the *n_fields pairs it holds on entry,
+ *   and *n_fields becomes the number of fields. */
 #define CG1_WHISK_SHUFFLE_DRAWS_MAX_PROVERS 4096
 #define CG1_WHISK_SHUFFLE_NO_DECODE 2   /* a tracker point is not a compressed encoding of a curve point */
 #define CG1_WHISK_SHUFFLE_NOT_G1    3   /* a tracker point lies outside the prime-order subgroup */
@@ -1045,6 +1069,10 @@ int cg1_whisk_shuffle_draws(size_t ell, size_t n_provers, const uint8_t* seed32,
 int cg1_whisk_shuffle_prove_seeded(cg1_ctx* ctx, cg1_fixed* tab, size_t ell, size_t n_provers, const uint32_t* g_index, const uint32_t* h_index, const uint32_t* u_index,
                                    const uint32_t* gt_index, const uint32_t* gu_index, const uint8_t* gth_affine96, const uint8_t* trackers96, const uint8_t* seed32,
                                    uint64_t first_index, uint8_t* out_post96, uint8_t* out_proofs, int32_t* out_status /* n_provers */, uint32_t* out_bad_at /* n_provers */);
+void cg1_whisk_last_witness_traffic(const cg1_ctx* ctx, uint64_t out[2]);
+int cg1_whisk_draws_buffer_is_zero(cg1_ctx* ctx);
+size_t cg1_whisk_witness_block_emulate(size_t ell, size_t P, const size_t* keep, size_t Q, const uint8_t* draws_block, int resident, int which_block, uint8_t* out, size_t cap,
+                                       uint64_t* out_fields, size_t* n_fields);
 
 /* ---- A chain of Whisk shuffles PROVED over the resident tracker set (the set: cg1_chain_expand above; shuffle_chain.py).  Block j, in order,
  * reads pre_j = [set[i] for i in indices_j] before any of its own writes and, unless refused, writes set[indices_j[t]] = k_j * pre_j[perm_j[t]],
