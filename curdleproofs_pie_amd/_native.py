@@ -176,6 +176,27 @@ cg1_get_last_counts = _proto("cg1_get_last_counts", c_int, c_void_p, POINTER(cty
 cg1_get_last_tail = _proto("cg1_get_last_tail", ctypes.c_uint32, c_void_p)
 cg1_get_last_launches = _proto("cg1_get_last_launches", c_int, c_void_p)
 cg1_plan_describe = _proto("cg1_plan_describe", c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int)
+cg1_msm_call_describe = _proto("cg1_msm_call_describe", c_int, POINTER(ctypes.c_char_p), POINTER(c_int), c_int, c_size_t, c_int, c_int, c_int, c_int, c_size_t, c_size_t, c_int,
+                               POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32))
+ENGINES = (None, "k_msm_small", "regime A", "regime A, two chains", "regime B", "regime B, two chains")      # CG1_ENGINE_*
+
+
+def msm_call_describe(switches, n, window_c=0, shard_rank=0, shard_world=1, source_kind=0, n_msms=0, max_terms=0, e_top=0):
+    """What an MSM call would launch under cg1_ctx_set_param settings `switches` ({name: value}) over the defaults, from the engine's own
+    planner (cg1_msm_call_describe; no GPU, no context) -> {"engine": one of ENGINES, "c", "glv", "chunk_len", "tail": the word
+    cg1_get_last_tail returns after the call}, or None where cg1_ctx_set_param or the call answers CG1_ERR_ARG."""
+    names = (ctypes.c_char_p * max(1, len(switches)))(*[k.encode() for k in switches])
+    values = (c_int * max(1, len(switches)))(*[int(v) for v in switches.values()])
+    engine, c, glv, chunk_len, tail = c_int(), c_int(), c_int(), ctypes.c_uint32(), ctypes.c_uint32()
+    rc = cg1_msm_call_describe(names, values, len(switches), n, window_c, shard_rank, shard_world, source_kind, n_msms, max_terms, e_top,
+                               ctypes.byref(engine), ctypes.byref(c), ctypes.byref(glv), ctypes.byref(chunk_len), ctypes.byref(tail))
+    if rc == ERR_ARG:
+        return None
+    if rc != OK:
+        raise NativeError(f"cg1_msm_call_describe failed with status {rc}")
+    return {"engine": ENGINES[engine.value], "c": c.value, "glv": bool(glv.value), "chunk_len": chunk_len.value, "tail": tail.value}
+
+
 cg1_timer_begin = _proto("cg1_timer_begin", c_int, c_void_p)
 cg1_timer_end = _proto("cg1_timer_end", c_int, c_void_p, POINTER(c_float))
 cg1_batch_mul_device = _proto("cg1_batch_mul_device", c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t)
@@ -401,7 +422,7 @@ EXPORTED_SYMBOLS = [
     "cg1_comm_create", "cg1_comm_port", "cg1_comm_rank", "cg1_comm_connect", "cg1_comm_set_timeout", "cg1_comm_attach_rccl", "cg1_comm_transport",
     "cg1_comm_world_seen", "cg1_comm_error", "cg1_comm_allgather", "cg1_comm_allgather_host", "cg1_comm_barrier", "cg1_comm_allreduce_g1", "cg1_comm_destroy",
     "cg1_validate_compressed", "cg1_fp_jacobi", "cg1_batch_decompress_pool", "cg1_batch_subgroup_pool", "cg1_batch_subgroup", "cg1_lincomb_batch", "cg1_lincomb_batch_pool", "cg1_glv_split", "cg1_batch_decompress_rows",
-    "cg1_probe_add_chain", "cg1_probe_fp_ops", "cg1_probe_g1_ops", "cg1_probe_fr_ops", "cg1_fr_ops_host", "cg1_msm_blobs", "cg1_stage_reserve", "cg1_msm_blobs_device", "cg1_vec_create", "cg1_vec_destroy", "cg1_vec_len", "cg1_msm_vec", "cg1_batch_normalize", "cg1_batch_from_affine96", "cg1_get_last_launches", "cg1_plan_describe",
+    "cg1_probe_add_chain", "cg1_probe_fp_ops", "cg1_probe_g1_ops", "cg1_probe_fr_ops", "cg1_fr_ops_host", "cg1_msm_blobs", "cg1_stage_reserve", "cg1_msm_blobs_device", "cg1_vec_create", "cg1_vec_destroy", "cg1_vec_len", "cg1_msm_vec", "cg1_batch_normalize", "cg1_batch_from_affine96", "cg1_get_last_launches", "cg1_plan_describe", "cg1_msm_call_describe",
     "cg1_fixed_create", "cg1_fixed_destroy", "cg1_fixed_len", "cg1_fixed_bytes", "cg1_fixed_msm", "cg1_fixed_msm_device", "cg1_fixed_digits",
     "cg1_ipa_proof_bytes", "cg1_ipa_prove_device", "cg1_ipa_round_emulate",
     "cg1_light_create", "cg1_light_destroy", "cg1_light_len", "cg1_light_bytes", "cg1_light_msm", "cg1_light_msm_device", "cg1_light_digits",

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcurdle_g1.so")
 SOURCES = [os.path.join(CSRC, "msm_gpu.hip"), os.path.join(CSRC, "host_g1.cpp"), os.path.join(CSRC, "merlin.cpp"), os.path.join(CSRC, "shuffle_verify.cpp"), os.path.join(CSRC, "comm.cpp"), os.path.join(CSRC, "lazy_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("kernels_opening.h", "kernels_generator.h", "kernels_fixed.h", "fixed_digits.h", "capi_fixed.h", "kernels_light.h", "light_digits.h", "capi_light.h", "kernels_tracker_scan.h", "capi_tracker_scan.h", "kernels_register.h", "capi_register.h", "kernels_tracker_set.h", "capi_tracker_set.h", "kernels_chain_prove.h", "capi_chain_prove.h", "chain_lineage.h", "kernels_exact.h", "capi_exact.h", "kernels_chain.h", "chain_rounds.h", "capi_chain.h", "kernels_ipa.h", "ipa_rounds.h", "capi_ipa.h", "kernels_same_msm.h", "same_msm_rounds.h", "capi_same_msm.h", "kernels_gprod.h", "gprod_rounds.h", "capi_gprod.h", "kernels_same_perm.h", "same_perm_rounds.h", "capi_same_perm.h", "kernels_same_scalar.h", "same_scalar_rounds.h", "capi_same_scalar.h", "kernels_shuffle.h", "shuffle_rounds.h", "capi_shuffle.h", "kernels_whisk_shuffle.h", "capi_whisk_shuffle.h", "whisk_shuffle_host.h", "fp28.h", "g1_xyzz.h", "g1_quad.h", "host_g1.h", "fe_mul_x86.h", "fr.h", "merlin_group.h", "bls_consts.h", "kernels_records.h", "kernels_prepare_digits.h",
-                                                    "kernels_sort.h", "kernels_accumulate.h", "kernels_reduce.h", "kernels_small.h", "kernels_batch.h", "kernels_rows.h", "kernels_merlin.h", "kernels_frontend.h", "pool.h", "secret_wipe.h", "lazy_host.h", "fp_row.h", "glv.h", "host_context.h", "host_chains.h", "capi_core_msm.h", "capi_vec_batched.h", "capi_lincomb.h",
+                                                    "kernels_sort.h", "kernels_accumulate.h", "kernels_reduce.h", "kernels_small.h", "kernels_batch.h", "kernels_rows.h", "kernels_merlin.h", "kernels_frontend.h", "pool.h", "secret_wipe.h", "lazy_host.h", "fp_row.h", "glv.h", "host_context.h", "msm_plan.h", "host_chains.h", "capi_core_msm.h", "capi_vec_batched.h", "capi_lincomb.h",
                                                     "capi_timing_batchmul.h", "capi_codec_transcripts.h", "capi_frontend.h", "capi_rows_probes.h")] + [
     os.path.join(HERE, "..", "include", "curdle_g1.h")
 ]

@@ -16,10 +16,10 @@ static int ensure_child(Ctx* ctx) {
   if (!ctx->child) {
     cg1_ctx* made = ctx->cu_mask.empty() ? cg1_ctx_create(ctx->device) : cg1_ctx_create_cu_mask(ctx->device, ctx->cu_mask.data(), ctx->cu_mask.size());
     if (!made) { snprintf(ctx->err, sizeof ctx->err, "could not create the second launch chain's context"); return CG1_ERR_HIP; }
-    made->split = 0;
-    made->batched_split = 0;
     ctx->child = made;
   }
+  static_cast<MsmSwitches&>(*child_of(ctx)) = *ctx;          // the second chain runs under this call's switches, all of them -- but never splits again
+  child_of(ctx)->split = child_of(ctx)->batched_split = 0;
   if (!ctx->ev_prep) HIPCHK(hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming));
   if (!ctx->ev_acc) HIPCHK(hipEventCreateWithFlags(&ctx->ev_acc, hipEventDisableTiming));
   return CG1_OK;
@@ -29,14 +29,11 @@ static int msm_begin_split(Ctx* ctx, const PtSrc& src, const void* d_scalars32, 
   HIPCHK(hipSetDevice(ctx->device));
   { int crc = ensure_child(ctx); if (crc) return crc; }
   Ctx* ch = child_of(ctx);
-  ch->profile = ctx->profile; ch->L0 = ctx->L0; ch->seg_m = ctx->seg_m; ch->quad = ctx->quad; ch->reduce_2d = ctx->reduce_2d;
-  ch->rowcol_quad = ctx->rowcol_quad; ch->rowcol_quad_max = ctx->rowcol_quad_max; ch->fold_pass = ctx->fold_pass; ch->tree_half = ctx->tree_half; ch->tree_shift = ctx->tree_shift; ch->rowcol_lgq = ctx->rowcol_lgq; ch->tree_row = ctx->tree_row; ch->rowcol_row = ctx->rowcol_row; ch->sort_sub_bits = ctx->sort_sub_bits;
-  ch->scan_one = ctx->scan_one; ch->zero_copy = ctx->zero_copy; ch->horner_threads = ctx->horner_threads; ch->host_split = ctx->host_split;
-  ch->blocking_sync = ctx->blocking_sync; ch->stage_sort = ctx->stage_sort; ch->use_partition_sort = ctx->use_partition_sort; ch->big_bins = ctx->big_bins;
-  const int n_own = win_count(plan.nwin, rank, world), n_lo = n_own / 2, n_hi = n_own - n_lo;      // this rank's windows: the upper ones here, the lower ones on the child
+  int sel_hi, sel_lo;                                       // this rank's windows: the upper ones here, the lower ones on the child
+  split_selectors(plan, rank, world, sel_hi, sel_lo);
   ChainHooks hi;
   hi.after_prepare = ctx->ev_prep; hi.after_accumulate = ctx->ev_acc;
-  int rc = msm_enqueue(ctx, src, d_scalars32, n, plan, rank, win_sel(world, n_lo, n_hi), hi);
+  int rc = msm_enqueue(ctx, src, d_scalars32, n, plan, rank, sel_hi, hi);
   if (rc) return rc;
   PtSrc shared;
   shared.kind = PtSrc::PREPARED;
@@ -44,7 +41,7 @@ static int msm_begin_split(Ctx* ctx, const PtSrc& src, const void* d_scalars32, 
   shared.flags = src.kind == PtSrc::PREPARED ? src.flags : ctx->d_flags;
   ChainHooks lo;
   lo.before_start = ctx->ev_prep; lo.before_accumulate = ctx->ev_acc;
-  rc = msm_enqueue(ch, shared, d_scalars32, n, plan, rank, win_sel(world, 0, n_lo), lo);
+  rc = msm_enqueue(ch, shared, d_scalars32, n, plan, rank, sel_lo, lo);
   if (rc) { snprintf(ctx->err, sizeof ctx->err, "%s", ch->err); cg1h::jac dummy; (void)msm_finish(ctx, dummy); return rc; }
   ctx->pend_split = true;
   return CG1_OK;
@@ -290,46 +287,20 @@ int cg1_ctx_device(const cg1_ctx* ctx) { return ctx ? ctx->device : -1; }
 void* cg1_ctx_stream(cg1_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 int cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value) {
   if (!ctx || !name) return CG1_ERR_ARG;
+  switch (cg1::set_msm_switch(*ctx, name, value)) {          // the MSM chains' switches; here only what a change of one does to the context
+    case cg1::SW_RANGE: return CG1_ERR_ARG;
+    case cg1::SW_SET:
+      if (!strcmp(name, "chunk_len") || !strcmp(name, "partition_sort")) cg1::free_bufs(ctx);      // the scratch buffers were sized under the old value
+      return CG1_OK;
+    default: break;
+  }
   if (!strcmp(name, "alloc_fail_at")) { if (value < 0) return CG1_ERR_ARG; ctx->alloc_fail_at = value; return CG1_OK; }
   if (!strcmp(name, "whisk_resident_witness")) { if (value != 0 && value != 1) return CG1_ERR_ARG; ctx->whisk_resident = value; return CG1_OK; }
-  if (!strcmp(name, "chunk_rule")) { ctx->chunk_rule = value != 0; return CG1_OK; }
-  if (!strcmp(name, "chunk_len")) { if (value < 1 || value > 65536) return CG1_ERR_ARG; ctx->L0 = (uint32_t)value; cg1::free_bufs(ctx); return CG1_OK; }
-  if (!strcmp(name, "stage_sort")) { ctx->stage_sort = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "quad")) { ctx->quad = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "glv")) { if (value < 0 || value > 2) return CG1_ERR_ARG; ctx->glv = value; return CG1_OK; }
-  if (!strcmp(name, "glv_max_n")) { if (value < 0) return CG1_ERR_ARG; ctx->glv_max_n = value; return CG1_OK; }
-  if (!strcmp(name, "batched_split")) { ctx->batched_split = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "batched_split_min_m")) { if (value < 2) return CG1_ERR_ARG; ctx->batched_split_min_m = value; return CG1_OK; }
   if (!strcmp(name, "lincomb_zero_copy")) { ctx->lincomb_zero_copy = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "fold_quad")) { ctx->fold_quad = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "rowcol_row")) { ctx->rowcol_row = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "tree_row")) { ctx->tree_row = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "horner_row")) { ctx->horner_row = value ? 1 : 0; return CG1_OK; }
   if (!strcmp(name, "batch_mul_row")) { ctx->batch_mul_row = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "small_msm")) { ctx->small_msm = value ? 1 : 0; return CG1_OK; }
   if (!strcmp(name, "fixed_slice")) { if (value < 0 || value > 128) return CG1_ERR_ARG; ctx->fixed_slice = value; return CG1_OK; }
   if (!strcmp(name, "fixed_waves")) { if (value != 0 && value != 4 && value != 8 && value != 16) return CG1_ERR_ARG; ctx->fixed_waves = value; return CG1_OK; }
   if (!strcmp(name, "ipa_inv")) { if (value != 0 && value != 1) return CG1_ERR_ARG; ctx->ipa_inv = value; return CG1_OK; }
-  if (!strcmp(name, "small_row_tail")) { ctx->small_row_tail = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "split")) { ctx->split = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "split_min_log2n")) { if (value < 10 || value > 31) return CG1_ERR_ARG; ctx->split_min_n = (size_t)1 << value; return CG1_OK; }
-  if (!strcmp(name, "reduce_2d")) { ctx->reduce_2d = value ? 1 : 0; return CG1_OK; }
-  if (!strcmp(name, "partition_sort")) { ctx->use_partition_sort = value ? 1 : 0; cg1::free_bufs(ctx); return CG1_OK; }
-  if (!strcmp(name, "blocking_sync")) { ctx->blocking_sync = value != 0; return CG1_OK; }
-  if (!strcmp(name, "big_bins")) { ctx->big_bins = value != 0; return CG1_OK; }
-  if (!strcmp(name, "host_split")) { ctx->host_split = value != 0; return CG1_OK; }
-  if (!strcmp(name, "arm_helpers")) { ctx->arm_helpers = value != 0; return CG1_OK; }
-  if (!strcmp(name, "horner_threads")) { if (value != 1 && value != 2 && value != 4) return CG1_ERR_ARG; ctx->horner_threads = value; return CG1_OK; }
-  if (!strcmp(name, "zero_copy")) { ctx->zero_copy = value != 0; return CG1_OK; }
-  if (!strcmp(name, "auto_plan")) { ctx->auto_plan = value != 0; return CG1_OK; }
-  if (!strcmp(name, "rowcol_quad")) { ctx->rowcol_quad = value != 0; return CG1_OK; }
-  if (!strcmp(name, "rowcol_quad_max")) { if (value < 0) return CG1_ERR_ARG; ctx->rowcol_quad_max = value; return CG1_OK; }
-  if (!strcmp(name, "fold_pass")) { ctx->fold_pass = value != 0; return CG1_OK; }
-  if (!strcmp(name, "scan_one")) { ctx->scan_one = value != 0; return CG1_OK; }
-  if (!strcmp(name, "batched_host_horner_max")) { if (value < 0) return CG1_ERR_ARG; ctx->batched_host_horner_max = value; return CG1_OK; }
-  if (!strcmp(name, "tree_shift")) { if (value < -1 || value > 4) return CG1_ERR_ARG; ctx->tree_shift = value; return CG1_OK; }
-  if (!strcmp(name, "rowcol_lgq")) { if (value != 0 && (value < 2 || value > 4)) return CG1_ERR_ARG; ctx->rowcol_lgq = value; return CG1_OK; }
-  if (!strcmp(name, "sort_sub_bits")) { if (value != 0 && (value < 4 || value > 8)) return CG1_ERR_ARG; ctx->sort_sub_bits = value; return CG1_OK; }
   if (!strcmp(name, "batch_mul_host_max")) { if (value < -1) return CG1_ERR_ARG; ctx->batch_mul_host_max = value; return CG1_OK; }
   if (!strcmp(name, "batch_mul_quad_max")) { if (value < 0) return CG1_ERR_ARG; ctx->batch_mul_quad_max = value; return CG1_OK; }
   if (!strcmp(name, "merlin_sync")) { ctx->merlin_sync = value != 0; return CG1_OK; }
@@ -341,15 +312,12 @@ int cg1_ctx_set_param(cg1_ctx* ctx, const char* name, int value) {
   if (!strcmp(name, "decompress_waves")) { if (value != 2 && value != 3) return CG1_ERR_ARG; ctx->decompress_waves = value; return CG1_OK; }
   if (!strcmp(name, "merlin_rows")) { ctx->merlin_rows = value != 0; return CG1_OK; }
   if (!strcmp(name, "merlin_lanes")) { if (value < 1 || value > 64) return CG1_ERR_ARG; ctx->merlin_lanes = value; return CG1_OK; }
-  if (!strcmp(name, "tree_half")) { ctx->tree_half = value != 0; return CG1_OK; }
   if (!strcmp(name, "wave_agg")) {
     int v = value ? 1 : 0;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(cg1::g_wave_agg), &v, sizeof v));
     return CG1_OK;
   }
-  if (!strcmp(name, "profile")) { if (value < 0 || value > 2) return CG1_ERR_ARG; ctx->profile = value; return CG1_OK; }
-  if (!strcmp(name, "seg_m")) { if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return CG1_ERR_ARG; ctx->seg_m = (uint32_t)value; return CG1_OK; }
   return CG1_ERR_ARG;
 }
 

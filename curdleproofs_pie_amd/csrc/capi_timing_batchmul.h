@@ -23,6 +23,40 @@ int cg1_plan_describe(int window_c, int glv, int* out_offsets, int* out_widths, 
   return pl.nwin;
 }
 
+// What an MSM call would launch (no GPU, no context): the planner's answer for a default switch set with `n_switches` of them changed
+// (include/curdle_g1.h has the layout).  The launch chains run the same functions, so this word IS what cg1_get_last_tail returns afterwards.
+int cg1_msm_call_describe(const char* const* switch_names, const int* switch_values, int n_switches, size_t n, int window_c, int shard_rank,
+                          int shard_world, int source_kind, size_t n_msms, size_t max_terms, int e_top,
+                          int* out_engine, int* out_c, int* out_glv, uint32_t* out_chunk_len, uint32_t* out_tail) {
+  using namespace cg1;
+  MsmSwitches sw;
+  for (int i = 0; i < n_switches; ++i)
+    if (!switch_names || !switch_values || !switch_names[i] || set_msm_switch(sw, switch_names[i], switch_values[i]) != SW_SET) return CG1_ERR_ARG;
+  if (source_kind < SRC_AFFINE96 || source_kind > SRC_PREPARED) return CG1_ERR_ARG;
+  const Route r = n_msms ? route_batched_call(sw, n_msms, n, max_terms, window_c, false) : route_msm_call(sw, n, window_c, shard_rank, shard_world, source_kind);
+  if (r.rc) return r.rc;
+  uint32_t L = 0, word = 0;
+  if (r.engine == ENGINE_SMALL) {
+    word = tail_with_horner(tail_word(small_tail(sw)), HORNER_HOST, small_horner_threads(sw, n_msms ? n_msms : 1, e_top));
+  } else if (r.engine == ENGINE_CHAIN_A || r.engine == ENGINE_TWO_CHAINS_A) {
+    int sel = shard_world, sel_lo = 0;
+    if (r.engine == ENGINE_TWO_CHAINS_A) split_selectors(r.plan, shard_rank, shard_world, sel, sel_lo);      // the context's own chain: the upper windows
+    const ChainPlan cp = plan_regime_a(sw, n, r.plan, shard_rank, sel, source_kind == SRC_PREPARED);
+    if (cp.nlw > 0) { L = cp.L; word = tail_with_horner(tail_word(cp.tail), HORNER_HOST, (uint32_t)host_horner_threads(sw, e_top)); }
+  } else if (r.engine != ENGINE_NONE) {
+    const bool two = r.engine == ENGINE_TWO_CHAINS_B;                // the context's own chain: the first M / 2 MSMs, taken as half the terms
+    const BatchPlan bp = plan_regime_b(sw, two ? n_msms / 2 : n_msms, two ? n / 2 : n, r.c, r.glv);
+    if (bp.rc) return bp.rc;
+    L = bp.L; word = tail_word(bp.tail);
+  }
+  if (out_engine) *out_engine = (int)r.engine;
+  if (out_c) *out_c = r.c;
+  if (out_glv) *out_glv = r.glv ? 1 : 0;
+  if (out_chunk_len) *out_chunk_len = L;
+  if (out_tail) *out_tail = word;
+  return CG1_OK;
+}
+
 int cg1_get_last_counts(const cg1_ctx* ctx, uint32_t* entries, uint32_t* chunks) {
   if (!ctx) return CG1_ERR_ARG;
   if (entries) *entries = ctx->last_entries;

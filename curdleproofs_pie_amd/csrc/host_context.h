@@ -73,7 +73,94 @@ struct Helper {
   }
 };
 
-struct Ctx {
+// Every switch the MSM launch chains and their planner (msm_plan.h) read, with its default.  A context IS one (Ctx derives from it), so a
+// second launch chain's context takes them all with one assignment, and the planner can be asked about a call without a context.
+struct MsmSwitches {
+  uint32_t L0 = 8;                      // "chunk_len": MINIMUM chunk length; the per-call length grows with the entry count
+  uint32_t seg_m = 4;                   // "seg_m": segment length of k_seg_reduce (1, 2, 4, 8, 16)
+  int chunk_rule = 1;                   // "chunk_rule": whole-bucket chunks at 2^17 .. 2^19 terms (A/B switch)
+  int stage_sort = 1;                   // LDS-staged, line-coalesced writes in k_part_scatter / k_bin_sort (A/B switch)
+  int quad = 1;                         // quad-lane EC ops in the latency-bound kernels (A/B switch)
+  int reduce_2d = 1;                    // 1: k_rowcol + k_small_tree; 0: k_seg_reduce + k_bit_tree (A/B switch)
+  int use_partition_sort = 1;           // "partition_sort": the two-level LDS partition sort up to 2^23 rows; 0: the global-atomic counting sort
+  int big_bins = 1;                     // giant bins of skewed scalars sorted by many blocks (A/B switch)
+  int sort_sub_bits = 0;                // partition sort: sub-bucket bits a k_bin_sort workgroup sorts by ("sort_sub_bits": 4 .. 8; 0 = 7 up to 2^16 terms, else 8)
+  int scan_one = 1;                     // the sort's two scans as one single-block launch each when they are small (A/B switch)
+  int fold_pass = 1;                    // k_bucket_fold in front of k_rowcol / k_seg_reduce; 0 leaves multi-chunk buckets to their bucket_sum loops
+                                        // (measured WORSE: 372 instead of 235 us at 2^16 -- divergent trip counts inside the row / column lanes)
+  int fold_quad = 1;                    // "fold_quad": small bucket counts: k_bucket_fold_quad (1) or the one-lane-per-bucket k_bucket_fold (0); A/B switch
+  int rowcol_quad = 1;                  // k_rowcol_quad for small bucket counts (A/B switch)
+  int rowcol_quad_max = 1 << 18;        // ... up to this many buckets ("rowcol_quad_max")
+  int rowcol_lgq = 0;                   // "rowcol_lgq": log2 of the quads per row / column of k_rowcol_quad (2, 3, 4; 0 = by cost)
+  int rowcol_row = 1;                   // "rowcol_row": with tree_row, small bucket counts: k_rowcol_quad_row (one wave per row / column, the cross-quad levels on rows)
+  int tree_row = 1;                     // "tree_row": regime A's 1 + hb + lb items per window by blocks of waves with one limb per lane (k_small_tree_row); 0: k_small_tree_quad
+  int tree_shift = 2;                   // "tree_shift": k_small_tree_quad's block = 4 lanes per element >> this (0 .. 4; -1 = tree_half's 0 / 1).  Measured
+                                        // (profiles/r04_tree_ab.txt, tree + export at 2^16 / 2^18 / 2^20): 0: 111 / 112 / 119 us, 1: 90 / 112 / 121, 2: 79 / 100 / 110, 4: 78 / 161 / 177
+  int tree_half = 1;                    // k_small_tree_quad: 2 lanes per element (a quad takes two elements) instead of 4 (A/B switch)
+  int zero_copy = 1;                    // 1: export kernel + flag polling instead of a D2H copy + stream wait (A/B switch)
+  int host_split = 1;                   // host Horner tail on two threads (A/B switch)
+  int arm_helpers = 1;                  // "arm_helpers": the Horner's helper threads spin for their part while a small / mid-size call's result is polled (A/B switch)
+  int horner_threads = 4;               // host threads of the Horner tail: 1, 2 or 4 (A/B switch; host_split = 0 forces 1)
+  int horner_row = 1;                   // "horner_row": regime B's device Horner with one wave per MSM, one limb per lane (A/B switch; 0: one quad per MSM)
+  int batched_host_horner_max = 24;     // regime B calls with at most this many MSMs run their Horner on the host ("batched_host_horner_max")
+  int small_msm = 1;                    // "small_msm": MSMs of <= SM_MAX_N = 2048 terms as ONE launch (k_msm_small); 0 = the regime-A chain (A/B switch)
+  int small_row_tail = 1;               // "small_row_tail": k_msm_small's items / combine / export one limb per lane, one wave per item (A/B switch)
+  int glv = 0;                          // "glv": the caller vouches that every point of its MSM calls lies in the prime-order subgroup, and the engine may run
+                                        // the endomorphism split (csrc/glv.h): 1 = where it pays (the single-launch kernel up to 1 024 terms, regime A up to
+                                        // glv_max_n terms), 2 = wherever it can (A/B runs).  WRONG results outside G1: default 0.
+  int glv_max_n = 1 << 14;              // "glv_max_n": largest regime-A call glv = 1 splits (profiles/r05_glv_ab.txt: slower from 2^15 terms up)
+  int auto_plan = 1;                    // window_c = 0 picks balanced window plans for mid-size inputs (A/B switch)
+  // "split" (A/B switch, OFF): one large call as TWO launch chains on two streams -- the high half of the windows on this context, the
+  // low half on `child` (own scratch buffers, stream and export flag; shared prepared points) -- meant to run the low half's sort under
+  // the high half's k_accumulate and the high half's reduction tail under the low half's.  MEASURED A LOSS (profiles/r04_split_ab.txt:
+  // 2^20 3.25 ms against 2.95, 2^18 1.54 against 1.22; only 2^16 gains 3 %): the resident blocks of k_accumulate hold every SIMD's
+  // registers for their whole ~1 ms life, so the other stream's kernels are dispatched only when it drains -- the two chains run one
+  // after the other, and each pays its own launch chain and the shorter chunks of half the entries.
+  int split = 0;
+  size_t split_min_n = (size_t)1 << 17; // "split_min_log2n": ... from this many terms on
+  int batched_split = 0;                // "batched_split": regime B as two launch chains of half the MSMs each, the second half's k_accumulate behind the first's
+                                        // (so that the first half's tail runs under it).  Measured SLOWER (1 024 x 627: 5.2-5.3 -> 5.6-5.8 ms, with the
+                                        // endomorphism split 4.72 -> 4.76-4.85, profiles/r05_regime_b_split.txt): the tails are not idle time.  A/B switch, off.
+  int batched_split_min_m = 256;        // "batched_split_min_m": ... from this many MSMs on
+  int blocking_sync = 0;                // waits sleep on an interrupt (Ctx::sync_ev) instead of spinning a core
+  int profile = 1;                      // 0: no hipEvents; 1: around k_accumulate only; 2: around every phase (read_phase_events)
+};
+
+// cg1_ctx_set_param's MSM names with their ranges, on a bare switch set (cg1_msm_call_describe applies its inputs through it too).
+enum { SW_SET = 0, SW_RANGE = 1, SW_UNKNOWN = 2 };
+static int set_msm_switch(MsmSwitches& sw, const char* name, int value) {
+  struct Named { const char* name; int MsmSwitches::* field; int lo, hi; };        // lo > hi: any value, stored as 0 / 1
+  static const Named table[] = {
+    {"chunk_rule", &MsmSwitches::chunk_rule, 1, 0}, {"stage_sort", &MsmSwitches::stage_sort, 1, 0}, {"quad", &MsmSwitches::quad, 1, 0},
+    {"reduce_2d", &MsmSwitches::reduce_2d, 1, 0}, {"partition_sort", &MsmSwitches::use_partition_sort, 1, 0}, {"big_bins", &MsmSwitches::big_bins, 1, 0},
+    {"scan_one", &MsmSwitches::scan_one, 1, 0}, {"fold_pass", &MsmSwitches::fold_pass, 1, 0}, {"fold_quad", &MsmSwitches::fold_quad, 1, 0},
+    {"rowcol_quad", &MsmSwitches::rowcol_quad, 1, 0}, {"rowcol_quad_max", &MsmSwitches::rowcol_quad_max, 0, INT32_MAX}, {"rowcol_row", &MsmSwitches::rowcol_row, 1, 0},
+    {"tree_row", &MsmSwitches::tree_row, 1, 0}, {"tree_shift", &MsmSwitches::tree_shift, -1, 4}, {"tree_half", &MsmSwitches::tree_half, 1, 0},
+    {"zero_copy", &MsmSwitches::zero_copy, 1, 0}, {"host_split", &MsmSwitches::host_split, 1, 0}, {"arm_helpers", &MsmSwitches::arm_helpers, 1, 0},
+    {"horner_row", &MsmSwitches::horner_row, 1, 0}, {"batched_host_horner_max", &MsmSwitches::batched_host_horner_max, 0, INT32_MAX},
+    {"small_msm", &MsmSwitches::small_msm, 1, 0}, {"small_row_tail", &MsmSwitches::small_row_tail, 1, 0}, {"glv", &MsmSwitches::glv, 0, 2},
+    {"glv_max_n", &MsmSwitches::glv_max_n, 0, INT32_MAX}, {"auto_plan", &MsmSwitches::auto_plan, 1, 0}, {"split", &MsmSwitches::split, 1, 0},
+    {"batched_split", &MsmSwitches::batched_split, 1, 0}, {"batched_split_min_m", &MsmSwitches::batched_split_min_m, 2, INT32_MAX},
+    {"blocking_sync", &MsmSwitches::blocking_sync, 1, 0}, {"profile", &MsmSwitches::profile, 0, 2},
+  };
+  for (const Named& t : table) {
+    if (strcmp(name, t.name)) continue;
+    if (t.lo <= t.hi && (value < t.lo || value > t.hi)) return SW_RANGE;
+    sw.*t.field = t.lo <= t.hi ? value : (value ? 1 : 0);
+    return SW_SET;
+  }
+  // the names whose values are not a plain interval, or not an int field
+  const auto one_of = [value](std::initializer_list<int> ok) { return std::find(ok.begin(), ok.end(), value) != ok.end(); };
+  if (!strcmp(name, "chunk_len")) { if (value < 1 || value > 65536) return SW_RANGE; sw.L0 = (uint32_t)value; return SW_SET; }
+  if (!strcmp(name, "seg_m")) { if (!one_of({1, 2, 4, 8, 16})) return SW_RANGE; sw.seg_m = (uint32_t)value; return SW_SET; }
+  if (!strcmp(name, "horner_threads")) { if (!one_of({1, 2, 4})) return SW_RANGE; sw.horner_threads = value; return SW_SET; }
+  if (!strcmp(name, "rowcol_lgq")) { if (!one_of({0, 2, 3, 4})) return SW_RANGE; sw.rowcol_lgq = value; return SW_SET; }
+  if (!strcmp(name, "sort_sub_bits")) { if (!one_of({0, 4, 5, 6, 7, 8})) return SW_RANGE; sw.sort_sub_bits = value; return SW_SET; }
+  if (!strcmp(name, "split_min_log2n")) { if (value < 10 || value > 31) return SW_RANGE; sw.split_min_n = (size_t)1 << value; return SW_SET; }
+  return SW_UNKNOWN;
+}
+
+struct Ctx : MsmSwitches {
   int device = 0;
   Helper helper[3];                     // the host Horner tail runs on up to four threads (this one + three helpers)
   hipStream_t stream = nullptr;
@@ -85,7 +172,6 @@ struct Ctx {
   hipStream_t side_stream = nullptr;    // small latency-bound kernels that run BESIDE the compute stream (cg1_subgroup_flags_enqueue)
   hipEvent_t side_ev = nullptr;
   hipEvent_t sync_ev = nullptr;         // blocking-sync event: waits sleep on an interrupt instead of spinning a core
-  int blocking_sync = 0;
   char err[256] = {0};
   int alloc_fail_at = 0;                // "alloc_fail_at": the k-th allocation grow_bufs attempts from now on fails as out of memory (a test's hook; 0 = off)
   // capacity
@@ -103,16 +189,6 @@ struct Ctx {
   size_t cap_digits = 0, cap_part = 0, cap_blockcnt = 0;
   uint32_t *d_slice_base = nullptr, *d_slicehist = nullptr, *d_subbase = nullptr; uint8_t* d_bigflag = nullptr;
   size_t cap_bigflag = 0, cap_slices = 0;
-  int big_bins = 1;                     // giant bins of skewed scalars sorted by many blocks (A/B switch)
-  int use_partition_sort = 1;
-  int stage_sort = 1;                   // LDS-staged, line-coalesced writes in k_part_scatter / k_bin_sort (A/B switch)
-  int host_split = 1;                   // host Horner tail on two threads (A/B switch)
-  int rowcol_quad = 1;                  // k_rowcol_quad for small bucket counts (A/B switch)
-  int rowcol_lgq = 0;                   // "rowcol_lgq": log2 of the quads per row / column of k_rowcol_quad (2, 3, 4; 0 = by cost)
-  int rowcol_quad_max = 1 << 18;        // ... up to this many buckets ("rowcol_quad_max")
-  int tree_shift = 2;                   // "tree_shift": k_small_tree_quad's block = 4 lanes per element >> this (0 .. 4; -1 = tree_half's 0 / 1).  Measured
-                                        // (profiles/r04_tree_ab.txt, tree + export at 2^16 / 2^18 / 2^20): 0: 111 / 112 / 119 us, 1: 90 / 112 / 121, 2: 79 / 100 / 110, 4: 78 / 161 / 177
-  int tree_half = 1;                    // k_small_tree_quad: 2 lanes per element (a quad takes two elements) instead of 4 (A/B switch)
   int merlin_sync = 1;                  // k_merlin_batch_sync (lanes permute together) instead of k_merlin_batch (A/B switch)
   uint32_t merlin_clk[2] = {0, 0};
   int fe_timed = 0;                     // "fe_timed": the block-program kernel reads the shader clock around the parts of a pass (cg1_shuffle_fe_last_split)
@@ -142,14 +218,9 @@ struct Ctx {
   void* d_merlin_rows = nullptr; size_t merlin_rows_cap = 0;      // the rows of the last such call (kept: 134 KB per shuffle-shaped transcript)
   int merlin_lanes = 64;                // transcripts per wave of k_merlin_batch_sync ("merlin_lanes": 1 .. 64)
   uint32_t merlin_passes = 0;           // of the last cg1_merlin_batch_device call: Keccak passes of the slowest wave
-  int sort_sub_bits = 0;                // partition sort: sub-bucket bits a k_bin_sort workgroup sorts by ("sort_sub_bits": 4 .. 8; 0 = 7 up to 2^16 terms, else 8)
   int batch_mul_host_max = -1;          // cg1_batch_mul_add (host pointers): outputs up to which the host's pool does the work ("batch_mul_host_max"; -1 = 16 per pool thread, 0 = never)
   int last_batch_mul_on_host = 0;
   int batch_mul_quad_max = 8192;        // k_batch_mul_quad up to this many outputs ("batch_mul_quad_max"; 0 = always one lane per output)
-  int scan_one = 1;                     // the sort's two scans as one single-block launch each when they are small (A/B switch)
-  int fold_pass = 1;                    // k_bucket_fold in front of k_rowcol / k_seg_reduce; 0 leaves multi-chunk buckets to their bucket_sum loops
-                                        // (measured WORSE: 372 instead of 235 us at 2^16 -- divergent trip counts inside the row / column lanes)
-  int auto_plan = 1;                    // window_c = 0 picks balanced window plans for mid-size inputs (A/B switch)
   struct Pending {                      // what msm_finish needs from msm_enqueue
     bool active = false;
     int c = 0, rank = 0, world = 1, nlw = 0, nbits = 0;
@@ -163,47 +234,22 @@ struct Ctx {
     const PointWords* hout = nullptr;   // where the exported items land (ctx->h_out, or h_small_out for k_msm_small)
     std::chrono::steady_clock::time_point h0, h1;
   } pend;
-  // "split" (A/B switch, OFF): one large call as TWO launch chains on two streams -- the high half of the windows on this context, the
-  // low half on `child` (own scratch buffers, stream and export flag; shared prepared points) -- meant to run the low half's sort under
-  // the high half's k_accumulate and the high half's reduction tail under the low half's.  MEASURED A LOSS (profiles/r04_split_ab.txt:
-  // 2^20 3.25 ms against 2.95, 2^18 1.54 against 1.22; only 2^16 gains 3 %): the resident blocks of k_accumulate hold every SIMD's
-  // registers for their whole ~1 ms life, so the other stream's kernels are dispatched only when it drains -- the two chains run one
-  // after the other, and each pays its own launch chain and the shorter chunks of half the entries.
-  int split = 0;
-  size_t split_min_n = (size_t)1 << 17;
   cg1_ctx* child = nullptr;
   hipEvent_t ev_prep = nullptr, ev_acc = nullptr;
   bool pend_split = false;
   int last_acc_launches = 0;            // k_accumulate launches of the last MSM call: 2 (split), 1, or 0 (k_msm_small)
-  int small_row_tail = 1;               // "small_row_tail": k_msm_small's items / combine / export one limb per lane, one wave per item (A/B switch)
-  int small_msm = 1;                    // "small_msm": MSMs of <= SM_MAX_N = 2048 terms as ONE launch (k_msm_small); 0 = the regime-A chain (A/B switch)
   PointSum* d_small_partial = nullptr; size_t cap_small_partial = 0;
   uint32_t* d_small_ctr = nullptr;
   PreparedPoint* d_small_pts = nullptr; uint8_t* d_small_flags = nullptr; size_t cap_small_pts = 0;      // k_prepare_blobs<true> output for un-normalised blob input
   PointWords* h_small_out = nullptr; PointWords* h_small_out_dev = nullptr;     // pinned + mapped: 64 x 9 window items + the status record
-  int quad = 1;                         // quad-lane EC ops in the latency-bound kernels (A/B switch)
-  int reduce_2d = 1;                    // 1: k_rowcol + k_small_tree; 0: k_seg_reduce + k_bit_tree (A/B switch)
   uint32_t* d_heavy = nullptr; size_t cap_heavy = 0;         // [0] count, then heavy bucket ids
   uint8_t* d_combined = nullptr; size_t cap_combined = 0;
   uint32_t* d_boffs = nullptr; size_t cap_boffs = 0;          // regime B: MSM offsets, group sums, per-MSM results
   PointSum* d_gsum = nullptr; size_t cap_gsum = 0;
   PointWords* d_bout = nullptr; PointWords* h_bout = nullptr; size_t cap_bout = 0;
   PointWords* d_gout = nullptr; PointWords* h_gout = nullptr; size_t cap_gout = 0;       // regime B, few MSMs: window sums exported for the host Horner
-  int glv = 0;                          // "glv": the caller vouches that every point of its MSM calls lies in the prime-order subgroup, and the engine may run
-                                        // the endomorphism split (csrc/glv.h): 1 = where it pays (the single-launch kernel up to 1 024 terms, regime A up to
-                                        // glv_max_n terms), 2 = wherever it can (A/B runs).  WRONG results outside G1: default 0.
-  int glv_max_n = 1 << 14;              // "glv_max_n": largest regime-A call glv = 1 splits (profiles/r05_glv_ab.txt: slower from 2^15 terms up)
   int lincomb_zero_copy = 1;            // "lincomb_zero_copy": small GPU shares of cg1_lincomb_batch are read from mapped host memory (no staged copy); A/B switch
-  int fold_quad = 1;                    // "fold_quad": small bucket counts: k_bucket_fold_quad (1) or the one-lane-per-bucket k_bucket_fold (0); A/B switch
-  int rowcol_row = 1;                   // "rowcol_row": with tree_row, small bucket counts: k_rowcol_quad_row (one wave per row / column, the cross-quad levels on rows)
-  int tree_row = 1;                     // "tree_row": regime A's 1 + hb + lb items per window by blocks of waves with one limb per lane (k_small_tree_row); 0: k_small_tree_quad
-  int horner_row = 1;                   // "horner_row": regime B's device Horner with one wave per MSM, one limb per lane (A/B switch; 0: one quad per MSM)
   int batch_mul_row = 1;                // "batch_mul_row": deferred map / fold batches of 96 .. 4096 results on k_batch_mul_row (A/B switch; 0: pool / k_batch_mul)
-  int batched_split = 0;                // "batched_split": regime B as two launch chains of half the MSMs each, the second half's k_accumulate behind the first's
-                                        // (so that the first half's tail runs under it).  Measured SLOWER (1 024 x 627: 5.2-5.3 -> 5.6-5.8 ms, with the
-                                        // endomorphism split 4.72 -> 4.76-4.85, profiles/r05_regime_b_split.txt): the tails are not idle time.  A/B switch, off.
-  int batched_split_min_m = 256;        // "batched_split_min_m": ... from this many MSMs on
-  int batched_host_horner_max = 24;     // regime B calls with at most this many MSMs run their Horner on the host ("batched_host_horner_max")
   PointSum *d_sums = nullptr, *d_segrun = nullptr, *d_segtot = nullptr;
   PointWords* d_out = nullptr;
   PointWords* h_out = nullptr;          // pinned, and mapped into the device: k_export_host writes the window sums straight into it
@@ -211,9 +257,6 @@ struct Ctx {
   uint32_t* h_flag = nullptr;           // pinned + mapped: k_export_host stores the call's sequence number here when h_out is complete
   uint32_t* h_flag_dev = nullptr;
   uint32_t seq = 0;
-  int zero_copy = 1;                    // 1: export kernel + flag polling instead of a D2H copy + stream wait (A/B switch)
-  int arm_helpers = 1;                  // "arm_helpers": the Horner's helper threads spin for their part while a small / mid-size call's result is polled (A/B switch)
-  int horner_threads = 4;               // host threads of the Horner tail: 1, 2 or 4 (A/B switch; host_split = 0 forces 1)
   // staging for host-pointer entry points
   void* d_stage_pts = nullptr; void* d_stage_sc = nullptr; size_t cap_stage_pts = 0, cap_stage_sc = 0;      // bytes
   uint8_t* h_lin = nullptr; uint8_t* h_lin_dev = nullptr; size_t cap_h_lin = 0;   // page-locked gather buffer of cg1_lincomb_batch (terms' points | scalars)
@@ -222,19 +265,16 @@ struct Ctx {
   float phase_ms[CG1_NPHASE] = {0};
   float host_tail_ms = 0;
   float host_ms[4] = {0, 0, 0, 0};      // enqueue, wait-for-GPU, event readout, Horner tail
-  int profile = 1;                      // 0: no hipEvents; 1: around k_accumulate only; 2: around every phase (read_phase_events)
   uint32_t last_chunks = 0, last_entries = 0;   // of the last MSM call: non-zero digits sorted into buckets; chunks k_accumulate ran
   uint32_t last_tail = 0;               // of the last MSM call: which reduction-tail kernels were launched (TAIL_* below; for the tests, cg1_get_last_tail)
   hipEvent_t tm_ev[2] = {nullptr, nullptr};     // cg1_timer_begin / cg1_timer_end
   int last_c = 0, pend_c = 0;
-  int chunk_rule = 1;                   // "chunk_rule": whole-bucket chunks at 2^17 .. 2^19 terms (A/B switch)
-  uint32_t L0 = 8;                      // MINIMUM chunk length; the per-call length grows with the entry count
-  uint32_t seg_m = 4;
 };
 
-// Ctx::last_tail: which leaves of the reduction tail the last call launched, as bit fields.  Plain host stores beside the launches
-// (msm_enqueue, msm_finish, msm_enqueue_small, batched_chain_enqueue); nothing reads it but cg1_get_last_tail, which exists for the tests
-// (tests/msm_tail_cases.py restates the decision and compares).
+// Ctx::last_tail: which leaves of the reduction tail the last call launched, as bit fields.  One word per call, built by tail_word
+// (msm_plan.h) from the enums of the call's plan -- the very ones the launch code switches on -- and completed by msm_finish with the host
+// Horner's thread count; nothing reads it but cg1_get_last_tail, which exists for the tests (tests/msm_tail_cases.py restates the
+// decision and compares; cg1_msm_call_describe gives the same word without a launch).
 //   fold    bits 0-1    0 none launched, 1 k_bucket_fold_quad, 2 k_bucket_fold
 //   rowcol  bits 2-4    1 k_rowcol_quad_row, 2 k_rowcol_quad, 3 k_rowcol, 4 k_seg_reduce (regime A: + k_bit_tree, k_bit_tree_final; regime B: + k_group_reduce)
 //   lgq     bits 5-7    k_rowcol_quad's lgq

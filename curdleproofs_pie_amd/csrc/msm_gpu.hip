@@ -12,7 +12,9 @@
 //                      two-level LDS partition sort by (window, bucket); no global atomics     [kernels_sort.h]
 //                      (k_hist/k_scatter: global-atomic counting sort, only for n > 2^23)
 //   k_scan1/2/3, k_chunk_desc, k_len_scan, k_order
-//                      bucket offsets; chunks of <= L entries (L = max(8, entries/2^18), <= 4096 chunks per bucket);
+//                      bucket offsets; chunks of <= L entries, <= 4096 chunks per bucket (L: "chunk_len", 8, doubled while
+//                      entries / 2^18 exceeds it; without shards at least 10 from 2^20 entries and, from 2^21 to 2^24 entries
+//                      over more than 2^18 buckets, a whole bucket -- mean load + 8 sigma + 1, below 2^22 entries 20 at most);
 //                      chunks ordered by descending length so a wave's lanes finish together
 //   k_accumulate  ***  the dominant kernel: one lane per chunk, XYZZ mixed adds over gathered points [kernels_accumulate.h]
 //   k_heavy_combine, k_bucket_fold
@@ -87,7 +89,8 @@ int pick_window(size_t n);
 #include "kernels_whisk_shuffle.h" // k_whisk_permute_mul: the post-shuffle trackers of a Whisk shuffle, k vec_R | k vec_S through the permutation
 #include "kernels_chain_prove.h"   // k_chain_lineage_mul: every pre and post tracker of a proved chain from (origin slot, composite scalar), one launch
 #include "host_context.h"          // Ctx: streams, helper threads, scratch buffers
-#include "host_chains.h"           // planner + launch chains: regime A, k_msm_small, regime B
+#include "msm_plan.h"              // the pure call planner: who serves a call, every number its chain derives, the tail word
+#include "host_chains.h"           // the launch chains as stages over a plan: regime A, k_msm_small, regime B
 #include "capi_core_msm.h"         // cg1_* : host operators, context, memory, parameters, MSM entry points
 #include "capi_vec_batched.h"      // resident vectors, batched normalisation, regime B
 #include "capi_lincomb.h"          // deferred G1Point evaluation: cg1_lincomb_batch, cg1_batch_subgroup

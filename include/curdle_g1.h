@@ -186,6 +186,27 @@ int cg1_get_last_launches(const cg1_ctx* ctx);
  * the endomorphism split instead of 256): offset and width of every window, low to high.  Returns the number of windows (<= capacity) or -1.
  * No GPU involved: the CPU tests check that every plan tiles the bit positions from 0 without a gap. */
 int cg1_plan_describe(int window_c, int glv, int* out_offsets, int* out_widths, int capacity);
+/* What an MSM call would launch, from the engine's own planner (csrc/msm_plan.h).  No GPU and no context involved: the CPU tests compare it
+ * with their models, the GPU tests with what the call then reports.
+ * In:  switch_names / switch_values: n_switches cg1_ctx_set_param settings applied, in order, to a default switch set (MSM switches only);
+ *      n, window_c, shard_rank, shard_world: as for cg1_msm_device; source_kind: 0 affine96, 1 point blobs, 2 a resident vector;
+ *      n_msms: 0 = one MSM (cg1_msm_device and its kin), else a cg1_msm_batched_device call of n_msms MSMs over n terms in all, the largest
+ *      of max_terms (window_c as for that call; the shard is ignored; neither half of the MSMs is taken to be empty);
+ *      e_top: the highest exponent of an exported point that is not the identity (it sizes the host Horner's thread count).
+ * Out (each may be NULL): *out_engine CG1_ENGINE_*; *out_c the plan's width as cg1_get_timings reports it (negative: balanced; 0: nothing
+ *      runs); *out_glv whether the endomorphism split is on; *out_chunk_len the call's chunk length (0: no k_accumulate);
+ *      *out_tail the word cg1_get_last_tail returns on the context after the call.  The two-chain forms describe the context's own chain:
+ *      the upper windows, or the first n_msms / 2 MSMs taken as n / 2 terms.
+ * Returns CG1_ERR_ARG where cg1_ctx_set_param would (unknown name, value out of range) or the call would (n, shard, width, batch size). */
+#define CG1_ENGINE_NONE         0   /* nothing to launch: no terms */
+#define CG1_ENGINE_SMALL        1   /* one k_msm_small launch */
+#define CG1_ENGINE_CHAIN_A      2   /* the regime-A launch chain */
+#define CG1_ENGINE_TWO_CHAINS_A 3   /* ... as two chains ("split") */
+#define CG1_ENGINE_CHAIN_B      4   /* the regime-B launch chain */
+#define CG1_ENGINE_TWO_CHAINS_B 5   /* ... as two chains ("batched_split") */
+int cg1_msm_call_describe(const char* const* switch_names, const int* switch_values, int n_switches, size_t n, int window_c, int shard_rank,
+                          int shard_world, int source_kind, size_t n_msms, size_t max_terms, int e_top,
+                          int* out_engine, int* out_c, int* out_glv, uint32_t* out_chunk_len, uint32_t* out_tail);
 /* hipEvent stopwatch on the context's compute stream: device time of everything enqueued between begin and end */
 int cg1_timer_begin(cg1_ctx* ctx);
 int cg1_timer_end(cg1_ctx* ctx, float* ms);

@@ -1,5 +1,5 @@
 """An exact integer model of everything an MSM call does BEFORE k_accumulate -- the window plan (make_plan), the signed-digit recoding
-(DigitIter::next), the endomorphism split (glv.h), the window shards, the bucket sort and the chunk plan (chunk_len / chunk_count) -- and
+(DigitIter::next), the endomorphism split (glv.h), the window shards, the bucket sort and the chunk plan (call_chunk_len / chunk_count) -- and
 the directed scalar families that drive every rare branch of it, shared by tests/test_msm_digits.py (host) and
 tests/test_msm_digits_gpu.py (device).  Plain Python on integers, written from the comments of the C++ and not from its code; the only
 product code here is split_native(), the ctypes wrapper of cg1_glv_split the tests compare split() with.
@@ -15,6 +15,7 @@ Which rare events a family reaches is ASSERTED, not hoped for (family_events / r
 some window, the most negative digit, the full carry chain or the carry-only top digit fails when it is built."""
 import ctypes
 import functools
+import math
 
 from oracle import bls12_381 as O
 
@@ -113,17 +114,32 @@ def chunk_count(cnt, L0):
     return -(-cnt // L)
 
 
-def call_chunk_len(L0, rows, nlw, world=1, chunk_rule=True):
-    """The chunk length a regime-A call of `rows` digit rows (2n with the split) over nlw owned windows runs with (the comment above
-    `uint32_t L0` in msm_enqueue): the parameter, doubled while rows * nlw / 2^18 exceeds it, and at least 10 between 2^20 and 2^21
-    rows x windows when "chunk_rule" is on and the call is not sharded.  The tests stay below 2^21, where the third rule starts."""
+def call_chunk_len(L0, rows, nlw, world=1, chunk_rule=True, cmax=None, rowcol_quad_max=1 << 18):
+    """The chunk length a regime-A call of `rows` digit rows (2n with the split) over nlw owned windows runs with (the comments in
+    plan_regime_a and above grown_chunk_len, csrc/msm_plan.h).  Three rules:
+      1. the parameter, doubled while rows * nlw / 2^18 exceeds it (up to 65536);
+    and, when "chunk_rule" is on and the call is not sharded,
+      2. at least 10 between 2^20 and 2^21 rows x windows;
+      3. between 2^21 and 2^24 rows x windows, where the lane-per-bucket tail runs (more buckets, nlw 2^(cmax - 1), than "rowcol_quad_max"):
+         at least a WHOLE bucket -- its mean load rows / 2^(cmax - 1) plus eight standard deviations of a Poisson spread (the root of
+         the mean) plus one, cut to an integer -- but below 2^22 rows x windows 20 at most.
+    cmax (the plan's widest window) is needed from 2^21 rows x windows on, where the third rule starts."""
     e = rows * nlw
-    assert e < 1 << 21
     L = L0
     while L < 65536 and (e >> 18) > L:
         L <<= 1
-    if chunk_rule and world == 1 and e >= 1 << 20 and L < 10:
+    if not chunk_rule or world != 1:
+        return L
+    if 1 << 20 <= e < 1 << 21 and L < 10:
         L = 10
+    if 1 << 21 <= e < 1 << 24:
+        assert cmax is not None, "the whole-bucket rule needs the plan's width"
+        if (nlw << (cmax - 1)) > rowcol_quad_max:
+            mean = rows / (1 << (cmax - 1))
+            want = int(mean + 8.0 * math.sqrt(mean) + 1.0)
+            if e < 1 << 22:
+                want = min(want, 20)
+            L = max(L, want)
     return L
 
 

@@ -140,6 +140,43 @@ def test_chunk_count_edges():
     assert M.call_chunk_len(1, 1 << 15, 32, chunk_rule=False) == 4 and M.call_chunk_len(1, 1 << 15, 32, world=2) == 4      # 2^20 rows x windows = 4 x 2^18
 
 
+def _described_chunk_len(L0, rows, c, world=1, chunk_rule=1):
+    d = N.msm_call_describe({"small_msm": 0, "chunk_len": L0, "chunk_rule": chunk_rule}, rows, c, 0, world)
+    assert d["engine"] == "regime A" and d["c"] == c and not d["glv"]
+    return d["chunk_len"]
+
+
+@pytest.mark.parametrize("L0", [1, 8, 64])
+@pytest.mark.parametrize("world", [1, 2])
+@pytest.mark.parametrize("chunk_rule", [0, 1])
+def test_call_chunk_len_is_the_planners(L0, world, chunk_rule):
+    """The planner's chunk length (cg1_msm_call_describe) == the model's, one row below, at and one row above every point where rows x
+    windows crosses 2^18 L0 (the first doubling), 2^20 and 2^21 (the rules' edges), whole plan and rank 0 of 2 of the 16 windows of c = 16."""
+    nlw = 16 // world
+    for edge in ((1 << 18) * L0, 1 << 20, 1 << 21):
+        for rows in (edge // nlw - 1, edge // nlw, edge // nlw + 1):
+            want = M.call_chunk_len(L0, rows, nlw, world, bool(chunk_rule), cmax=16)
+            assert _described_chunk_len(L0, rows, 16, world, chunk_rule) == want, (L0, world, chunk_rule, rows, want)
+
+
+def test_whole_bucket_chunks_under_the_automatic_plan():
+    """The third rule -- a chunk holds a whole bucket between 2^21 and 2^24 rows x windows -- at 2^17, 2^18 and 2^19 rows under the plan
+    window_c = 0 picks (-15, 16, 16), on both sides of 2^22 rows x windows, where the cap of 20 ends, and of its two outer edges.  The
+    lengths are written out: mean load 8 -> 8 + 8 sqrt 8 + 1 = 31 (capped: 20), mean load 16 -> 49."""
+    for rows, c, nwin, want in ((1 << 17, -15, 18, 20), (1 << 18, 16, 16, 31), (1 << 19, 16, 16, 49)):
+        d = N.msm_call_describe({}, rows, 0)
+        assert (d["engine"], d["c"], d["chunk_len"]) == ("regime A", c, want), (rows, d)
+        assert M.call_chunk_len(8, rows, nwin, cmax=abs(c)) == want, rows
+    assert M.call_chunk_len(8, (1 << 18) - 1, 16, cmax=16) == 20 and M.call_chunk_len(8, 1 << 18, 16, cmax=16) == 31      # 2^22 rows x windows
+    for rows in ((1 << 17) - 1, 1 << 17, (1 << 18) - 1, 1 << 18, (1 << 20) - 1, 1 << 20):       # 2^21, 2^22 and 2^24 rows x windows at c = 16
+        for L0 in (1, 8, 64):
+            assert _described_chunk_len(L0, rows, 16) == M.call_chunk_len(L0, rows, 16, cmax=16), (rows, L0)
+    # sharded, switched off, or with the quad tail taking every bucket ("rowcol_quad_max"): the first rule alone
+    assert M.call_chunk_len(8, 1 << 18, 8, world=2, cmax=16) == M.call_chunk_len(8, 1 << 18, 16, chunk_rule=False, cmax=16) - 8 == 8
+    assert M.call_chunk_len(8, 1 << 18, 16, cmax=16, rowcol_quad_max=1 << 19) == 16
+    assert N.msm_call_describe({"rowcol_quad_max": 1 << 19}, 1 << 18, 16)["chunk_len"] == 16
+
+
 @pytest.mark.parametrize("c", [8, 16, -13])
 def test_bucket_load_cases_load_what_they_say(c):
     pl = M.plan(c)

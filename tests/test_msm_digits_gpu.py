@@ -103,6 +103,7 @@ def _check(ctx, c, scalars, coef, p96, L0, glv=False, rows=None, rank=0, world=1
     nrows = (2 if glv else 1) * len(scalars)
     L = M.call_chunk_len(L0, nrows, len(own), world)
     assert L == L0, (c, L0, L)
+    assert N.msm_call_describe({"small_msm": 0, "chunk_len": L0, "glv": 2 if glv else 0}, len(scalars), c, rank, world)["chunk_len"] == L      # the planner's own answer
     if rows is None:
         rows = [M.rows_of(s, pl, glv) for s in scalars]
     ident = [k == 0 for k in coef]

@@ -1,10 +1,12 @@
 """tests/msm_tail_cases.py checked on the host: the families have the properties that force doublings and cancellations in any correct
 reduction tail, their closed forms are what the oracle's compute_MSM gives, and the configuration list reaches every leaf of every choice
-the tail makes, with a call on each side of every threshold.  No GPU."""
+the tail makes, with a call on each side of every threshold; and the engine's own planner (cg1_msm_call_describe: which engine serves a
+call, its plan, its tail word) against these models and against expectations written out here.  No GPU."""
 import pytest
 
 import msm_digit_model as M
 import msm_tail_cases as T
+from curdleproofs_pie_amd import _native as N
 from oracle import bls12_381 as O
 
 R = T.R
@@ -152,3 +154,134 @@ def test_the_suspected_combination_is_in_the_list():
     assert any(p == T.SUSPECT for p, _ in T.configs(8))
     for x in T.chunk_cases(8):                                     # and the chunks family gives it buckets of 2 .. 16 chunks to lose
         assert any(2 <= M.chunk_count(cnt, 1) < T.HEAVY for _, cnt in x.buckets[x.w].values())
+
+
+# ------------------------------------------------------------------ the engine's planner (cg1_msm_call_describe) against the models
+REGIME_A = {"small_msm": 0, "chunk_len": 8}                        # what tests/test_msm_tail_gpu.py's context runs under
+
+
+def _described_tail(params, n, c, shard=None, e_top=0, **kw):
+    rank, world = (0, 1) if shard is None else (shard, len(M.plan(c)))
+    d = N.msm_call_describe(dict(T.DEFAULT_PARAMS, **params), n, c, rank, world, e_top=e_top, **kw)
+    return N.decode_tail(d["tail"])
+
+
+def test_the_planner_takes_every_regime_a_path_the_model_takes():
+    """Every configuration of the list (every leaf at every width, both sides of "rowcol_quad_max", the one-window shards, every legal
+    triple at the product widths): the planner's tail word, decoded, == tail_path."""
+    paths = _all_paths()
+    assert len(paths) > 700
+    for c, p, shard, want in paths:
+        assert _described_tail(dict(p, **REGIME_A), 1 << (abs(c) - 1), c, shard) == want, (c, p, shard)
+
+
+def test_the_planner_counts_the_host_horners_threads_as_the_model_does():
+    for c, w in T.HORNER_TOPS:
+        n, e = len(T.horner_thread_case(c, w)), M.plan(c)[w][0]
+        for p in T.HORNER_THREAD_PARAMS:
+            for v in ({}, {"reduce_2d": 0}, {"zero_copy": 0}):
+                q = dict(p, **v)
+                assert _described_tail(dict(q, **REGIME_A), n, c, e_top=e) == T.tail_path(c, len(M.plan(c)), n, q, e), (c, w, q)
+
+
+def test_the_planner_takes_every_regime_b_and_small_path_the_model_takes():
+    for M_ in T.BATCHED_M:
+        for c in (4, 7):
+            for p in T.batched_params(M_):
+                got = _described_tail(dict(p, **REGIME_A), 3 * M_, c, n_msms=M_, max_terms=4)
+                assert got == T.tail_path_batched(c, M_, p), (M_, c, p)
+    for rt in (0, 1):
+        p = {"small_row_tail": rt}
+        for e in (0, 95, 96, 111, 112, 254):
+            for ht in T.HORNER_THREAD_PARAMS:
+                q = dict(p, **ht)
+                assert _described_tail(q, 627, 7, e_top=e) == T.tail_path_small(1, q, e), (q, e)                      # cg1_msm_device
+                assert _described_tail(q, 627, 7, e_top=e, n_msms=1, max_terms=627) == T.tail_path_small(1, q, e)     # one MSM, batched
+        for M_ in (4, 5, 64):
+            assert _described_tail(p, 3 * M_, 7, n_msms=M_, max_terms=4, e_top=200) == T.tail_path_small(M_, p), (M_, rt)
+
+
+def _route(switches, n, c=0, rank=0, world=1, **kw):
+    d = N.msm_call_describe(switches, n, c, rank, world, **kw)
+    return None if d is None else (d["engine"], d["c"], d["glv"])
+
+
+def test_routing_on_each_side_of_every_threshold():
+    """Who serves a call, the plan's width and whether the endomorphism split is on: written out, not computed."""
+    A, A2, B, B2, SMALL = "regime A", "regime A, two chains", "regime B", "regime B, two chains", "k_msm_small"
+    assert _route({}, 0) == (None, 0, False) and _route({}, 1) == (SMALL, 4, False)
+    # SM_MAX_N = 2048 terms: 32 windows x 8 slices is one round of workgroups
+    assert _route({}, 2048) == (SMALL, 8, False) and _route({}, 2049) == (A, 8, False)
+    assert _route({"small_msm": 0}, 2048) == (A, 8, False) and _route({}, 2048, world=2) == (A, 8, False)
+    assert _route({}, 1536, c=7) == (SMALL, 7, False) and _route({}, 1537, c=7) == (A, 7, False)      # 37 windows x 6 slices = 222 workgroups, x 7 = 259: more than one round of 256
+    assert _route({}, 1536) == (SMALL, 7, False) and _route({}, 1537) == (SMALL, 8, False)
+    assert _route({}, 627, c=5) == (A, 5, False) and _route({}, 627, c=10) == (A, 10, False) and _route({}, 627, c=9) == (SMALL, 9, False)
+    # "glv" = 1: the single launch over 2n entries up to 1024 terms, regime A's split up to "glv_max_n" = 2^14 terms
+    G = {"glv": 1}
+    assert _route(G, 1024) == (SMALL, 8, True) and _route(G, 1025) == (SMALL, 7, False)
+    assert _route(G, 2049) == (A, 8, True)
+    assert _route(G, 1 << 14) == (A, -13, True) and _route(G, (1 << 14) + 1) == (A, -13, False)
+    assert _route(G, 1 << 14, source_kind=2) == (A, -12, False)       # a resident vector holds n records: no split
+    assert _route(dict(G, partition_sort=0), 1 << 14) == (A, -12, False)
+    assert _route({"glv": 2}, 1 << 22) == (A, 16, True) and _route({"glv": 2}, (1 << 22) + 1) == (A, 16, False)      # 2n <= 2^23
+    assert _route(dict(G, glv_max_n=1 << 15), 1 << 15) == (A, -13, True) and _route(dict(G, glv_max_n=1 << 15), (1 << 15) + 1) == (A, -13, False)
+    # the automatic plan
+    for n, c in ((128, 4), (129, 8), (8192, 8), (8193, -12), (1 << 14, -12), ((1 << 14) + 1, -13), (3 << 15, -13), ((3 << 15) + 1, -15),
+                 (3 << 16, -15), ((3 << 16) + 1, 16), (1 << 20, 16)):
+        assert _route({"small_msm": 0}, n) == (A, c, False), n
+    assert _route({"auto_plan": 0}, 1 << 14) == (A, 16, False) and _route({"auto_plan": 0}, 8192) == (A, 8, False)
+    # "split": from "split_min_log2n" terms on, where the rank owns two windows at least
+    S = {"split": 1}
+    assert _route(S, (1 << 17) - 1, c=16) == (A, 16, False) and _route(S, 1 << 17, c=16) == (A2, 16, False)
+    assert _route(S, 1 << 17, c=16, rank=0, world=16) == (A, 16, False) and _route(S, 1 << 17, c=16, rank=0, world=8) == (A2, 16, False)
+    assert _route(S, 1 << 17, c=16, rank=15, world=15) is None and _route(S, 1 << 17, c=16, rank=14, world=15) == (A, 16, False)
+    assert _route(dict(S, split_min_log2n=10), 1023, c=16) == (A, 16, False) and _route(dict(S, split_min_log2n=10), 1024, c=16, world=2) == (A2, 16, False)
+    # regime B: "batched_split_min_m"
+    b = lambda sw, M_, c=0, per=4: _route(sw, per * M_, c, n_msms=M_, max_terms=per)
+    assert b({"batched_split": 1}, 255, 7) == (B, 7, False) and b({"batched_split": 1}, 256, 7) == (B2, 7, False) and b({}, 256, 7) == (B, 7, False)
+    assert b({"batched_split": 1, "batched_split_min_m": 2}, 2, 7, per=4096) == (B2, 7, False)
+    assert b({"glv": 1}, 256, 7) == (B, 7, True)
+    # one k_msm_small launch: SM_MAX_MSMS = 64 MSMs, SM_MAX_GROUPS = 2560 workgroups (windows x slices x MSMs), SM_MAX_N terms each
+    assert b({}, 64, 7) == (SMALL, 7, False) and b({}, 65, 7) == (B, 7, False)
+    assert b({}, 40, 4) == (SMALL, 4, False) and b({}, 41, 4) == (B, 4, False)                          # 64 windows: 2560 / 2624
+    assert b({}, 34, 7, per=257) == (SMALL, 7, False) and b({}, 35, 7, per=256) == (SMALL, 7, False)    # 37 windows x 2 slices x 34 = 2516; x 35 = 2590
+    assert b({}, 35, 7, per=257) == (B, 7, False) and b({}, 1, 8, per=2048) == (SMALL, 8, False) and b({}, 1, 8, per=2049) == (B, 8, False)
+    assert b({"small_msm": 0}, 4, 7) == (B, 7, False) and b({}, 4, 5) == (B, 5, False) and b({}, 0) == (None, 0, False)
+    # the refusals
+    for c in (3, 17, -3, -17):
+        assert _route({}, 2049, c) is None and _route({}, 5, c) is None, c
+    assert _route({}, 2049, 4) == (A, 4, False) and _route({}, 2049, -16) == (A, -16, False)
+    assert b({}, 100, 10) is None and b({}, 100, 3) is None and b({}, 100, 9) == (B, 9, False)
+    assert _route({}, 1 << 31) is None and _route({"small_msm": 0}, (1 << 31) - 1, 16) == (A, 16, False)
+    assert b({}, 65536) is None and _route({}, 1 << 31, n_msms=4, max_terms=1 << 29) is None
+    for rank, world in ((1, 1), (2, 2), (-1, 1), (0, 0), (0, 256)):
+        assert _route({}, 2049, 8, rank, world) is None, (rank, world)
+    assert _route({}, 2049, 8, 254, 255) == (A, 8, False)
+    assert _route({}, 5, source_kind=3) is None and _route({}, 5, source_kind=-1) is None
+
+
+# (name, lowest, highest) of every MSM switch with a range of values; the others store value != 0
+SWITCH_RANGES = (("chunk_len", 1, 65536), ("glv", 0, 2), ("glv_max_n", 0, 2**31 - 1), ("rowcol_quad_max", 0, 2**31 - 1), ("batched_host_horner_max", 0, 2**31 - 1),
+                 ("batched_split_min_m", 2, 2**31 - 1), ("tree_shift", -1, 4), ("profile", 0, 2), ("split_min_log2n", 10, 31))
+SWITCH_SETS = (("seg_m", (1, 2, 4, 8, 16)), ("horner_threads", (1, 2, 4)), ("rowcol_lgq", (0, 2, 3, 4)), ("sort_sub_bits", (0, 4, 5, 6, 7, 8)))
+SWITCH_FLAGS = ("chunk_rule", "stage_sort", "quad", "reduce_2d", "partition_sort", "big_bins", "scan_one", "fold_pass", "fold_quad", "rowcol_quad", "rowcol_row",
+                "tree_row", "tree_half", "zero_copy", "host_split", "arm_helpers", "horner_row", "small_msm", "small_row_tail", "auto_plan", "split",
+                "batched_split", "blocking_sync")
+
+
+def test_every_switch_accepts_its_range_and_nothing_beyond():
+    ok = lambda name, v: N.msm_call_describe({name: v}, 5) is not None
+    assert len(SWITCH_RANGES) + len(SWITCH_SETS) + len(SWITCH_FLAGS) == 36
+    for name, lo, hi in SWITCH_RANGES:
+        assert ok(name, lo) and ok(name, hi) and not ok(name, lo - 1), name
+        assert hi == 2**31 - 1 or not ok(name, hi + 1), name
+    for name, values in SWITCH_SETS:
+        for v in range(min(values) - 1, max(values) + 2):
+            assert ok(name, v) == (v in values), (name, v)
+    for name in SWITCH_FLAGS:
+        assert all(ok(name, v) for v in (0, 1, -1, 7)), name
+    for name in ("", "nonsense", "chunk_len ", "L0", "use_partition_sort", "split_min_n", "merlin_lanes", "alloc_fail_at", "wave_agg"):
+        assert not ok(name, 1), name
+    # a setting that is refused refuses the call, wherever it stands; a later setting of a name wins
+    assert N.msm_call_describe({"quad": 0, "seg_m": 3}, 5) is None
+    assert _route({"small_msm": 0, "glv": 1}, 2049) == ("regime A", 8, True)

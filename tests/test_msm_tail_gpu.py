@@ -81,6 +81,13 @@ class Tail:
             self.ctx.set_param(name, value)
             self.extra[name] = value
 
+    def describe(self, n, c, rank=0, world=1, **kw):
+        """The planner's word (cg1_msm_call_describe, no GPU) for a call under the switches as they stand."""
+        return N.msm_call_describe(dict(self.cur, **self.extra), n, c, rank, world, **kw)["tail"]
+
+    def raw_tail(self):
+        return int(N.cg1_get_last_tail(self.ctx.handle))
+
     def reset(self):
         self.set({})
         self.set_extra("small_msm", 0)
@@ -129,6 +136,8 @@ def _run(tail, case, dev, c, params, shard, failures):
     want_tail = T.tail_path(c, nlw, dev.n, p, case.e_top(p, windows))
     if ran != want_tail:
         failures.append(f"plan {c}, {params}, shard {shard}, {case.label}: ran {ran}, the model says {want_tail}")
+    if tail.raw_tail() != tail.describe(dev.n, c, rank, world, e_top=case.e_top(p, windows)):
+        failures.append(f"plan {c}, {params}, shard {shard}, {case.label}: ran {ran}, the planner says {N.decode_tail(tail.describe(dev.n, c, rank, world, e_top=case.e_top(p, windows)))}")
     if got != _expected(case.log(windows)):
         where = _localise(tail, case, dev, c) if shard is None else f"window {shard}"
         failures.append(f"plan {c}, {params}, shard {shard}, {case.label} ({ran['fold']} / {ran['rowcol']} lgq {ran['lgq']} / {ran['tree']} x {ran['tree_waves']} / "
@@ -231,6 +240,8 @@ def test_regime_b_horners(tail, M_, c):
         ran_kinds.add(ran["horner"])
         if ran != T.tail_path_batched(c, M_, params):
             failures.append(f"M {M_}, width {c}, {params}: ran {ran}, the model says {T.tail_path_batched(c, M_, params)}")
+        if tail.raw_tail() != tail.describe(dev.n, c, n_msms=M_, max_terms=4):
+            failures.append(f"M {M_}, width {c}, {params}: ran {ran}, the planner says another word")
         bad = [j for j, b in enumerate(blobs) if _compress(b) != want[j]]
         if bad:
             failures.append(f"M {M_}, width {c}, {params} ({ran['horner']}): WRONG points of MSMs {bad[:8]} ({len(bad)} in all)")
@@ -270,6 +281,8 @@ def test_small_kernel_tails(tail, c):
             ran, want_tail = tail.ctx.last_tail(), T.tail_path_small(1, {"small_row_tail": rt}, case.e_top({}))
             if tail.ctx.last_counts()["accumulate_launches"] != 0 or ran != want_tail:
                 failures.append(f"width {c}, small_row_tail {rt}, {case.label}: ran {ran}, the model says {want_tail}")
+            if tail.raw_tail() != tail.describe(dev.n, c, e_top=case.e_top({})):
+                failures.append(f"width {c}, small_row_tail {rt}, {case.label}: ran {ran}, the planner says another word")
             if got != _expected(case.log()):
                 failures.append(f"width {c}, small_row_tail {rt}, {case.label}: WRONG point")
         dev.free()
@@ -280,7 +293,7 @@ def test_small_kernel_tails(tail, c):
             tail.set({"small_row_tail": rt})
             blobs = tail.ctx.msm_batched_device(dev.d_p, dev.d_s, offs, window_c=c)
             ran = tail.ctx.last_tail()
-            if ran != T.tail_path_small(M_, {"small_row_tail": rt}):
+            if ran != T.tail_path_small(M_, {"small_row_tail": rt}) or tail.raw_tail() != tail.describe(dev.n, c, n_msms=M_, max_terms=4):
                 failures.append(f"width {c}, small_row_tail {rt}, {M_} MSMs: ran {ran}")
             bad = [j for j, b in enumerate(blobs) if _compress(b) != _expected(sum(k * s for s, k in terms[offs[j]: offs[j + 1]]) % R)]
             if bad:
