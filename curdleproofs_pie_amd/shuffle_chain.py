@@ -39,6 +39,7 @@ from typing import List, Optional
 
 from . import _native as N
 from .shuffle_verifier import REJECT_LENGTH, ShuffleBatchVerifier, _tracker_bytes
+from .verifier_pipeline import Batch, sum_stats
 
 
 _FR_MODULUS = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
@@ -270,7 +271,7 @@ class ShuffleChainVerifier:
 
     def _pieces(self, idx, posts: bytes, proofs: bytes, n: int, pre_status, weights):
         """The call's internal batches as the inner verifier's stream takes them: each expanded against the set's host bytes as the batches
-        before it left them, with its chain plan as the ticket's sixth field."""
+        before it left them, with its chain plan as the Batch's `chain`."""
         import numpy as np
 
         ts, ell, L, pb = self.set, self.crs.ell, self.crs.points_per_proof, self.crs.proof_bytes
@@ -292,8 +293,8 @@ class ShuffleChainVerifier:
             pairs[0::2, 0], pairs[1::2, 0] = 2 * writers[:, 0], 2 * writers[:, 0] + 1
             pairs[0::2, 1], pairs[1::2, 1] = src, src + ell
             chain = {"set": ts, "plan": plan, "pairs": pairs.tobytes(), "n_pairs": 2 * nw.value, "decoded_points": 0, "gathered_points": 0}
-            yield (inst, proofs if m == n else bytes(prf[a * pb: (a + m) * pb]), m, None if pre_status is None else list(pre_status[a: a + m]),
-                   None if w is None else bytes(w[a * 12 * 32: (a + m) * 12 * 32]), chain)
+            yield Batch(inst, proofs if m == n else bytes(prf[a * pb: (a + m) * pb]), m, None if pre_status is None else list(pre_status[a: a + m]),
+                        None if w is None else bytes(w[a * 12 * 32: (a + m) * 12 * 32]), chain)
 
     def verify_blocks_packed(self, indices, posts: bytes, proofs: bytes, n: int, mode: str = "merged", rng=None, weights=None, pre_status=None) -> List[int]:
         import numpy as np
@@ -321,11 +322,7 @@ class ShuffleChainVerifier:
         try:
             for st in self.verifier.verify_stream(self._pieces(idx, posts, proofs, n, pre_status, weights), mode=mode, rng=rng):
                 out += st
-                for k, v in (self.verifier.last_stats or {}).items():      # the call's statistics: summed over its internal batches
-                    if isinstance(v, bool) or not isinstance(v, (int, float)):
-                        total[k] = v
-                    else:
-                        total[k] = total.get(k, 0) + v
+                sum_stats(total, self.verifier.last_stats)             # the call's statistics: summed over its internal batches
             prefix = next((i for i, s in enumerate(out) if s), n)
             if prefix < n:
                 # rare, and allowed to be slow: the host bytes are authoritative -- the prefix replayed over the state before the call --

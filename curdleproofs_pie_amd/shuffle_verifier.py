@@ -22,66 +22,24 @@ from __future__ import annotations
 
 import ctypes
 import os
+import queue
 import secrets
+import threading
+import time
+from collections import deque, namedtuple
 from typing import List, Optional, Sequence, Tuple
 
 from . import _native as N
+from .verifier_pipeline import N_EXACT_POINTS, Batch, Lanes, Slot, Ticket, _addr, _runs, _Segments, coalesce_plan, sum_stats  # noqa: F401
 
 FR_MODULUS = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001  # util.py:7
 N_BLINDERS = 4                                                                   # curdleproofs.py:26
 N_WEIGHTS = 12
-N_EXACT_POINTS = 10            # T_1 T_2 U_1 U_2 R S cm_A cm_B: the proof's points in the same-scalar equalities (same_scalar.py:82-108)
 
 REJECT_NAMES = {0: "prepared", 1: "bad scalar encoding", 2: "bad point encoding", 3: "vec_T[0] is infinity", 4: "bad weight",
                 5: "bad length", 6: "verification equation failed"}
 REJECT_LENGTH, REJECT_EQUATION = 5, 6
 _CLEAR_TOP2 = bytes(b & 0x3F for b in range(256))
-
-
-def _addr(b) -> int:
-    """Address of the first byte of a bytes object / ctypes buffer (to pass sub-ranges of a batch to native code)."""
-    if isinstance(b, bytes):
-        return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p).value
-    return ctypes.addressof(b)
-
-
-class _Segments:
-    """Several callers' batches travelling as ONE internal batch without being copied together: item i of the internal batch is item
-    i - first of the segment that holds it.  `runs(lo, hi)` cuts [lo, hi) at the segment boundaries."""
-
-    def __init__(self, parts, item_bytes: int):
-        self.parts = list(parts)                              # [(bytes-like, n_items)]
-        self.item_bytes = item_bytes
-        self.first = [0]
-        for _, n in self.parts:
-            self.first.append(self.first[-1] + n)
-
-    def __len__(self) -> int:
-        return self.first[-1] * self.item_bytes
-
-    def runs(self, lo: int, hi: int):
-        """(address of item `a`, a, count) for every maximal run [a, a + count) of [lo, hi) inside one segment"""
-        for k, (buf, n) in enumerate(self.parts):
-            f = self.first[k]
-            a, b = max(lo, f), min(hi, f + n)
-            if a < b:
-                yield _addr(buf) + (a - f) * self.item_bytes, a, b - a
-
-    def item_addr(self, i: int) -> int:
-        for addr, a, cnt in self.runs(i, i + 1):
-            return addr
-        raise IndexError(i)
-
-    def joined(self) -> bytes:
-        return b"".join(bytes(buf) for buf, _ in self.parts)
-
-
-def _runs(buf, item_bytes: int, lo: int, hi: int):
-    """The same for a plain contiguous buffer: one run."""
-    if isinstance(buf, _Segments):
-        yield from buf.runs(lo, hi)
-    else:
-        yield _addr(buf) + lo * item_bytes, lo, hi - lo
 
 
 def _tracker_bytes(trackers) -> Tuple[bytes, bytes]:
@@ -99,6 +57,16 @@ def _tracker_bytes(trackers) -> Tuple[bytes, bytes]:
         return b"".join(rs), b"".join(ks)                 # bytes-likes (BLSPubkey is a bytes subclass)
     except TypeError:
         return b"".join(bytes(r) for r in rs), b"".join(bytes(k) for k in ks)
+
+
+_FeLane = namedtuple("_FeLane", "ctx fe aux_h aux_d")      # a front-end lane: its context (stream), device front-end handle, aux staging
+
+
+def _sum_is_identity(a: bytes, b: bytes) -> bool:
+    """The independent decision of one proof: P_i over its own points, Q_i over the CRS points; valid iff P_i + Q_i = 0."""
+    tmp = ctypes.create_string_buffer(N.POINT_BYTES)
+    N.cg1_add(tmp, a, b)
+    return bool(N.cg1_is_identity(tmp.raw))
 
 
 class ShuffleCrs:
@@ -140,21 +108,22 @@ class ShuffleCrs:
 class Prepared:
     """Output of the native front-end for n proofs (host buffers)."""
 
-    def __init__(self, crs: ShuffleCrs, n: int, want_challenges: bool, staging=None):
+    def __init__(self, crs: ShuffleCrs, n: int, want_challenges: bool, staging: Optional[Slot] = None):
         L, C = crs.points_per_proof, crs.ncrs
         self.n = n
         if staging is not None:                    # page-locked buffers of the GPU flow (scalars32 has room for the CRS row)
-            self.points48, self.scalars32 = staging["wire"].buf, staging["sc"].buf
+            self.points48, self.scalars32 = staging.pin.wire.buf, staging.pin.sc.buf
         else:
             self.points48 = ctypes.create_string_buffer(max(1, n * L * 48))
             self.scalars32 = ctypes.create_string_buffer(max(1, n * L * 32))
-        if staging is not None and staging.get("crs_scalars") is not None and len(staging["crs_scalars"]) >= n * C * 32:
-            self.crs_scalars32, self.status = staging["crs_scalars"], staging["status"]      # every byte is rewritten by prepare
+        kept = staging.scratch if staging is not None else None
+        if kept is not None and kept.crs_scalars is not None and len(kept.crs_scalars) >= n * C * 32:
+            self.crs_scalars32, self.status = kept.crs_scalars, kept.status      # every byte is rewritten by prepare
         else:
             self.crs_scalars32 = ctypes.create_string_buffer(max(1, n * C * 32))
             self.status = (ctypes.c_int32 * max(1, n))()
-            if staging is not None:
-                staging["crs_scalars"], staging["status"] = self.crs_scalars32, self.status
+            if kept is not None:
+                kept.crs_scalars, kept.status = self.crs_scalars32, self.status
         self.challenges = ctypes.create_string_buffer(n * crs.challenges_per_proof * 32) if want_challenges and n else None
 
 
@@ -183,6 +152,11 @@ class ShuffleBatchVerifier:
         self._coalesce_arg = coalesce
         self.crs = crs if isinstance(crs, ShuffleCrs) else ShuffleCrs(crs)
         self._ctx = ctx
+        self._user_ctx = None               # fe_cus: the caller's context, which stays untouched
+        self._own_ctx = False               # close() closes `_ctx`: it was made here (fe_cus) or for this pipeline (_sibling)
+        self._ctx_blocking = False          # `_ctx` was switched to blocking waits: close() sets it back
+        self._host_twin = None              # verify_packed's verifier with the host front-end, for isolated batches
+        self._kids = None                   # _verify_stream_pipelines' child verifiers
         self.threads = threads
         # blocking_sync: the two GPU-lane threads wait for the device asleep (hipEventBlockingSync) instead of spinning.  Measured
         # neutral on a 16-thread box (profiles/r03_verify_thread_sweep.txt: the front-end is bound by its 8 physical cores either
@@ -204,7 +178,6 @@ class ShuffleBatchVerifier:
         if env in ("0", "1"):
             device_front_end = env == "1"
         self._fe_by_default = device_front_end is None      # nobody asked for one of the two: an ISOLATED batch may take the other (verify_packed)
-        self._host_twin = None
         if device_front_end is None:
             # (round 5: also with the runtime's default of 4 hardware queues -- a stream then travels in coalesced internal batches of up to
             # 4 096 proofs, _verify_stream_coalesced: 1.55e5 proofs/s whatever the host's cores, against 7.6e4 for 1 024-proof batches alone;
@@ -225,7 +198,6 @@ class ShuffleBatchVerifier:
         self.pipelines = max(1, int(pipelines)) if self.device_front_end else 1
         if fe_lanes is None:
             fe_lanes = 2 if (self.pipelines > 1 or N.hw_queues() < 8) else 3
-        self._kids = None
         self.fe_lanes = max(1, int(fe_lanes)) if self.device_front_end else 0
         # coalesce: a STREAM of batches is verified in internal batches of up to this many proofs (_verify_stream_coalesced; 0 = never): a
         # front-end launch takes ~12 ms whatever it carries, so larger internal batches amortise it.  Measured with 1 024-proof batches
@@ -245,9 +217,8 @@ class ShuffleBatchVerifier:
             self._user_ctx = self._ctx                 # the caller's context stays untouched: this mode drives contexts of its own
             self._ctx = N.Context(self._user_ctx.device, cu_mask=range(0, self._cu_total - self.fe_cus))
             self._own_ctx = True
-        self._gpu_threads = [None, None] + [None] * self.fe_lanes
-        self._gpu_jobs = [None, None] + [None] * self.fe_lanes
-        self._fe = [None] * self.fe_lanes              # (context, cg1_shuffle_fe handle) per front-end lane
+        self._lanes = Lanes(2 + self.fe_lanes)
+        self._fe = [None] * self.fe_lanes              # a _FeLane per front-end lane, made on first use
         self._fe_next = 0
         self._ctx_msm = None
         self.prefetch_big = True            # two large decompress launches for batches decoded a batch ahead (A/B switch)
@@ -271,16 +242,16 @@ class ShuffleBatchVerifier:
         """Stop the two GPU threads (after what is queued has drained) and release the buffer slots and the MSM context.
         The verifier must not be used afterwards.  Idempotent; also run by __del__ and on cache eviction."""
         self._release_lanes()
-        if getattr(self, "_host_twin", None) is not None:
+        if self._host_twin is not None:
             self._host_twin.close()
             self._host_twin = None
-        for kid in (getattr(self, "_kids", None) or []):
+        for kid in self._kids or []:
             kid.close()
         self._kids = None
-        if getattr(self, "_ctx_blocking", False) and self._ctx is not None and self._ctx.handle:
+        if self._ctx_blocking and self._ctx is not None and self._ctx.handle:
             self._ctx.set_param("blocking_sync", 0)
             self._ctx_blocking = False
-        if getattr(self, "_own_ctx", False) and self._ctx is not None:
+        if self._own_ctx and self._ctx is not None:
             self._ctx.close()
             self._ctx = None
             self._own_ctx = False
@@ -289,31 +260,18 @@ class ShuffleBatchVerifier:
         """Give back what this verifier's OWN lanes hold -- GPU threads, buffer slots, the MSM context, the front-end contexts -- and
         with them their hardware queues (a process has 24: a verifier whose pipelines run on child verifiers must not keep lanes of its
         own alive beside them).  They are rebuilt on demand."""
-        for lane in range(len(self._gpu_threads)):
-            t, q = self._gpu_threads[lane], self._gpu_jobs[lane]
-            if t is not None:
-                q.put(None)
-                t.join()
-            self._gpu_threads[lane] = self._gpu_jobs[lane] = None
-        for i, b in enumerate(self._slots):
-            if b is not None:
-                for k in ("wire", "pts", "pstat", "sgflags", "sc", "rowin", "hstat", "csrows", "dstat"):
-                    b[k].free()
-                for x in (b.get("exact") or {}).values():
-                    x.free()
-                for h in b["host"].values():
-                    if isinstance(h, N.PinnedBuffer):          # (the staging dict also caches plain ctypes buffers)
-                        h.free()
-                self._slots[i] = None
+        self._lanes.stop()
+        for b in filter(None, self._slots):
+            b.free()
+        self._slots = [None] * self._nslots
         if self._ctx_msm is not None:
             self._ctx_msm.close()
             self._ctx_msm = None
-        for k, pair in enumerate(getattr(self, "_fe", [])):
-            if pair is not None:
-                cx, fe, aux_h, aux_d = pair
-                N.cg1_shuffle_fe_destroy(fe)
-                aux_h.free(); aux_d.free()
-                cx.close()
+        for k, lane in enumerate(self._fe):
+            if lane is not None:
+                N.cg1_shuffle_fe_destroy(lane.fe)
+                lane.aux_h.free(); lane.aux_d.free()
+                lane.ctx.close()
                 self._fe[k] = None
 
     def __del__(self):
@@ -383,7 +341,7 @@ class ShuffleBatchVerifier:
                 self._own_ctx = True
             else:
                 self._ctx = N.default_context()
-        if self.blocking_sync and not getattr(self, "_ctx_blocking", False):
+        if self.blocking_sync and not self._ctx_blocking:
             self._ctx.set_param("blocking_sync", 1)        # (a shared context: close() sets it back)
             self._ctx_blocking = True
         return self._ctx
@@ -397,76 +355,27 @@ class ShuffleBatchVerifier:
             self._ctx_msm.set_param("blocking_sync", 1 if self.blocking_sync else 0)
         return self._ctx_msm
 
-    def _gpu_submit(self, fn, lane: int = 0) -> None:
-        """GPU work runs on two persistent threads (a thread's first HIP call is expensive; a context takes one call at
-        a time): lane 0 drives `ctx` (staging + decompression, in submission order), lane 1 drives `ctx_msm` (MSMs)."""
-        import queue
-        import threading
-
-        if self._gpu_threads[lane] is None:
-            jobs = self._gpu_jobs[lane] = queue.Queue()
-
-            def loop(jobs=jobs):
-                while True:
-                    job = jobs.get()
-                    if job is None:
-                        return
-                    job()
-
-            self._gpu_threads[lane] = threading.Thread(target=loop, daemon=True)
-            self._gpu_threads[lane].start()
-        self._gpu_jobs[lane].put(fn)
-
-    def _alloc_slot(self, n: int) -> dict:
-        crs, ctx = self.crs, self.ctx
-        L, C = crs.points_per_proof, crs.ncrs
-        return {
-            "cap": n, "busy": None,
-            "wire": ctx.alloc(n * L * 48),
-            "pts": ctx.alloc((n * L + C) * 96),              # own points of all proofs, then the CRS points
-            "pstat": ctx.alloc(n * L),
-            "sgflags": ctx.alloc(n * N_EXACT_POINTS),        # 1 = outside G1, for the points of the exactly-asserted equalities
-            "sc": ctx.alloc((n * L + C) * 32),
-            "rowin": ctx.alloc(n * self._rowin_scalars * 32),   # device row builder: input blocks, host codes, CRS rows, final codes
-            "hstat": ctx.alloc(4 * n), "csrows": ctx.alloc(n * C * 32), "dstat": ctx.alloc(4 * n),
-            "host": {                                        # page-locked staging
-                "wire": N.PinnedBuffer(ctx, n * L * 48),
-                "sc": N.PinnedBuffer(ctx, (n * L + C) * 32),
-                "rowin": N.PinnedBuffer(ctx, n * self._rowin_scalars * 32),
-                "hstat": N.PinnedBuffer(ctx, 4 * n),
-                "pstat": N.PinnedBuffer(ctx, n * L),
-                "decoded": N.PinnedBuffer(ctx, n * 768),
-                "fe_wire": N.PinnedBuffer(ctx, min(n, self.FE_FIRST_MAX) * L * 48),   # the front-end's own copy of a tiny batch's points
-            },
-        }
+    def _slot_dims(self) -> tuple:
+        return self.crs.points_per_proof, self.crs.ncrs, self._rowin_scalars, self.FE_FIRST_MAX
 
     def _slot_pinned_bytes(self, n: int) -> int:
-        L, C = self.crs.points_per_proof, self.crs.ncrs
-        return n * L * 48 + (n * L + C) * 32 + n * self._rowin_scalars * 32 + 4 * n + n * L + n * 768 + min(n, self.FE_FIRST_MAX) * L * 48
+        return sum(Slot.sizes(n, *self._slot_dims())["pinned"].values())
+
+    def _alloc_slot(self, n: int) -> Slot:
+        return Slot(self.ctx, n, *self._slot_dims())
 
     def footprint(self) -> dict:
         """Bytes this verifier holds for its batch slots and front-end lanes: {"pinned_bytes", "device_bytes", "slots", "pipelines": [...]}
         (page-locked host staging / hipMalloc'd buffers; the contexts' own scratch -- MSM buckets, sort buffers -- is not counted here)."""
-        pinned = device = slots = 0
-        for b in self._slots:
-            if b is None:
-                continue
-            slots += 1
-            for v in b.values():
-                if isinstance(v, N.DeviceBuffer):
-                    device += v.nbytes
-            for v in b["host"].values():
-                if isinstance(v, N.PinnedBuffer):
-                    pinned += v.nbytes
-        for pair in self._fe:
-            if pair is not None:
-                pinned += pair[2].nbytes
-                device += pair[3].nbytes
+        held = [b for b in self._slots if b is not None]
+        lanes = [fe for fe in self._fe if fe is not None]
+        pinned = sum(b.pinned_bytes for b in held) + sum(fe.aux_h.nbytes for fe in lanes)
+        device = sum(b.device_bytes for b in held) + sum(fe.aux_d.nbytes for fe in lanes)
         kids = [k.footprint() for k in (self._kids or [])]
         return {"pinned_bytes": pinned + sum(k["pinned_bytes"] for k in kids), "device_bytes": device + sum(k["device_bytes"] for k in kids),
-                "slots": slots, "pipelines": kids}
+                "slots": len(held), "pipelines": kids}
 
-    def _slot(self, n: int) -> dict:
+    def _slot(self, n: int) -> Slot:
         """Buffers of one batch in flight (3 slots rotate: MSM of batch k-1, front-end of k, decompression of k+1).
         All three are allocated together the first time a batch size is seen (page-locking tens of MB takes
         milliseconds: not something to meet again in the middle of a stream)."""
@@ -479,228 +388,189 @@ class ShuffleBatchVerifier:
         idx = self._next_slot
         self._next_slot = (idx + 1) % self._nslots
         b = self._slots[idx]
-        if b is not None and b["busy"] is not None:
-            b["busy"].wait()                                  # its previous batch must have left the GPU
-        if b is None or b["cap"] < n:
+        if b is not None and b.busy is not None:
+            b.busy.wait()                                     # its previous batch must have left the GPU
+        if b is None or b.cap < n:
             for j in range(self._nslots):
                 o = self._slots[j]
-                if o is None or (o["cap"] < n and (o["busy"] is None or o["busy"].is_set())):
+                if o is None or (o.cap < n and (o.busy is None or o.busy.is_set())):
                     self._slots[j] = self._alloc_slot(n)
             b = self._slots[idx]
-            if b["cap"] < n:                                  # was still busy above: wait, then replace
-                b["busy"].wait()
+            if b.cap < n:                                     # was still busy above: wait, then replace
+                b.busy.wait()
                 b = self._slots[idx] = self._alloc_slot(n)
         return b
 
-    def _stage_in(self, b: dict, instances, proofs, lo: int, hi: int) -> None:
+    def _stage_in(self, b: Slot, instances, proofs, lo: int, hi: int) -> None:
         """GPU thread: gather the own points of proofs [lo, hi) into page-locked memory and queue their H2D copy on the
         context's copy stream (it overlaps the decompression kernel of the previous sub-batch)."""
         crs, ctx = self.crs, self.ctx
         L = crs.points_per_proof
-        wire = b["host"]["wire"].ptr + lo * L * 48
+        wire = b.pin.wire.ptr + lo * L * 48
         for (ia, a, cnt), (pa, _, _) in zip(_runs(instances, 4 * crs.ell * 48, lo, hi), _runs(proofs, crs.proof_bytes, lo, hi)):
-            ctx.check(N.cg1_shuffle_gather_points(crs.handle, cnt, ia, pa, b["host"]["wire"].ptr + a * L * 48))
-        ctx.check(N.cg1_h2d_async(ctx.handle, b["wire"].ptr + lo * L * 48, wire, (hi - lo) * L * 48))
+            ctx.check(N.cg1_shuffle_gather_points(crs.handle, cnt, ia, pa, b.pin.wire.ptr + a * L * 48))
+        ctx.check(N.cg1_h2d_async(ctx.handle, b.dev.wire.ptr + lo * L * 48, wire, (hi - lo) * L * 48))
 
-    def _decompress_launch(self, b: dict, lo: int, hi: int, chain: Optional[dict] = None) -> None:
+    def _decompress_launch(self, b: Slot, lo: int, hi: int, chain: Optional[dict] = None) -> None:
         """GPU thread: once the sub-batch's copy has landed, launch its decompression (points stay on the device for the MSM).
         chain (shuffle_chain.py): the pre trackers -- the first 2 ell points of every proof -- are not decoded again: the strided launch
         leaves them out and the gather behind it, on the same stream, copies their records from where they were decoded before."""
         ctx, L = self.ctx, self.crs.points_per_proof
         ctx.check(N.cg1_copy_fence(ctx.handle))
         if chain is None:
-            ctx.check(N.cg1_batch_decompress_enqueue(ctx.handle, b["wire"].ptr + lo * L * 48, b["pts"].ptr + lo * L * 96,
-                                                     b["pstat"].ptr + lo * L, (hi - lo) * L, 0))
+            ctx.check(N.cg1_batch_decompress_enqueue(ctx.handle, b.dev.wire.ptr + lo * L * 48, b.dev.pts.ptr + lo * L * 96,
+                                                     b.dev.pstat.ptr + lo * L, (hi - lo) * L, 0))
             return
         pre = 2 * self.crs.ell
-        ctx.check(N.cg1_batch_decompress_strided_enqueue(ctx.handle, b["wire"].ptr + lo * L * 48, b["pts"].ptr + lo * L * 96, b["pstat"].ptr + lo * L,
+        ctx.check(N.cg1_batch_decompress_strided_enqueue(ctx.handle, b.dev.wire.ptr + lo * L * 48, b.dev.pts.ptr + lo * L * 96, b.dev.pstat.ptr + lo * L,
                                                          hi - lo, L, pre, L - pre))
         chain["decoded_points"] += (hi - lo) * (L - pre)
 
-    def _chain_gather(self, b: dict, n: int, lo: int, hi: int, chain: dict) -> None:
+    def _chain_gather(self, b: Slot, n: int, lo: int, hi: int, chain: dict) -> None:
         """GPU thread, directly behind the sub-batch's decoding: every pre position of the proofs [lo, hi) <- its source's decoded record
         and status byte (an earlier proof's post position in this slot, or an entry of the resident set)."""
         ctx, L, pre, ts = self.ctx, self.crs.points_per_proof, 2 * self.crs.ell, chain["set"]
-        ctx.check(N.cg1_chain_gather_enqueue(ctx.handle, b["pts"].ptr, b["pstat"].ptr, n * L, ts.d_pts.ptr, ts.d_pstat.ptr, 2 * ts.n_slots,
+        ctx.check(N.cg1_chain_gather_enqueue(ctx.handle, b.dev.pts.ptr, b.dev.pstat.ptr, n * L, ts.d_pts.ptr, ts.d_pstat.ptr, 2 * ts.n_slots,
                                              ctypes.addressof(chain["plan"]) + lo * pre * 4, lo, hi - lo, L, pre))
         chain["gathered_points"] += (hi - lo) * pre
 
-    def _chain_scatter(self, b: dict, n: int, chain: dict) -> None:
+    def _chain_scatter(self, b: Slot, n: int, chain: dict) -> None:
         """GPU thread, behind the batch's last sub-batch: the final post of every slot the batch wrote -> the resident set."""
         ctx, ts = self.ctx, chain["set"]
-        ctx.check(N.cg1_chain_scatter_enqueue(ctx.handle, b["pts"].ptr, b["pstat"].ptr, n * self.crs.points_per_proof, ts.d_pts.ptr, ts.d_pstat.ptr,
+        ctx.check(N.cg1_chain_scatter_enqueue(ctx.handle, b.dev.pts.ptr, b.dev.pstat.ptr, n * self.crs.points_per_proof, ts.d_pts.ptr, ts.d_pstat.ptr,
                                               2 * ts.n_slots, chain["pairs"], chain["n_pairs"]))
 
-    def _decompress_collect(self, b: dict, lo: int, hi: int) -> None:
+    def _decompress_collect(self, b: Slot, lo: int, hi: int) -> None:
         """GPU thread: wait for the kernel, bring back the per-point verdicts and the 8-point window the front-end wants."""
         crs, ctx = self.crs, self.ctx
-        L, h, m = crs.points_per_proof, b["host"], hi - lo
+        L, h, m = crs.points_per_proof, b.pin, hi - lo
         ctx.check(N.cg1_stream_sync(ctx.handle))                  # this context's kernel only: the MSM context keeps running
-        ctx.check(N.cg1_d2h(ctx.handle, h["pstat"].ptr + lo * L, b["pstat"].ptr + lo * L, m * L))
-        ctx.check(N.cg1_d2h_2d(ctx.handle, h["decoded"].ptr + lo * 768, 768, b["pts"].ptr + (lo * L + 4 * crs.ell + 1) * 96, L * 96, 768, m))
+        ctx.check(N.cg1_d2h(ctx.handle, h.pstat.ptr + lo * L, b.dev.pstat.ptr + lo * L, m * L))
+        ctx.check(N.cg1_d2h_2d(ctx.handle, h.decoded.ptr + lo * 768, 768, b.dev.pts.ptr + (lo * L + 4 * crs.ell + 1) * 96, L * 96, 768, m))
 
-    def _begin(self, batch, mode: str, rng, prefetched: bool = False) -> dict:
+    def _begin(self, batch: Batch, mode: str, rng, prefetched: bool = False) -> Ticket:
         """Stage 1 of a batch (asynchronous): claim a slot and queue the GPU decompression of its sub-batches.
         prefetched: the batch is decoded a whole batch ahead of its front-end, so small sub-batches buy nothing and
         two large launches fill the GPU better (2 x 2.3 ms instead of 4 x 1.4 ms per 1024 proofs)."""
-        import queue
-        import threading
-        import time
-
-        instances, proofs, n = batch[0], batch[1], batch[2]
+        instances, proofs, n = batch.instances, batch.proofs, batch.n
         crs = self.crs
-        L, C = crs.points_per_proof, crs.ncrs
+        L = crs.points_per_proof
         assert n >= 1 and len(instances) == n * 4 * crs.ell * 48 and len(proofs) == n * crs.proof_bytes
-        weights = batch[4] if len(batch) > 4 else None       # None: drawn on the GPU thread while the first kernel runs
-        chain = batch[5] if len(batch) > 5 else None         # a chain plan (shuffle_chain.py): pre trackers are gathered, not decoded
-        assert weights is None or len(weights) == n * N_WEIGHTS * 32
+        chain = batch.chain                                  # a chain plan (shuffle_chain.py): pre trackers are gathered, not decoded
+        assert batch.weights is None or len(batch.weights) == n * N_WEIGHTS * 32      # None: drawn on the GPU thread while the first kernel runs
         b = self._slot(n)
-        tk = {"slot": b, "n": n, "instances": instances, "proofs": proofs, "weights": weights, "mode": mode,
-              "pre_status": batch[3] if len(batch) > 3 else None, "chunks": queue.Queue(), "done": threading.Event(),
-              "error": None, "t0": time.perf_counter(), "flags_done": threading.Event(), "sgflags": None, "chain": chain}
         step = max(self.chunk, (n + 1) // 2) if (prefetched and self.prefetch_big) else self.chunk
-        tk["bounds"] = [(lo, min(lo + step, n)) for lo in range(0, n, step)]
-        b["busy"] = tk["done"]
         # a handful of proofs (IsValidWhiskShuffleProof is a batch of one): the front-end does not wait for the GPU's decoding -- it decodes
         # the four points it needs itself (4 x 14 us per proof) and runs BESIDE the decompression launch instead of behind it
-        tk["fe_first"] = n <= self.FE_FIRST_MAX and not self.device_front_end
-        if tk["fe_first"] and tk["weights"] is None:
-            tk["weights"] = self.draw_weights(n, rng)
+        tk = Ticket(batch, b, mode, [(lo, min(lo + step, n)) for lo in range(0, n, step)], fe_first=n <= self.FE_FIRST_MAX and not self.device_front_end)
+        b.busy = tk.done
+        if tk.fe_first and tk.weights is None:
+            tk.weights = self.draw_weights(n, rng)
 
-        def gpu_stage(tk=tk, b=b):
-            try:
-                t_dec = time.perf_counter()
-                if b.get("crs_at") != n:                       # CRS points sit right behind the batch's own points
-                    b["pts"].upload(crs.affine96, n * L * 96)
-                    b["crs_at"] = n
-                bounds = tk["bounds"]
-                self._stage_in(b, instances, proofs, *bounds[0])
-                for i, (lo, hi) in enumerate(bounds):              # copy of sub-batch i+1 overlaps the kernel of sub-batch i
-                    self._decompress_launch(b, lo, hi, chain)
-                    if chain is not None:
-                        self._chain_gather(b, n, lo, hi, chain)
-                        if i + 1 == len(bounds):
-                            self._chain_scatter(b, n, chain)
-                    if tk["weights"] is None:
-                        tk["weights"] = self.draw_weights(n, rng)
-                    if i + 1 < len(bounds):
-                        self._stage_in(b, instances, proofs, *bounds[i + 1])
+        def gpu_stage():
+            t_dec = time.perf_counter()
+            if b.crs_at != n:                                 # CRS points sit right behind the batch's own points
+                b.dev.pts.upload(crs.affine96, n * L * 96)
+                b.crs_at = n
+            bounds = tk.bounds
+            self._stage_in(b, instances, proofs, *bounds[0])
+            for i, (lo, hi) in enumerate(bounds):              # copy of sub-batch i+1 overlaps the kernel of sub-batch i
+                self._decompress_launch(b, lo, hi, chain)
+                if chain is not None:
+                    self._chain_gather(b, n, lo, hi, chain)
                     if i + 1 == len(bounds):
-                        # beside whatever runs next (side stream, one launch per batch): are the proof's points in the
-                        # exactly-asserted same-scalar equalities inside G1?
-                        self.ctx.check(N.cg1_subgroup_flags_enqueue(self.ctx.handle, b["pts"].ptr, L, n, self._exact_offsets,
-                                                                    N_EXACT_POINTS, b["sgflags"].ptr))
-                    self._decompress_collect(b, lo, hi)
-                    tk["decompress_s"] = time.perf_counter() - t_dec   # staging + H2D + kernel + D2H of the batch's sub-batches
-                    tk["chunks"].put((lo, hi))
-                # the subgroup flags come back on THIS thread (a context takes one call at a time; the MSM stage runs on the other
-                # lane): the front-end is already released, so only this lane's next batch waits for the side stream
-                self.ctx.check(N.cg1_side_sync(self.ctx.handle))
-                tk["sgflags"] = b["sgflags"].download(n * N_EXACT_POINTS)
-            except BaseException as e:                          # surfaced in the consumer
-                tk["chunks"].put(e)
-            finally:
-                tk["flags_done"].set()
+                        self._chain_scatter(b, n, chain)
+                if tk.weights is None:
+                    tk.weights = self.draw_weights(n, rng)
+                if i + 1 < len(bounds):
+                    self._stage_in(b, instances, proofs, *bounds[i + 1])
+                if i + 1 == len(bounds):
+                    # beside whatever runs next (side stream, one launch per batch): are the proof's points in the
+                    # exactly-asserted same-scalar equalities inside G1?
+                    self.ctx.check(N.cg1_subgroup_flags_enqueue(self.ctx.handle, b.dev.pts.ptr, L, n, self._exact_offsets,
+                                                                N_EXACT_POINTS, b.dev.sgflags.ptr))
+                self._decompress_collect(b, lo, hi)
+                tk.decompress_s = time.perf_counter() - t_dec   # staging + H2D + kernel + D2H of the batch's sub-batches
+                tk.chunks.put((lo, hi))
+            # the subgroup flags come back on THIS thread (a context takes one call at a time; the MSM stage runs on the other
+            # lane): the front-end is already released, so only this lane's next batch waits for the side stream
+            self.ctx.check(N.cg1_side_sync(self.ctx.handle))
+            tk.sgflags = b.dev.sgflags.download(n * N_EXACT_POINTS)
 
-        self._gpu_submit(gpu_stage)
+        self._lanes.stage(0, tk, tk.flags_done, gpu_stage)
         return tk
 
-    def _front_end(self, tk: dict) -> None:
-        if isinstance(tk["instances"], _Segments):            # (the host front-end takes contiguous bytes; coalescing is the device front-end's)
-            tk["instances"], tk["proofs"] = tk["instances"].joined(), tk["proofs"].joined()
-        return self._front_end_contiguous(tk)
-
-    def _front_end_contiguous(self, tk: dict) -> None:
+    def _front_end(self, tk: Ticket) -> None:
         """Stage 2 (caller's thread, all cores through the native pool): the front-end of each sub-batch as soon as the
         GPU has decoded it.  device_rows: it emits the row builder's input blocks (challenges + derived scalars), which go
         to the device with the host's reject codes; else the rows themselves, then point verdicts, early rejects and the
         summed CRS row on the host."""
-        import time
-
+        if isinstance(tk.instances, _Segments):               # (the host front-end takes contiguous bytes; coalescing is the device front-end's)
+            tk.instances, tk.proofs = tk.instances.joined(), tk.proofs.joined()
         crs = self.crs
         L, C, K = crs.points_per_proof, crs.ncrs, self._rowin_scalars
-        b, n = tk["slot"], tk["n"]
-        host = b["host"]
+        b, n, fe_first = tk.slot, tk.n, tk.fe_first
+        host = b.pin
         t0 = time.perf_counter()
-        dev = self.device_rows
-        tk["device_rows"] = dev
-        prep = None if dev else Prepared(crs, n, False, host)
-        tk["prep"] = prep
-        hstat = (ctypes.c_int32 * n).from_address(host["hstat"].ptr)
-        fe_first = tk.get("fe_first", False)
-        if fe_first:
-            todo = [(0, n)]                                   # the whole batch at once, before the GPU has decoded anything
-        else:
-            todo = tk["bounds"]
-        for item in todo:
-            if fe_first:
-                r = item
-            else:
-                r = tk["chunks"].get()
-            if isinstance(r, BaseException):
-                tk["error"] = r
-                tk["done"].set()
-                raise r
-            lo, hi = r
-            args = (crs.handle, hi - lo, _addr(tk["instances"]) + lo * 4 * crs.ell * 48, _addr(tk["proofs"]) + lo * crs.proof_bytes,
-                    _addr(tk["weights"]) + lo * N_WEIGHTS * 32, None if fe_first else host["decoded"].ptr + lo * 768, 768,
-                    host["fe_wire"].ptr + lo * L * 48 if fe_first else host["wire"].ptr + lo * L * 48)
+        dev = tk.device_rows = self.device_rows
+        prep = tk.prep = None if dev else Prepared(crs, n, False, b)
+        hstat = (ctypes.c_int32 * n).from_address(host.hstat.ptr)
+        for whole in ([(0, n)] if fe_first else tk.bounds):  # fe_first: the whole batch at once, before the GPU has decoded anything
+            lo, hi = whole if fe_first else tk.next_chunk()
+            args = (crs.handle, hi - lo, _addr(tk.instances) + lo * 4 * crs.ell * 48, _addr(tk.proofs) + lo * crs.proof_bytes,
+                    _addr(tk.weights) + lo * N_WEIGHTS * 32, None if fe_first else host.decoded.ptr + lo * 768, 768,
+                    host.fe_wire.ptr + lo * L * 48 if fe_first else host.wire.ptr + lo * L * 48)
             if dev:
-                rc = N.cg1_shuffle_prepare_inputs(*args, host["rowin"].ptr + lo * K * 32, host["hstat"].ptr + lo * 4, self.threads)
+                rc = N.cg1_shuffle_prepare_inputs(*args, host.rowin.ptr + lo * K * 32, host.hstat.ptr + lo * 4, self.threads)
             else:
-                rc = N.cg1_shuffle_prepare(*args, host["sc"].ptr + lo * L * 32, ctypes.addressof(prep.crs_scalars32) + lo * C * 32,
+                rc = N.cg1_shuffle_prepare(*args, host.sc.ptr + lo * L * 32, ctypes.addressof(prep.crs_scalars32) + lo * C * 32,
                                            ctypes.addressof(prep.status) + lo * 4, None, self.threads)
             if rc:
-                tk["done"].set()
-                raise N.NativeError(f"cg1_shuffle_prepare failed ({rc})")
+                tk.fail(N.NativeError(f"cg1_shuffle_prepare failed ({rc})"))
+                raise tk.error
         if fe_first:                                          # now the decoding must have finished (point verdicts, decoded points for the MSM)
-            for _ in tk["bounds"]:
-                r = tk["chunks"].get()
-                if isinstance(r, BaseException):
-                    tk["error"] = r
-                    tk["done"].set()
-                    raise r
+            for _ in tk.bounds:
+                tk.next_chunk()
         if dev:
-            for i, s in enumerate(tk["pre_status"] or ()):
+            for i, s in enumerate(tk.pre_status or ()):
                 if s:
                     hstat[i] = s
             # input blocks + host codes to the device on the MSM context's copy stream, from this thread
-            self.ctx_msm.check(N.cg1_h2d_async(self.ctx_msm.handle, b["rowin"].ptr, host["rowin"].ptr, n * K * 32))
-            self.ctx_msm.check(N.cg1_h2d_async(self.ctx_msm.handle, b["hstat"].ptr, host["hstat"].ptr, 4 * n))
-            tk["front_end_s"] = time.perf_counter() - t0
-            return
-        self.ctx.check(N.cg1_shuffle_apply_point_status(prep.status, host["pstat"].buf, n, L, prep.scalars32, prep.crs_scalars32, C))
-        for i, s in enumerate(tk["pre_status"] or ()):
-            if s:
-                prep.status[i] = s
-                ctypes.memset(ctypes.addressof(prep.scalars32) + i * L * 32, 0, L * 32)
-                ctypes.memset(ctypes.addressof(prep.crs_scalars32) + i * C * 32, 0, C * 32)
-        crs_sum = ctypes.create_string_buffer(C * 32)
-        self.ctx.check(N.cg1_shuffle_sum_crs_scalars(prep.crs_scalars32, prep.status, n, C, crs_sum))
-        ctypes.memmove(host["sc"].ptr + n * L * 32, crs_sum, C * 32)
-        # scalars to the device on the copy stream, from this thread, while the GPU thread is busy with other batches
-        self.ctx_msm.check(N.cg1_h2d_async(self.ctx_msm.handle, b["sc"].ptr, host["sc"].ptr, (n * L + C) * 32))
-        tk["front_end_s"] = time.perf_counter() - t0
+            self.ctx_msm.check(N.cg1_h2d_async(self.ctx_msm.handle, b.dev.rowin.ptr, host.rowin.ptr, n * K * 32))
+            self.ctx_msm.check(N.cg1_h2d_async(self.ctx_msm.handle, b.dev.hstat.ptr, host.hstat.ptr, 4 * n))
+        else:
+            self.ctx.check(N.cg1_shuffle_apply_point_status(prep.status, host.pstat.buf, n, L, prep.scalars32, prep.crs_scalars32, C))
+            for i, s in enumerate(tk.pre_status or ()):
+                if s:
+                    prep.status[i] = s
+                    ctypes.memset(ctypes.addressof(prep.scalars32) + i * L * 32, 0, L * 32)
+                    ctypes.memset(ctypes.addressof(prep.crs_scalars32) + i * C * 32, 0, C * 32)
+            crs_sum = ctypes.create_string_buffer(C * 32)
+            self.ctx.check(N.cg1_shuffle_sum_crs_scalars(prep.crs_scalars32, prep.status, n, C, crs_sum))
+            ctypes.memmove(host.sc.ptr + n * L * 32, crs_sum, C * 32)
+            # scalars to the device on the copy stream, from this thread, while the GPU thread is busy with other batches
+            self.ctx_msm.check(N.cg1_h2d_async(self.ctx_msm.handle, b.dev.sc.ptr, host.sc.ptr, (n * L + C) * 32))
+        tk.front_end_s = time.perf_counter() - t0
+        tk.fe_done.set()
 
-    def _decide_flagged(self, tk: dict, i: int) -> bool:
+    def _decide_flagged(self, tk: Ticket, i: int) -> bool:
         """MSM lane: proof i of the batch (it carries a point outside G1 in the same-scalar argument) on its own -- the weighted
         statement without the four same-scalar equalities (w1..w4 = 0) over its decoded points, which are still on the device,
         plus those four equalities exactly (cg1_shuffle_exact_same_scalar)."""
         crs, ctx = self.crs, self.ctx_msm
         L, C = crs.points_per_proof, crs.ncrs
-        b, n = tk["slot"], tk["n"]
+        b, n = tk.slot, tk.n
         ib, pb = 4 * crs.ell * 48, crs.proof_bytes
-        inst = next(_runs(tk["instances"], ib, i, i + 1))[0]
-        proof = next(_runs(tk["proofs"], pb, i, i + 1))[0]
+        inst = next(_runs(tk.instances, ib, i, i + 1))[0]
+        proof = next(_runs(tk.proofs, pb, i, i + 1))[0]
         ok = ctypes.c_int(0)
         ctx.check(N.cg1_shuffle_exact_same_scalar(crs.handle, inst, proof, ctypes.byref(ok)))
         if not ok.value:
             return False
-        w = bytearray(tk["weights"][i * N_WEIGHTS * 32: (i + 1) * N_WEIGHTS * 32])
+        w = bytearray(tk.weights[i * N_WEIGHTS * 32: (i + 1) * N_WEIGHTS * 32])
         w[8 * 32: 12 * 32] = bytes(4 * 32)
-        host = b["host"]
         sc, csc, st = ctypes.create_string_buffer(L * 32), ctypes.create_string_buffer(C * 32), (ctypes.c_int32 * 1)()
-        rc = N.cg1_shuffle_prepare(crs.handle, 1, inst, proof, bytes(w), host["decoded"].ptr + i * 768, 768, host["wire"].ptr + i * L * 48,
+        rc = N.cg1_shuffle_prepare(crs.handle, 1, inst, proof, bytes(w), b.pin.decoded.ptr + i * 768, 768, b.pin.wire.ptr + i * L * 48,
                                    sc, csc, st, None, 1)
         if rc:
             raise N.NativeError(f"cg1_shuffle_prepare failed ({rc})")
@@ -709,15 +579,13 @@ class ShuffleBatchVerifier:
         d_sc, d_csc = ctx.alloc(L * 32), ctx.alloc(C * 32)
         try:
             d_sc.upload(sc.raw); d_csc.upload(csc.raw)
-            own = ctx.msm_device(b["pts"].ptr + i * L * 96, d_sc, L)
-            shared = ctx.msm_device(b["pts"].ptr + n * L * 96, d_csc, C)
+            own = ctx.msm_device(b.dev.pts.ptr + i * L * 96, d_sc, L)
+            shared = ctx.msm_device(b.dev.pts.ptr + n * L * 96, d_csc, C)
         finally:
             d_sc.free(); d_csc.free()
-        tmp = ctypes.create_string_buffer(N.POINT_BYTES)
-        N.cg1_add(tmp, own, shared)
-        return bool(N.cg1_is_identity(tmp.raw))
+        return _sum_is_identity(own, shared)
 
-    def _decide_flagged_device(self, tk: dict, flagged: List[int]):
+    def _decide_flagged_device(self, tk: Ticket, flagged: List[int]):
         """MSM lane: the live proofs `flagged` of the batch (each carries a point outside G1 in the same-scalar argument) decided together,
         as _decide_flagged decides one: -> ([accepted per proof], native calls made).
           * the 4 f same-scalar equalities EXACTLY, in one launch of k_exact_relations: term lists straight over the slot's decoded points
@@ -733,15 +601,8 @@ class ShuffleBatchVerifier:
 
         crs, ctx = self.crs, self.ctx_msm
         L, C, K, ell, lg = crs.points_per_proof, crs.ncrs, self._rowin_scalars, crs.ell, crs.lg
-        b, n, f = tk["slot"], tk["n"], len(flagged)
-        x = b.get("exact")
-        if x is None:
-            cap = b["cap"]
-            x = b["exact"] = {"ok": ctx.alloc(4 * cap), "rowin": ctx.alloc(cap * K * 32), "pts": ctx.alloc(cap * L * 96), "rep": ctx.alloc(cap * C * 96),
-                              "sc": ctx.alloc((cap * L + C) * 32), "csrows": ctx.alloc(cap * C * 32), "dstat": ctx.alloc(4 * cap),
-                              "hstat": ctx.alloc(4 * cap), "pstat": ctx.alloc(cap * L)}
-            x["hstat"].upload(bytes(4 * cap)); x["pstat"].upload(bytes(cap * L))      # live proofs, decodable points: never written again
-        calls = 0
+        b, n, f = tk.slot, tk.n, len(flagged)
+        x = b.exact_buffers(ctx)
         idx = np.asarray(flagged, dtype=np.uint64)
         own, cb, sb = idx * L + 4 * ell, n * L, idx * K
         fields = ell + 10 + 4 * lg
@@ -756,103 +617,80 @@ class ShuffleBatchVerifier:
                           R, zk, H, zt, A2, minus_one, T2, al | neg,                        # R z_k + H z_t - cm_A.T_2 - alpha T_2
                           Gu, zu, B1, minus_one, U1, al | neg, none, zero,                  # G_u z_u - cm_B.T_1 - alpha U_1
                           S, zk, H, zu, B2, minus_one, U2, al | neg], axis=1).astype("<u4")  # S z_k + H z_u - cm_B.T_2 - alpha U_2
-        ctx.check(N.cg1_exact_relations_device(ctx.handle, b["pts"].ptr, n * L + C, b["rowin"].ptr, n * K, terms.tobytes(), 4 * f, x["ok"].ptr))
+        ctx.check(N.cg1_exact_relations_device(ctx.handle, b.dev.pts.ptr, n * L + C, b.dev.rowin.ptr, n * K, terms.tobytes(), 4 * f, x.ok.ptr))
         i32 = idx.astype("<u4").tobytes()
-        ctx.check(N.cg1_exact_gather_device(ctx.handle, b["rowin"].ptr, n, K * 32, i32, f, x["rowin"].ptr, K * 32, K * 32, (fields + 6 + 8) * 32, 4 * 32))
-        ctx.check(N.cg1_exact_gather_device(ctx.handle, b["pts"].ptr, n, L * 96, i32, f, x["pts"].ptr, L * 96, L * 96, 0, 0))
-        ctx.check(N.cg1_exact_gather_device(ctx.handle, b["pts"].ptr + n * L * 96, 1, 0, bytes(4 * f), f, x["rep"].ptr, C * 96, C * 96, 0, 0))
-        ctx.check(N.cg1_shuffle_rows_device(ctx.handle, ell, lg, f, x["rowin"].ptr, x["hstat"].ptr, x["pstat"].ptr, x["sc"].ptr, x["csrows"].ptr,
-                                            x["dstat"].ptr))
+        ctx.check(N.cg1_exact_gather_device(ctx.handle, b.dev.rowin.ptr, n, K * 32, i32, f, x.rowin.ptr, K * 32, K * 32, (fields + 6 + 8) * 32, 4 * 32))
+        ctx.check(N.cg1_exact_gather_device(ctx.handle, b.dev.pts.ptr, n, L * 96, i32, f, x.pts.ptr, L * 96, L * 96, 0, 0))
+        ctx.check(N.cg1_exact_gather_device(ctx.handle, b.dev.pts.ptr + n * L * 96, 1, 0, bytes(4 * f), f, x.rep.ptr, C * 96, C * 96, 0, 0))
+        ctx.check(N.cg1_shuffle_rows_device(ctx.handle, ell, lg, f, x.rowin.ptr, x.hstat.ptr, x.pstat.ptr, x.sc.ptr, x.csrows.ptr,
+                                            x.dstat.ptr))
         ctx.check(N.cg1_stream_sync(ctx.handle))
-        p_own = ctx.msm_batched_device(x["pts"], x["sc"], [j * L for j in range(f + 1)])
-        p_crs = ctx.msm_batched_device(x["rep"], x["csrows"], [j * C for j in range(f + 1)])
-        ok, dstat = x["ok"].download(4 * f), np.frombuffer(x["dstat"].download(4 * f), dtype="<i4")
-        calls += 10
-        tmp = ctypes.create_string_buffer(N.POINT_BYTES)
-        out = []
-        for j in range(f):
-            good = ok[4 * j: 4 * j + 4] == b"\x01\x01\x01\x01" and dstat[j] == 0
-            if good:
-                N.cg1_add(tmp, p_own[j], p_crs[j])
-                good = bool(N.cg1_is_identity(tmp.raw))
-            out.append(good)
-        return out, calls
+        p_own = ctx.msm_batched_device(x.pts, x.sc, [j * L for j in range(f + 1)])
+        p_crs = ctx.msm_batched_device(x.rep, x.csrows, [j * C for j in range(f + 1)])
+        ok, dstat = x.ok.download(4 * f), np.frombuffer(x.dstat.download(4 * f), dtype="<i4")
+        return [bool(ok[4 * j: 4 * j + 4] == b"\x01\x01\x01\x01" and dstat[j] == 0 and _sum_is_identity(p_own[j], p_crs[j])) for j in range(f)], 10
 
-    def _fe_lane(self, k: int, n: int):
+    def _fe_lane(self, k: int, n: int) -> _FeLane:
         """Front-end lane k: its own context (stream), device front-end handle and aux staging, created on first use."""
-        pair = self._fe[k]
-        if pair is None or pair[2].nbytes < n * 19 * 32:
-            if pair is not None:
-                cx, fe, aux_h, aux_d = pair
-                aux_h.free(); aux_d.free()
+        lane = self._fe[k]
+        if lane is None or lane.aux_h.nbytes < n * 19 * 32:
+            if lane is not None:
+                cx, fe = lane.ctx, lane.fe
+                lane.aux_h.free(); lane.aux_d.free()
             else:
                 cx = N.Context(self.ctx.device, cu_mask=range(self._cu_total - self.fe_cus, self._cu_total) if self.fe_cus else None)
                 cx.set_param("fe_prio", self.fe_prio)
                 fe = N.cg1_shuffle_fe_create(cx.handle, self.crs.ell, self.crs.lg, self.crs.affine96, self.crs.bytes)
                 if not fe:
                     raise N.NativeError("cg1_shuffle_fe_create failed")
-            pair = self._fe[k] = (cx, fe, N.PinnedBuffer(cx, n * 19 * 32), cx.alloc(n * 19 * 32))
-        return pair
+            lane = self._fe[k] = _FeLane(cx, fe, N.PinnedBuffer(cx, n * 19 * 32), cx.alloc(n * 19 * 32))
+        return lane
 
-    def _front_end_device(self, tk: dict) -> None:
+    def _front_end_device(self, tk: Ticket) -> None:
         """Stage 2 on the GPU (asynchronous): once the batch is decoded, one k_shuffle_front_end launch on the next front-end lane
         writes the row-input blocks and the front-end codes straight into the slot's device buffers."""
-        import threading
-        import time
-
         k = self._fe_next
         self._fe_next = (k + 1) % self.fe_lanes
-        tk["device_rows"] = True
-        tk["prep"] = None
-        tk["fe_done"] = threading.Event()
-        b, n = tk["slot"], tk["n"]
+        b, n = tk.slot, tk.n
 
         def job():
-            try:
-                for _ in tk["bounds"]:
-                    r = tk["chunks"].get()
-                    if isinstance(r, BaseException):
-                        raise r
-                t0 = time.perf_counter()
-                cx, fe, aux_h, aux_d = self._fe_lane(k, n)
-                aux_rec = N.cg1_shuffle_fe_aux_bytes()
-                for pa, a, cnt in _runs(tk["proofs"], self.crs.proof_bytes, 0, n):
-                    cx.check(N.cg1_shuffle_gather_aux(self.crs.handle, cnt, pa, _addr(tk["weights"]) + a * N_WEIGHTS * 32, aux_h.ptr + a * aux_rec))
-                cx.check(N.cg1_h2d(cx.handle, aux_d.ptr, aux_h.ptr, n * 19 * 32))
-                cx.check(N.cg1_shuffle_fe_enqueue(fe, cx.handle, n, b["wire"].ptr, b["pts"].ptr, aux_d.ptr, b["rowin"].ptr, b["hstat"].ptr, 0))
-                cx.check(N.cg1_stream_sync(cx.handle))
-                pre = tk["pre_status"]
-                if pre is not None and any(pre):                  # proofs rejected while packing (bad lengths): their codes win
-                    hs = (ctypes.c_int32 * n).from_buffer_copy(b["hstat"].download(4 * n))
-                    for i, s_ in enumerate(pre):
-                        if s_:
-                            hs[i] = s_
-                    b["hstat"].upload(bytes(hs))
-                tk["front_end_s"] = time.perf_counter() - t0
-            except BaseException as e:
-                tk["error"] = e
-            finally:
-                tk["fe_done"].set()
+            for _ in tk.bounds:
+                tk.next_chunk()
+            t0 = time.perf_counter()
+            cx, fe, aux_h, aux_d = self._fe_lane(k, n)
+            aux_rec = N.cg1_shuffle_fe_aux_bytes()
+            for pa, a, cnt in _runs(tk.proofs, self.crs.proof_bytes, 0, n):
+                cx.check(N.cg1_shuffle_gather_aux(self.crs.handle, cnt, pa, _addr(tk.weights) + a * N_WEIGHTS * 32, aux_h.ptr + a * aux_rec))
+            cx.check(N.cg1_h2d(cx.handle, aux_d.ptr, aux_h.ptr, n * 19 * 32))
+            cx.check(N.cg1_shuffle_fe_enqueue(fe, cx.handle, n, b.dev.wire.ptr, b.dev.pts.ptr, aux_d.ptr, b.dev.rowin.ptr, b.dev.hstat.ptr, 0))
+            cx.check(N.cg1_stream_sync(cx.handle))
+            pre = tk.pre_status
+            if pre is not None and any(pre):                  # proofs rejected while packing (bad lengths): their codes win
+                hs = (ctypes.c_int32 * n).from_buffer_copy(b.dev.hstat.download(4 * n))
+                for i, s_ in enumerate(pre):
+                    if s_:
+                        hs[i] = s_
+                b.dev.hstat.upload(bytes(hs))
+            tk.front_end_s = time.perf_counter() - t0
 
-        self._gpu_submit(job, lane=2 + k)
+        self._lanes.stage(2 + k, tk, tk.fe_done, job)
+
+    def _sibling(self, ctx, own_ctx: bool = False, **overrides) -> "ShuffleBatchVerifier":
+        """A verifier over the same CRS with this one's options, but for `overrides`; own_ctx: `ctx` was made for it and closes with it."""
+        options = dict(threads=self.threads, chunk=self.chunk, device_rows=self.device_rows, blocking_sync=self.blocking_sync, fe_lanes=self.fe_lanes,
+                       fe_prio=self.fe_prio, exact_device=self.exact_device, max_pinned_bytes=self.max_pinned_bytes)
+        v = ShuffleBatchVerifier(self.crs, ctx, **{**options, **overrides})
+        v._own_ctx = own_ctx
+        return v
 
     def _verify_stream_pipelines(self, batches, mode: str, rng):
         """verify_stream over `pipelines` child verifiers (same CRS, own contexts and threads) that take the batches in turn; verdicts
         are yielded in the order of the input."""
-        import queue
-        import threading
-        from collections import deque
-
         if self._kids is None:
             self._release_lanes()                             # (lanes a single batch may have built on this verifier itself)
-            dev = self.ctx.device
-            self._kids = [ShuffleBatchVerifier(self.crs, N.Context(dev), threads=self.threads, chunk=self.chunk, device_rows=self.device_rows,
-                                               blocking_sync=self.blocking_sync, device_front_end=True, fe_lanes=self.fe_lanes, fe_prio=self.fe_prio, pipelines=1, exact_device=self.exact_device,
-                                               max_pinned_bytes=self.max_pinned_bytes, coalesce=0)      # (the stream is coalesced once, by this verifier: a child
-                                                                                                       # waiting for a second batch to merge would starve its siblings' order)
-                          for _ in range(self.pipelines)]
-            for k in self._kids:
-                k._own_ctx = True
+            # coalesce=0: the stream is coalesced once, by this verifier: a child waiting for a second batch to merge would starve its
+            # siblings' order
+            self._kids = [self._sibling(N.Context(self.ctx.device), own_ctx=True, device_front_end=True, pipelines=1, coalesce=0) for _ in range(self.pipelines)]
         P = len(self._kids)
         depth = self.fe_lanes + 3
         in_q = [queue.Queue(maxsize=depth) for _ in range(P)]
@@ -882,12 +720,10 @@ class ShuffleBatchVerifier:
         try:
             k = 0
             for batch in batches:
-                if rng is not None:
+                if rng is not None and batch.weights is None:
                     # a caller's generator (tests, seeded runs) is used by THIS thread only, in batch order: reproducible weights, and
                     # no generator is shared between the pipelines' threads
-                    batch = tuple(batch) + (None,) * (5 - len(batch))
-                    if batch[4] is None:
-                        batch = batch[:4] + (self.draw_weights(batch[2], rng),)
+                    batch = batch.with_weights(self.draw_weights(batch.n, rng))     # (and keeps its chain plan)
                 in_q[k % P].put(batch)
                 order.append(k % P)
                 k += 1
@@ -912,20 +748,18 @@ class ShuffleBatchVerifier:
             for t in ths:
                 t.join()
 
-    def _verify_stream_device(self, batches, mode: str, rng):
+    def _verify_stream_device(self, batches, mode: str, rng, single: bool = False):
         """verify_stream with the front-end on the GPU: up to fe_lanes + 2 batches in flight (decoding | front-end launches side by
-        side | rows + merged MSM), verdicts yielded in order."""
-        from collections import deque
-
+        side | rows + merged MSM), verdicts yielded in order.  single: the caller handed over one batch, not a stream."""
         # several pipelines pay off on a STREAM of batches; one batch alone (is_valid_whisk_shuffle_proof, verify_many) runs on this
         # verifier's own lanes: no child verifiers, contexts or threads are made for it
         if self.pipelines > 1:
-            if not (isinstance(batches, (list, tuple)) and len(batches) <= 1):
+            if not single:
                 yield from self._verify_stream_pipelines(batches, mode, rng)
                 return
             if self._kids:                                    # the pipelines exist already: the batch rides the first one, in this thread
                 kid = self._kids[0]
-                for st in kid._verify_stream_device(batches, mode, rng):
+                for st in kid._verify_stream_device(batches, mode, rng, single):
                     self.last_status, self.last_stats = st, dict(kid.last_stats)
                     yield st
                 return
@@ -944,131 +778,113 @@ class ShuffleBatchVerifier:
             while inflight:
                 yield self._finish(inflight.popleft())
         finally:
-            left = [t for t in inflight if not t["done"].is_set()]
-            for t in left:
-                t["done"].wait()
+            for t in inflight:
+                t.done.wait()
 
-    def _enqueue_msm(self, tk: dict) -> None:
+    def _enqueue_msm(self, tk: Ticket) -> None:
         """Stage 3 (asynchronous, GPU thread): scalars H2D, the merged MSM, and -- if it is not the identity, or in mode
         "independent" -- the per-proof MSMs that name the invalid proofs."""
-        import time
-
         crs, ctx = self.crs, self.ctx_msm
         L, C = crs.points_per_proof, crs.ncrs
-        b, n, prep = tk["slot"], tk["n"], tk["prep"]
+        b, n = tk.slot, tk.n
 
         def gpu_stage():
-            try:
-                if tk.get("fe_done") is not None:                 # device front-end: its launch wrote the blocks and codes into the slot
-                    tk["fe_done"].wait()
-                    if tk["error"] is not None:
-                        raise tk["error"]
-                t0 = time.perf_counter()
-                ctx.check(N.cg1_copy_fence(ctx.handle))          # the scalars / input blocks queued by _front_end
-                if tk["device_rows"]:
-                    # the rows are expanded on the device, the point verdicts folded in there, the CRS rows summed behind them
-                    ctx.check(N.cg1_shuffle_rows_device(ctx.handle, crs.ell, crs.lg, n, b["rowin"].ptr, b["hstat"].ptr, b["pstat"].ptr,
-                                                        b["sc"].ptr, b["csrows"].ptr, b["dstat"].ptr))
-                    ctx.check(N.cg1_stream_sync(ctx.handle))
-                    status = list((ctypes.c_int32 * n).from_buffer_copy(b["dstat"].download(4 * n)))
+            tk.wait(tk.fe_done)                               # (device front-end: its launch wrote the blocks and codes into the slot)
+            prep = tk.prep
+            t0 = time.perf_counter()
+            ctx.check(N.cg1_copy_fence(ctx.handle))          # the scalars / input blocks queued by _front_end
+            if tk.device_rows:
+                # the rows are expanded on the device, the point verdicts folded in there, the CRS rows summed behind them
+                ctx.check(N.cg1_shuffle_rows_device(ctx.handle, crs.ell, crs.lg, n, b.dev.rowin.ptr, b.dev.hstat.ptr, b.dev.pstat.ptr,
+                                                    b.dev.sc.ptr, b.dev.csrows.ptr, b.dev.dstat.ptr))
+                ctx.check(N.cg1_stream_sync(ctx.handle))
+                status = list((ctypes.c_int32 * n).from_buffer_copy(b.dev.dstat.download(4 * n)))
+            else:
+                status = [int(prep.status[i]) for i in range(n)]
+            live = [i for i in range(n) if status[i] == 0]
+            merged_ok = None
+            if live and tk.mode == "merged":
+                merged_ok = bool(N.cg1_is_identity(ctx.msm_device(b.dev.pts, b.dev.sc, n * L + C)))
+            t1 = time.perf_counter()
+            if live and not merged_ok:
+                # independent: P_i over the proof's own points, Q_i over the CRS points; valid iff P_i + Q_i = 0
+                own = ctx.msm_batched_device(b.dev.pts, b.dev.sc, [i * L for i in range(n + 1)])
+                rep_pts = ctx.alloc(n * C * 96)
+                rep_pts.upload(crs.affine96 * n)
+                if tk.device_rows:
+                    shared = ctx.msm_batched_device(rep_pts, b.dev.csrows, [i * C for i in range(n + 1)])
                 else:
-                    status = [int(prep.status[i]) for i in range(n)]
-                live = [i for i in range(n) if status[i] == 0]
-                merged_ok = None
-                if live and tk["mode"] == "merged":
-                    merged_ok = bool(N.cg1_is_identity(ctx.msm_device(b["pts"], b["sc"], n * L + C)))
-                t1 = time.perf_counter()
-                if live and not merged_ok:
-                    # independent: P_i over the proof's own points, Q_i over the CRS points; valid iff P_i + Q_i = 0
-                    own = ctx.msm_batched_device(b["pts"], b["sc"], [i * L for i in range(n + 1)])
-                    rep_pts = ctx.alloc(n * C * 96)
-                    rep_pts.upload(crs.affine96 * n)
-                    if tk["device_rows"]:
-                        shared = ctx.msm_batched_device(rep_pts, b["csrows"], [i * C for i in range(n + 1)])
-                    else:
-                        rep_sc = ctx.alloc(n * C * 32)
-                        ctx.check(N.cg1_h2d(ctx.handle, rep_sc.ptr, prep.crs_scalars32, n * C * 32))
-                        shared = ctx.msm_batched_device(rep_pts, rep_sc, [i * C for i in range(n + 1)])
-                        rep_sc.free()
-                    rep_pts.free()
-                    tmp = ctypes.create_string_buffer(N.POINT_BYTES)
-                    for i in live:
-                        N.cg1_add(tmp, own[i], shared[i])
-                        if not N.cg1_is_identity(tmp.raw):
-                            status[i] = REJECT_EQUATION
-                # Proofs carrying a point outside G1 in the same-scalar equalities.  The reference asserts those four equalities
-                # EXACTLY (same_scalar.py:101-108), with its scalars as integers in [0, r): a random weight reduced mod r is blind
-                # to a torsion defect with probability 1/3, and -- the other direction -- torsion components that cancel in the
-                # exact equalities (the reference accepts) do NOT cancel once T_1, U_1, cm_A, cm_B carry different weights.  So a
-                # flagged proof is decided apart from the batch, whatever the weighted passes above said about it: its statement
-                # again with the same-scalar weights w1..w4 (rho[8..11]) set to ZERO -- every check the reference itself runs
-                # through its randomised MSMAccumulator, where A' = A + T_1 + U_1 is formed from the decoded points as the
-                # reference forms it -- AND the four equalities evaluated without weights on the host.
-                # (None in honest traffic.  The flags were brought back by the decompression lane: tk["sgflags"].)
-                tk["flags_done"].wait()
-                flags = tk["sgflags"]
-                n_exact, exact_path, exact_calls = 0, None, 0
-                if flags is not None and any(flags):
-                    was_live = set(live)
-                    flagged = [i for i in range(n) if i in was_live and any(flags[i * N_EXACT_POINTS: (i + 1) * N_EXACT_POINTS])]
-                    n_exact = len(flagged)
-                    on_device = bool(flagged) and tk["device_rows"] and (self.exact_device if self.exact_device is not None
-                                                                          else n_exact >= self.EXACT_DEVICE_MIN)
-                    if on_device:
-                        exact_path = "device"
-                        verdicts, exact_calls = self._decide_flagged_device(tk, flagged)
-                        for i, good in zip(flagged, verdicts):
-                            status[i] = 0 if good else REJECT_EQUATION
-                    elif flagged:
-                        exact_path, exact_calls = "host", n_exact      # one decision per proof, each a dozen native calls of its own
-                        for i in flagged:
-                            status[i] = 0 if self._decide_flagged(tk, i) else REJECT_EQUATION
-                tk["status"] = status
-                tk["stats"] = {"merged_msm_s": t1 - t0, "exact_checks": n_exact, "exact_path": exact_path, "exact_native_calls": exact_calls, "independent_s": time.perf_counter() - t1, "merged_ok": merged_ok,
-                               "front_end_s": tk.get("front_end_s", 0.0), "decompress_s": tk.get("decompress_s", 0.0), "n": n, "points": n * L + C, "pipelined": len(tk["bounds"]) > 1}
-                if tk["chain"] is not None:
-                    tk["stats"].update(decoded_points=tk["chain"]["decoded_points"], gathered_points=tk["chain"]["gathered_points"])
-            except BaseException as e:
-                tk["error"] = e
-            finally:
-                tk["done"].set()
+                    rep_sc = ctx.alloc(n * C * 32)
+                    ctx.check(N.cg1_h2d(ctx.handle, rep_sc.ptr, prep.crs_scalars32, n * C * 32))
+                    shared = ctx.msm_batched_device(rep_pts, rep_sc, [i * C for i in range(n + 1)])
+                    rep_sc.free()
+                rep_pts.free()
+                for i in live:
+                    if not _sum_is_identity(own[i], shared[i]):
+                        status[i] = REJECT_EQUATION
+            # Proofs carrying a point outside G1 in the same-scalar equalities.  The reference asserts those four equalities
+            # EXACTLY (same_scalar.py:101-108), with its scalars as integers in [0, r): a random weight reduced mod r is blind
+            # to a torsion defect with probability 1/3, and -- the other direction -- torsion components that cancel in the
+            # exact equalities (the reference accepts) do NOT cancel once T_1, U_1, cm_A, cm_B carry different weights.  So a
+            # flagged proof is decided apart from the batch, whatever the weighted passes above said about it: its statement
+            # again with the same-scalar weights w1..w4 (rho[8..11]) set to ZERO -- every check the reference itself runs
+            # through its randomised MSMAccumulator, where A' = A + T_1 + U_1 is formed from the decoded points as the
+            # reference forms it -- AND the four equalities evaluated without weights on the host.
+            # (None in honest traffic.  The flags were brought back by the decompression lane: Ticket.flags.)
+            flags = tk.flags()
+            n_exact, exact_path, exact_calls = 0, None, 0
+            if flags is not None and any(flags):
+                was_live = set(live)
+                flagged = [i for i in range(n) if i in was_live and any(flags[i * N_EXACT_POINTS: (i + 1) * N_EXACT_POINTS])]
+                n_exact = len(flagged)
+                on_device = bool(flagged) and tk.device_rows and (self.exact_device if self.exact_device is not None
+                                                                  else n_exact >= self.EXACT_DEVICE_MIN)
+                if on_device:
+                    exact_path = "device"
+                    verdicts, exact_calls = self._decide_flagged_device(tk, flagged)
+                    for i, good in zip(flagged, verdicts):
+                        status[i] = 0 if good else REJECT_EQUATION
+                elif flagged:
+                    exact_path, exact_calls = "host", n_exact      # one decision per proof, each a dozen native calls of its own
+                    for i in flagged:
+                        status[i] = 0 if self._decide_flagged(tk, i) else REJECT_EQUATION
+            tk.status = status
+            tk.stats = {"merged_msm_s": t1 - t0, "exact_checks": n_exact, "exact_path": exact_path, "exact_native_calls": exact_calls, "independent_s": time.perf_counter() - t1, "merged_ok": merged_ok,
+                        "front_end_s": tk.front_end_s, "decompress_s": tk.decompress_s, "n": n, "points": n * L + C, "pipelined": len(tk.bounds) > 1}
+            if tk.chain is not None:
+                tk.stats.update(decoded_points=tk.chain["decoded_points"], gathered_points=tk.chain["gathered_points"])
 
-        self._gpu_submit(gpu_stage, lane=1)
+        self._lanes.stage(1, tk, tk.done, gpu_stage)
 
-    def _finish(self, tk: dict) -> List[int]:
-        import time
-
-        tk["done"].wait()
-        if tk["error"] is not None:
-            raise tk["error"]
-        self.last_status = tk["status"]
-        self.last_stats = dict(tk["stats"])
-        self.last_stats["total_s"] = time.perf_counter() - tk["t0"]
-        return tk["status"]
+    def _finish(self, tk: Ticket) -> List[int]:
+        self.last_status = tk.result()
+        self.last_stats = dict(tk.stats, total_s=time.perf_counter() - tk.t0)
+        return tk.status
 
     def verify_stream(self, batches, mode: str = "merged", rng=None):
         """Verify a sequence of batches, three stages overlapped across batches: while the host front-end works on batch k,
         the GPU finishes the MSM of batch k-1 and already decompresses batch k+1.
-        `batches` yields (instances, proofs, n[, pre_status[, weights[, chain plan]]]); yields one status list (0 = valid) per batch.
+        `batches` yields (instances, proofs, n[, pre_status[, weights[, chain plan]]]) or `Batch`es; yields one status list (0 = valid) per batch.
         (The chain plan is shuffle_chain.ShuffleChainVerifier's: the batch's pre trackers are gathered from where they were decoded before.)"""
+        single = isinstance(batches, (list, tuple)) and len(batches) <= 1      # one batch on its own, not a stream
+        batches = map(Batch.of, batches)                      # the one place a caller's tuple is taken apart
         if self.device_front_end:
             if self._host_twin is not None:            # (its lanes would keep hardware queues the pipelines need)
                 self._host_twin.close()
                 self._host_twin = None
-            if self.coalesce and not (isinstance(batches, (list, tuple)) and len(batches) <= 1):
+            if self.coalesce and not single:
                 yield from self._verify_stream_coalesced(batches, mode, rng)
                 return
-            yield from self._verify_stream_device(batches, mode, rng)
+            yield from self._verify_stream_device(batches, mode, rng, single)
             return
-        it = iter(batches)
-        cur = next(it, None)
+        cur = next(batches, None)
         if cur is None:
             return
         tk = self._begin(cur, mode, rng)
         pending = tk_next = None
         try:
             while tk is not None:
-                nxt = next(it, None)
+                nxt = next(batches, None)
                 tk_next = self._begin(nxt, mode, rng, prefetched=True) if nxt is not None else None    # decompression of the next batch
                 self._front_end(tk)
                 self._enqueue_msm(tk)
@@ -1082,59 +898,26 @@ class ShuffleBatchVerifier:
         finally:
             # abandoned mid-way (an error, or the consumer stopped iterating): release the buffer slots of the batches
             # still in flight once the GPU thread has drained what was queued for them
-            left = [t for t in (pending, tk, tk_next) if t is not None and not t["done"].is_set()]
+            left = [t for t in (pending, tk, tk_next) if t is not None and not t.done.is_set()]
             if left:
-                self._gpu_submit(lambda: self._gpu_submit(lambda: [t["done"].set() for t in left], lane=1))
+                self._lanes.submit(lambda: self._lanes.submit(lambda: [t.done.set() for t in left], lane=1))
 
     def _verify_stream_coalesced(self, batches, mode: str, rng):
         """verify_stream for a process with few hardware queues (the runtime's default is 4): a front-end launch takes ~12 ms whatever it
         carries and only one or two run side by side there, so consecutive batches of the stream travel together -- up to `coalesce` proofs
         per internal batch (one front-end launch, one decoding pass, one merged MSM for all of them) -- and every caller's batch still gets
         its own status list, in order.  Batches that bring their own pre_status / weights, and batches already that large, go through
-        as they are.  (profiles/r05_verify_queues_ab.txt: 4 queues, 1 024 proofs per batch: 7.8e4 proofs/s alone, ~1.5e5 in fours.)"""
-        from collections import deque
-
-        limit = int(self.coalesce)
+        as they are (coalesce_plan).  (profiles/r05_verify_queues_ab.txt: 4 queues, 1 024 proofs per batch: 7.8e4 proofs/s alone, ~1.5e5 in fours.)"""
         groups = deque()                                        # per internal batch: the sizes of the callers' batches inside it
 
-        ib, pb = 4 * self.crs.ell * 48, self.crs.proof_bytes
+        def internal():
+            for batch, sizes in coalesce_plan(batches, int(self.coalesce), 4 * self.crs.ell * 48, self.crs.proof_bytes):
+                groups.append(sizes)
+                yield batch
 
-        def together(pend, size):
-            """the callers' batches as one internal batch, NOT copied together: the stages gather from the segments where they lie"""
-            if len(pend) == 1:
-                return pend[0]
-            for x in pend:
-                assert len(x[0]) == x[2] * ib and len(x[1]) == x[2] * pb
-            return (_Segments([(x[0], x[2]) for x in pend], ib), _Segments([(x[1], x[2]) for x in pend], pb), size)
-
-        def merged():
-            pend, size = [], 0
-            for b in batches:
-                n = b[2]
-                plain = len(b) == 3
-                if not plain or n >= limit or (pend and size + n > limit):
-                    if pend:
-                        groups.append([x[2] for x in pend])
-                        yield together(pend, size)
-                        pend, size = [], 0
-                    if not plain or n >= limit:
-                        groups.append([n])
-                        yield b
-                        continue
-                pend.append(b)
-                size += n
-                if size >= limit:
-                    groups.append([x[2] for x in pend])
-                    yield together(pend, size)
-                    pend, size = [], 0
-            if pend:
-                groups.append([x[2] for x in pend])
-                yield together(pend, size)
-
-        for st in self._verify_stream_device(merged(), mode, rng):
-            sizes = groups.popleft()
+        for st in self._verify_stream_device(internal(), mode, rng):
             lo = 0
-            for n in sizes:
+            for n in groups.popleft():
                 yield st[lo: lo + n]
                 lo += n
 
@@ -1155,19 +938,15 @@ class ShuffleBatchVerifier:
             def pieces():
                 for a in range(0, n, self.SPLIT):
                     m = min(self.SPLIT, n - a)
-                    yield (bytes(inst[a * ib: (a + m) * ib]), bytes(prf[a * pb: (a + m) * pb]), m,
-                           None if pre_status is None else list(pre_status[a: a + m]),
-                           None if w is None else bytes(w[a * N_WEIGHTS * 32: (a + m) * N_WEIGHTS * 32]))
+                    yield Batch(bytes(inst[a * ib: (a + m) * ib]), bytes(prf[a * pb: (a + m) * pb]), m,
+                                None if pre_status is None else list(pre_status[a: a + m]),
+                                None if w is None else bytes(w[a * N_WEIGHTS * 32: (a + m) * N_WEIGHTS * 32]))
 
             out: List[int] = []
             total: dict = {}
             for st in self.verify_stream(pieces(), mode=mode, rng=rng):
                 out += st
-                for k, v in (self.last_stats or {}).items():             # the call's statistics: summed over its pieces
-                    if isinstance(v, bool) or not isinstance(v, (int, float)):
-                        total[k] = v
-                    else:
-                        total[k] = total.get(k, 0) + v
+                sum_stats(total, self.last_stats)             # the call's statistics: summed over its pieces
             self.last_status, self.last_stats = out, total
             return out
         if self.device_front_end and self._fe_by_default:
@@ -1178,14 +957,13 @@ class ShuffleBatchVerifier:
             threads = self.threads or int(N.cg1_shuffle_default_threads())
             host_ms = 1.4 + 1.05 * n / max(1, min(threads, n))
             if host_ms < 12.5 + 0.03 * n:
-                if self._host_twin is None:
-                    self._host_twin = ShuffleBatchVerifier(self.crs, self._ctx if not getattr(self, "_own_ctx", False) else None, threads=self.threads,
-                                                           chunk=self.chunk, device_rows=self.device_rows, blocking_sync=self.blocking_sync, device_front_end=False, exact_device=self.exact_device)
+                if self._host_twin is None:                   # (on the caller's context, unless this verifier drives one of its own)
+                    self._host_twin = self._sibling(None if self._own_ctx else self._ctx, device_front_end=False)
                 tw = self._host_twin
                 out = tw.verify_packed(instances, proofs, n, mode=mode, rng=rng, weights=weights, pre_status=pre_status)
                 self.last_status, self.last_stats = tw.last_status, tw.last_stats
                 return out
-        return next(self.verify_stream([(instances, proofs, n, pre_status, weights)], mode=mode, rng=rng))
+        return next(self.verify_stream([Batch(instances, proofs, n, pre_status, weights)], mode=mode, rng=rng))
 
     def verify_many(self, items, mode: str = "merged", rng=None) -> List[bool]:
         """[IsValidWhiskShuffleProof(crs, pre, post, proof) for (pre, post, proof) in items] (whisk_interface.py:72-87)."""

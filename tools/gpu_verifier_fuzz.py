@@ -72,7 +72,7 @@ while time.time() - t0 < budget:
     old.ctx.set_param("fe_rows", it & 1)                       # the single pipeline alternates between the two kernel forms
     for k in range(old.fe_lanes):
         if old._fe[k] is not None:
-            old._fe[k][0].set_param("fe_rows", it & 1)
+            old._fe[k].ctx.set_param("fe_rows", it & 1)
     got1 = old.verify_packed(bytes(inst), bytes(prf), B, mode=mode, weights=bytes(w))
     rejected += sum(1 for x in want if x)
     if got != want or got1 != want:
